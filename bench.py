@@ -100,6 +100,11 @@ def parse_args():
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the 'secondary' block of the default line (Transformer processor @ config 3 with the mesh "
                          "attention's MFMA roofline, config 2, config 5: 5 steps each, behind the timed region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the prediction; with --rollout, "
+                         "the last lead time's) as DIR/output.npy in float32, rank 0 only; beyond 60 MiB a fixed, seeded "
+                         "sample of its rows.  Inputs and weights are seeded: two builds run with the same arguments can be "
+                         "compared output for output")
     return ap.parse_args()
 
 
@@ -336,6 +341,28 @@ def profile_pass(model, x, group, dtype_name: str, detail: bool = False, traffic
     if "roofline" in out and total_ms > 0:
         out["roofline"]["share_of_step"] = round(agg["linear"]["ms"] / total_ms, 3)
     return out
+
+
+DUMP_BYTES = 60 * 2**20  # --dump-outputs: every array together, .npy headers included, stays below 64 MB
+
+
+def dump_outputs(directory: str, outputs: dict) -> None:
+    """``--dump-outputs``: each tensor of ``outputs`` as ``directory/<name>.npy`` in float32.  A tensor larger than its share
+    of DUMP_BYTES is flattened to rows of its last dimension and cut to a sample of whole rows, drawn by a generator with a
+    fixed seed and sorted: the same rows on every run with the same arguments (config 3's 542 080 x 80 prediction: 196 608
+    of its rows)."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    budget = DUMP_BYTES // len(outputs)
+    for name, t in outputs.items():
+        t = t.detach()
+        if t.numel() * 4 > budget:
+            t = t.reshape(-1, t.shape[-1])
+            n = max(1, budget // (4 * t.shape[1]))
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:n].sort().values
+            t = t.index_select(0, rows.to(t.device))
+        np.save(os.path.join(directory, f"{name}.npy"), t.float().cpu().numpy())
 
 
 def _rel(a, b) -> float:
@@ -784,6 +811,8 @@ def _run(stage, args) -> int:
         marks[i + 1].record()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs is not None and rank == 0:  # before anything else runs step() again (--hipgraph: a static buffer)
+        dump_outputs(args.dump_outputs, {"output": y_timed})
     # reproducibility of the step (no kernel of the path uses atomics: identical calls give identical bits): the last timed
     # output against two more steps, outside the timed region.  Reported, not gated -- a `false` is a hazard or a race.
     run_to_run_identical = None

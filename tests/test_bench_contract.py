@@ -253,3 +253,50 @@ def test_host_threads_follow_the_cgroup_cpu_quota(tmp_path, monkeypatch):
     assert bench.host_threads() == 256
     monkeypatch.setattr(builtins, "open", fake("50000 100000\n"))
     assert bench.host_threads() == 1
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """``bench.dump_outputs`` (``--dump-outputs DIR``): float32 ``.npy`` files; an output within the budget is written
+    whole, in its own shape; config 3's prediction (542 080 x 80) is cut to whole rows of a seeded sample -- sorted, the
+    same rows on every call -- and the file stays under 64 MB."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    n = 542080
+    big = torch.arange(n, dtype=torch.float32)[:, None].expand(n, 80).reshape(1, 1, n, 80)  # every column: the row index
+    small = torch.randn(1, 1, 5248, 80).to(torch.bfloat16)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"output": big})
+    bench.dump_outputs(str(tmp_path / "c"), {"output": small})
+    a, b, c = (np.load(tmp_path / d / "output.npy") for d in ("a", "b", "c"))
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_BYTES // (4 * 80), 80) and np.array_equal(a, b)
+    rows = a[:, 0]
+    assert np.all(a == rows[:, None]) and np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < n
+    assert os.path.getsize(tmp_path / "a" / "output.npy") < 64 * 10**6
+    assert c.dtype == np.float32 and c.shape == (1, 1, 5248, 80) and np.array_equal(c, small.float().numpy())
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_same_across_runs(tmp_path):
+    """``--dump-outputs``: the prediction of the last timed step, float32, the whole config-1 output; two runs with other
+    ``--steps`` / ``--warmup`` compute the same bits (seeded inputs and weights, no atomics on the path), and ``steps`` in
+    the line is the number asked for."""
+    import numpy as np
+
+    outs = []
+    for steps, warmup in ((1, 0), (3, 1)):
+        d = tmp_path / f"s{steps}"
+        res = subprocess.run([sys.executable, BENCH, "--steps", str(steps), "--warmup", str(warmup), "--workload", "cfg1",
+                              "--no-cpu-baseline", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900,
+                             env=dict(os.environ, WORLD_SIZE="1", RANK="0"))
+        assert res.returncode == 0, res.stderr[-3000:]
+        line = _last_json(res.stdout)
+        assert line["steps"] == steps and line["warmup"] == warmup
+        assert sorted(os.listdir(d)) == ["output.npy"]
+        y = np.load(d / "output.npy")
+        assert y.dtype == np.float32 and y.shape == (1, 1, line["config"]["grid_nodes"], 80) and np.isfinite(y).all()
+        outs.append(y)
+    assert np.array_equal(outs[0], outs[1])
