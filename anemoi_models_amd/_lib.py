@@ -32,7 +32,7 @@ BF16 = 1
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_RELU = 0, 1, 2, 3
 ACT_CODES = {"Identity": ACT_NONE, "GELU": ACT_GELU, "SiLU": ACT_SILU, "ReLU": ACT_RELU}
 
-ABI_VERSION = 41
+ABI_VERSION = 42
 
 
 class GtBlockArgs(ctypes.Structure):
@@ -202,6 +202,10 @@ SIGNATURES = {
     "anemoi_gt_block_tail": (c_int, [ctypes.POINTER(GtBlockArgs), c_void_p]),
     "anemoi_gt_processor_block_forward": (c_int, [ctypes.POINTER(GtBlockArgs), c_void_p]),
     "anemoi_transformer_block_forward": (c_int, [ctypes.POINTER(TfmBlockArgs), c_void_p]),
+    "anemoi_mx_quantize": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p,
+                                   c_int64, c_int64, c_int, c_int, c_void_p]),
+    "anemoi_linear_mx": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                 c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p]),
 }
 
 _lib = None

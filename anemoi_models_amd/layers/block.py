@@ -30,6 +30,7 @@ from .conv import GraphTransformerConv
 from .mlp import MLP
 from .mlp import NativeSequential
 from .mlp import activation_class
+from .mlp import fused_activation_name
 from .mlp import linear_native
 
 
@@ -454,6 +455,36 @@ class GraphTransformerBaseBlock(BaseBlock, ABC):
             return run(y, residual=y, out_stats_eps=out_stats_eps)
         return torch.cat([run(c, residual=c) for c in y.tensor_split(num_chunks, dim=0) if c.shape[0] > 0], dim=0)
 
+    # ---- MXFP8 route (runtime.mxfp8_enabled): op by op, weights quantised once per version
+    def _mx_check(self, width: int, halo) -> None:
+        if halo is not None:
+            raise NotImplementedError("ANEMOI_AMD_MXFP8=1: the node-partitioned forward has no MXFP8 route")
+        if width % 128 != 0:
+            raise NotImplementedError(f"ANEMOI_AMD_MXFP8=1 needs block widths that are a multiple of 128, got {width}")
+
+    def _mx_node_mlp(self, y: Tensor, which: str, num_chunks: int = 1) -> Tensor:
+        """``mlp(y) + y`` for mlp = LayerNorm, Linear + act, Linear: LayerNorm + quantise in one pass, fc1 with an MXFP8
+        output, fc2 with the residual."""
+        seq = self.node_dst_mlp if which == "dst" else self.node_src_mlp
+        mods = list(seq)
+        if (len(mods) != 4 or not isinstance(mods[0], nn.LayerNorm) or not isinstance(mods[1], nn.Linear)
+                or not isinstance(mods[3], nn.Linear) or fused_activation_name(mods[2]) is None):
+            raise NotImplementedError("ANEMOI_AMD_MXFP8=1 covers node MLPs of the form LayerNorm, Linear, act, Linear")
+        ln, fc1, fc2 = mods[0], mods[1], mods[3]
+        self._mx_check(fc1.in_features, None)
+        w1 = runtime.mx_weight(self._packed, ("mlp", which, 1), [fc1.weight, fc1.bias], lambda: (fc1.weight, fc1.bias))
+        w2 = runtime.mx_weight(self._packed, ("mlp", which, 2), [fc2.weight, fc2.bias], lambda: (fc2.weight, fc2.bias))
+        ln_args = (runtime.f32c(ln.weight), runtime.f32c(ln.bias), ln.eps)
+        act = fused_activation_name(mods[2])
+
+        def run(rows: Tensor) -> Tensor:
+            h = ops.linear_mx(ops.mx_quantize(rows, ln=ln_args), w1[0], w1[1], act=act, out="mx")
+            return ops.linear_mx(h, w2[0], w2[1], residual=rows)
+
+        if num_chunks <= 1:
+            return run(y)
+        return torch.cat([run(c) for c in y.tensor_split(num_chunks, dim=0) if c.shape[0] > 0], dim=0)
+
     def _check_channels(self, dtype) -> None:
         mult = ops.k_multiple(dtype)
         width = self.num_heads * self.out_channels_conv
@@ -485,6 +516,8 @@ class GraphTransformerProcessorBlock(GraphTransformerBaseBlock):
         """
         dtype = x.dtype
         self._check_channels(dtype)
+        if runtime.mxfp8_enabled(dtype):
+            return self._native_mx(x, edge_attr_csr, plan, halo)
         c = self.num_heads * self.out_channels_conv
         xh = self._ln_begin(self.layer_norm1, x)
         up = self.fold_width(dtype)
@@ -535,6 +568,40 @@ class GraphTransformerProcessorBlock(GraphTransformerBaseBlock):
                               self.edge_dim, we, be, plan, self.num_heads)
         y = ops.linear(att, wp, bp, residual=x, stats_eps=self._mlp_ln_eps("dst", dtype))  # projection(out + x_r) + x
         return self._node_mlp(y, "dst", 1, out_stats_eps=self._next_ln_eps(dtype))
+
+    # ANEMOI_AMD_MXFP8=1 runs the x_r | q | k | v | u product on MXFP8 only when this is set; off by default, it costs the
+    # most accuracy of the covered products (profiles/r07_mxfp8.md section 5); off, the product keeps the bf16 LayerNorm fold
+    mx_sqkvu = False
+
+    def _native_mx(self, x: Tensor, edge_attr_csr: Tensor, plan: EdgePlan, halo=None) -> Tensor:
+        """The block with its four products on MXFP8: LayerNorm + quantise -> x_r | q | k | v | u; the folded edge phase
+        (bf16); quantise -> projection of [out | t] + x; the node MLP (``_mx_node_mlp``)."""
+        c = self.num_heads * self.out_channels_conv
+        self._mx_check(x.shape[1], halo)
+        self._mx_check(c, None)
+        up = self.fold_width(x.dtype)
+        if up is None:
+            raise NotImplementedError("ANEMOI_AMD_MXFP8=1 needs the folded edge kernel (head size / edge width)")
+        all4 = [self.lin_self, self.lin_query, self.lin_key, self.lin_value]
+        w_in = (runtime.mx_weight(self._packed, ("sqkvu", up), self._fold_params(all4), lambda: self._folded_rows(all4, up))
+                if self.mx_sqkvu else None)
+        w_out = runtime.mx_weight(
+            self._packed, ("projf", up), [self.lin_edge.weight, self.lin_edge.bias, self.projection.weight,
+                                          self.projection.bias],
+            lambda: (torch.cat([self.projection.weight.detach().float(), self._projection_fold(up)], dim=1),
+                     self.projection.bias))
+        ln = self.layer_norm1
+        if self.mx_sqkvu:
+            xq = ops.mx_quantize(x, ln=(runtime.f32c(ln.weight), runtime.f32c(ln.bias), ln.eps))
+            sq = ops.linear_mx(xq, w_in[0], w_in[1])  # [N, 4C + H*up] = x_r | q | k | v | u
+        else:
+            sq = self._ln_linear(self._ln_begin(ln, x), "sqkvu", lambda: self._folded_in("sqkvu", all4, x.dtype, up),
+                                 lambda: self._folded_rows(all4, up), self._fold_params(all4))
+        att = folded_edge_phase(sq[:, c:2 * c], sq[:, 2 * c:3 * c], sq[:, 3 * c:4 * c], sq[:, :c], sq[:, 4 * c:],
+                                edge_attr_csr, plan, self.num_heads, up,
+                                ld_out=ops.round_up(c + self.num_heads * up, ops.k_multiple(x.dtype)))
+        y = ops.linear_mx(ops.mx_quantize(att[:, :c + self.num_heads * up]), w_out[0], w_out[1], residual=x)
+        return self._mx_node_mlp(y, "dst")
 
     def _sharded(self, x: Tensor, edge_attr: Tensor, edge_index: Tensor, shapes: tuple, batch_size: int, model_comm_group,
                  size=None) -> Tensor:
@@ -604,6 +671,8 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
         )
         self.layer_norm2 = nn.LayerNorm(in_channels)
 
+    mx_node_mlp = True  # ANEMOI_AMD_MXFP8=1 runs node_dst_mlp on MXFP8 (the decoder's mapper turns it off)
+
     def native(self, x_src: Tensor, x_dst: Tensor, edge_attr_csr: Tensor, plan: EdgePlan, num_chunks: int = 1,
                halo=None, out_stats_eps: Optional[float] = None):
         """``out_stats_eps``: epsilon of the LayerNorm the new destination nodes enter next (its statistics then come
@@ -611,6 +680,9 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
         sources of the plan are appended by one all-to-all-v."""
         dtype = x_dst.dtype
         self._check_channels(dtype)
+        mx = runtime.mxfp8_enabled(dtype) and self.mx_node_mlp  # the destination nodes' MLP on MXFP8 (DESIGN.md 4.6)
+        if mx:
+            self._mx_check(self.node_dst_mlp[1].in_features if isinstance(self.node_dst_mlp[1], nn.Linear) else 0, halo)
         c = self.num_heads * self.out_channels_conv
         # EmbeddedRows (mappers): the rows arrive as the raw features they are embedded from; ``h_dst`` is materialised
         h_dst = x_dst.h if isinstance(x_dst, EmbeddedRows) else x_dst
@@ -638,7 +710,7 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
             del xd
             if halo is not None:
                 halo.finish(pending)
-            if num_chunks <= 1 and not self.update_src_nodes:
+            if num_chunks <= 1 and not self.update_src_nodes and not mx:
                 done = self._block_tail(sq[:, c:2 * c], kv[:, :c], kv[:, c:], sq[:, :c], sq[:, 2 * c:], edge_attr_csr, plan,
                                         h_dst, up, out_stats_eps)
                 if done is not None:
@@ -660,7 +732,10 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
         y = ops.linear(att, wp, bp, residual=h_dst,
                        stats_eps=self._mlp_ln_eps("dst", dtype) if num_chunks <= 1 else None)
         del att
-        new_dst = self._node_mlp(y, "dst", num_chunks, out_stats_eps=out_stats_eps)
+        if mx:
+            new_dst = self._mx_node_mlp(y, "dst", num_chunks)
+        else:
+            new_dst = self._node_mlp(y, "dst", num_chunks, out_stats_eps=out_stats_eps)
         if isinstance(x_src, EmbeddedRows):
             x_src = x_src.h
         new_src = self._node_mlp(x_src, "src", num_chunks) if self.update_src_nodes else x_src

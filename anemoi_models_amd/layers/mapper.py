@@ -309,6 +309,7 @@ class GraphTransformerBackwardMapper(BackwardMapperPostProcessMixin, GraphTransf
                          src_grid_size=src_grid_size, dst_grid_size=dst_grid_size)
         self.node_data_extractor = nn.Sequential(nn.LayerNorm(self.hidden_dim),
                                                  nn.Linear(self.hidden_dim, self.out_channels_dst))
+        self.proc.mx_node_mlp = False  # MXFP8 on the grid rows' MLP costs the most accuracy (profiles/r07_mxfp8.md)
 
     def pre_process(self, x, shard_shapes, model_comm_group=None):
         """Only the destination is embedded; the source already lives in the hidden space (reference :412-418)."""

@@ -342,6 +342,8 @@ class GraphTransformerProcessor(GraphEdgeMixin, BaseProcessor):
     def _block_abi_plan(self, x: Tensor, ea: Tensor, plan):
         if not self.block_abi or ops.PROFILE is not None or not x.is_cuda or x.dtype != torch.bfloat16 or x.shape[0] == 0:
             return None
+        if runtime.mxfp8_enabled(x.dtype):  # the MXFP8 route runs op by op (GraphTransformerProcessorBlock._native_mx)
+            return None
         if x.stride(1) != 1 or x.stride(0) != x.shape[1] or plan.num_edges == 0:
             return None
         params = self.__dict__.get("_abi_params")

@@ -9,6 +9,7 @@ them with CPU tensors raises.  (CPU tests of the host logic substitute this modu
 
 from __future__ import annotations
 
+from typing import NamedTuple
 from typing import Optional
 
 import torch
@@ -225,6 +226,97 @@ def linear(x: Tensor, w: Tensor, bias: Optional[Tensor] = None, *, act: str = "I
                 _lib.ACT_CODES[act], _stream())
     _lib.check(st, "anemoi_linear" if ln is None else "anemoi_linear_ln")
     return out
+
+
+class MXTensor(NamedTuple):
+    """MXFP8 rows (format: ``include/anemoi_amd.h``, "MXFP8"): ``q`` e4m3 bytes ``[rows, Kp]``, ``scales`` E8M0 bytes
+    ``[rows, Kp / 32]``, ``k`` the logical width (columns ``k .. Kp-1`` are zero padding)."""
+
+    q: Tensor
+    scales: Tensor
+    k: int
+
+
+def mx_quantize(x: Tensor, ln=None) -> MXTensor:
+    """MXFP8 of the rows of ``x`` (bf16 or f32 ``[M, K]``), K padded to a multiple of 128.
+
+    ``ln=(weight, bias, eps)`` quantises ``LayerNorm(x)`` instead, in the same row pass (statistics in f32)."""
+    _dev(x)
+    _rows(x)
+    m, k = x.shape
+    kp = round_up(k, 128)
+    q = torch.empty((m, kp), dtype=torch.uint8, device=x.device)
+    s = torch.empty((m, kp // 32), dtype=torch.uint8, device=x.device)
+    gamma = beta = None
+    eps = 0.0
+    if ln is not None:
+        gamma, beta, eps = ln
+        _dev(gamma, beta)
+        if gamma.dtype != torch.float32 or beta.dtype != torch.float32 or gamma.numel() != k or beta.numel() != k \
+                or not gamma.is_contiguous() or not beta.is_contiguous():
+            raise ValueError(f"mx_quantize: LayerNorm weight / bias must be contiguous f32 vectors of length {k}")
+    if m == 0:
+        return MXTensor(q, s, k)
+    with _Timed("mx_quantize", bytes=m * k * x.element_size() + m * (kp + kp // 32), m=m, k=k):
+        st = _lib.load().anemoi_mx_quantize(dtype_code(x.dtype), x.data_ptr(), _ld(x), _ptr(gamma), _ptr(beta),
+                                            float(eps), q.data_ptr(), kp, s.data_ptr(), kp // 32, m, k, kp, _stream())
+    _lib.check(st, "anemoi_mx_quantize")
+    return MXTensor(q, s, k)
+
+
+def linear_mx(xq: MXTensor, wq: MXTensor, bias: Optional[Tensor] = None, *, act: str = "Identity",
+              residual: Optional[Tensor] = None, out: str = "bf16"):
+    """``act(x @ w.T + bias) + residual`` from MXFP8 operands (``mx_quantize`` of the activations and of the ``[N, K]``
+    weight), f32 accumulation.  ``out="bf16"``: a bf16 ``[M, N]`` tensor; ``out="mx"``: the result as an
+    :class:`MXTensor` of width N, ready to be the next ``linear_mx``'s input.  ``residual`` is bf16 ``[M, N]``."""
+    _dev(xq.q, wq.q, bias, residual)
+    if out not in ("bf16", "mx"):
+        raise ValueError(f"linear_mx: out must be 'bf16' or 'mx', got {out!r}")
+    if act not in _lib.ACT_CODES:
+        raise RuntimeError(f"activation {act} is not supported by the MXFP8 Linear kernel")
+    if xq.k != wq.k or xq.q.shape[1] != wq.q.shape[1]:
+        raise ValueError(f"linear_mx: activations have K={xq.k} ({xq.q.shape[1]} padded), weight K={wq.k} "
+                         f"({wq.q.shape[1]} padded)")
+    if not wq.q.is_contiguous() or not wq.scales.is_contiguous():
+        raise ValueError("linear_mx: the weight's elements and scales must be contiguous")
+    for name, t in (("activations", xq), ("weight", wq)):
+        _dev(t.scales)
+        _rows(t.q)
+        _rows(t.scales)
+        if t.q.dtype != torch.uint8 or t.scales.dtype != torch.uint8 or t.q.device != xq.q.device \
+                or t.scales.device != xq.q.device:
+            raise ValueError(f"linear_mx: {name} elements and scales must be uint8 tensors on the activations' device")
+        if t.q.shape[1] % 128 or t.scales.shape != (t.q.shape[0], t.q.shape[1] // 32):
+            raise ValueError(f"linear_mx: {name} must be [rows, Kp] elements (Kp a multiple of 128) with [rows, Kp / 32] "
+                             f"scales, got {tuple(t.q.shape)} and {tuple(t.scales.shape)}")
+    if residual is not None and residual.dtype != torch.bfloat16:
+        raise ValueError("linear_mx: the residual must be bf16")
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
+        raise ValueError("linear_mx: the bias must be a contiguous f32 vector")
+    m, kp = xq.q.shape
+    n = wq.q.shape[0]
+    if residual is not None and (_rows(residual).shape != (m, n) or residual.device != xq.q.device):
+        raise ValueError(f"linear_mx: residual must be [{m}, {n}] on the activations' device, got {tuple(residual.shape)}")
+    if bias is not None and (bias.numel() < n or bias.device != xq.q.device):
+        raise ValueError(f"linear_mx: bias needs {n} entries on the activations' device, got {bias.numel()}")
+    if out == "mx":
+        npad = round_up(n, 128)
+        y = torch.empty((m, npad), dtype=torch.uint8, device=xq.q.device)
+        ys = torch.empty((m, npad // 32), dtype=torch.uint8, device=xq.q.device)
+    else:
+        y = torch.empty((m, n), dtype=torch.bfloat16, device=xq.q.device)
+        ys = None
+    if m > 0:
+        alg = m * kp * 33 // 32 + n * kp * 33 // 32 + m * n * (2 if out == "bf16" else 1) + (
+            0 if residual is None else m * n * 2)
+        with _Timed("linear_mx", flops=2 * m * n * kp, bytes=alg, m=m, n=n, k=kp):
+            st = _lib.load().anemoi_linear_mx(
+                xq.q.data_ptr(), _ld(_rows(xq.q)), xq.scales.data_ptr(), _ld(_rows(xq.scales)), wq.q.data_ptr(),
+                wq.scales.data_ptr(), _ptr(bias), _ptr(residual), 0 if residual is None else _ld(_rows(residual)),
+                int(out == "mx"), y.data_ptr(), _ld(y), _ptr(ys), 0 if ys is None else _ld(ys), m, n, kp,
+                _lib.ACT_CODES[act], _stream())
+        _lib.check(st, "anemoi_linear_mx")
+    return MXTensor(y, ys, n) if out == "mx" else y
 
 
 def edge_attr_csr(a0: Tensor, a1: Optional[Tensor], perm: Tensor, ld_out: Optional[int] = None,

@@ -628,6 +628,22 @@ def fold_layer_norm(w_rows: Tensor, bias: Optional[Tensor], gamma: Tensor, beta:
     return wp, b.contiguous(), colsum
 
 
+def mxfp8_enabled(dtype: torch.dtype) -> bool:
+    """``ANEMOI_AMD_MXFP8=1``: the GraphTransformer blocks' covered Linears run on MXFP8.  bf16
+    compute only: the f32 route is the exact parity route and ignores the switch; training never reaches the native blocks."""
+    return dtype == torch.bfloat16 and os.environ.get("ANEMOI_AMD_MXFP8", "0") == "1"
+
+
+def mx_weight(cache: "PackedWeights", key, params: Sequence[Optional[Tensor]], rows: Callable[[], tuple]):
+    """``(MXTensor of the weight rows, f32 bias or None)`` of ``rows() -> (w [N, K] f32, bias [N] f32 or None)``, quantised
+    once by ``ops.mx_quantize`` and kept until a parameter is replaced or modified in place (``PackedWeights``)."""
+    def build():
+        w, b = rows()
+        return ops.mx_quantize(w.detach().float().contiguous()), None if b is None else b.detach().float().contiguous()
+
+    return cache.get(("mxfp8",) + tuple(key), params, build)
+
+
 def embed_fold_enabled(dtype: torch.dtype) -> bool:
     """Embedding -> LayerNorm -> Linear chains of the mappers run as ONE narrow GEMM on the raw node features
     (``fold_embedded_layer_norm``; bf16 LayerNorm-fold path only; ``ANEMOI_AMD_EMBED_FOLD=0`` disables)."""

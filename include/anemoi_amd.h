@@ -655,6 +655,41 @@ typedef struct anemoi_tfm_block_args {
 } anemoi_tfm_block_args;
 int anemoi_transformer_block_forward(const anemoi_tfm_block_args* args, anemoi_stream_t stream);
 
+/*
+ * MXFP8 (OCP MX v1.0, E4M3 elements) -- opt-in inference format of csrc/mx.hip.
+ *   block    32 consecutive K-elements of one row.
+ *   scale    amax = max |v| over the block; e = floor(log2(amax)) - 8 clamped to [-127, 127] (so amax 2^-e lies in
+ *            [256, 512)); stored as the E8M0 byte e + 127.  An all-zero block has scale byte 0 and zero elements.
+ *   element  v 2^-e rounded to nearest-even into e4m3fn; |v 2^-e| > 448 saturates to +-448 (never NaN).
+ *   padding  K is padded with zero bytes (scale byte 0) up to Kp, a multiple of 128.
+ *   layout   elements [rows, Kp] uint8 (ldq bytes per row), scales [rows, Kp / 32] uint8 (lds bytes per row).
+ * The scaled MFMA (v_mfma_scale_f32_16x16x128_f8f6f4) reads this layout directly: lane l of a 16-row operand tile holds
+ * row l & 15, K bytes [16 (l >> 4), +16) and [64 + 16 (l >> 4), +16) of the 128-byte slab, and the scale of block l >> 4
+ * of row l & 15 (measured with exact data: profiles/r07_mxfp8.md).  No other internal layout exists.
+ */
+
+/* LayerNorm (optional) + MXFP8 quantisation of x [rows, K] (ldx, `dtype`) in one row pass: q [rows, Kp] (ldq), s [rows,
+ * Kp / 32] (lds).  gamma / beta f32 [K], both NULL for no LayerNorm (statistics in f32, two-pass, biased variance, eps inside
+ * the sqrt, as anemoi_layer_norm).  Kp a multiple of 128 with K <= Kp <= 4096; ldq a multiple of 16 and >= Kp, lds >= Kp / 32;
+ * columns K .. Kp-1 are written as zero bytes with scale byte 0. */
+int anemoi_mx_quantize(int dtype, const void* x, int64_t ldx, const float* gamma, const float* beta, float eps,
+                       uint8_t* q, int64_t ldq, uint8_t* s, int64_t lds, int64_t rows, int K, int Kp,
+                       anemoi_stream_t stream);
+
+/* y = act(dequant(xq) dequant(wq)^T + bias) + residual on the scaled MFMA, f32 accumulation.
+ *   xq [M, K] (ldxq) / xs [M, K / 32] (ldxs): MXFP8 activations; wq [N, K] / ws [N, K / 32]: MXFP8 weights, contiguous.
+ *   bias f32 [N] or NULL; residual bf16 [M, N] (ldr) or NULL; act an ANEMOI_ACT_* code.
+ *   out_mx = 0: y bf16 [M, N] (ldy), ys unused.
+ *   out_mx = 1: the result quantised to MXFP8 as anemoi_mx_quantize would from its f32 value: y uint8 [M, round_up(N, 128)]
+ *               (ldy bytes), ys [M, round_up(N, 128) / 32] (ldys); the padding columns are written as zeros, so the
+ *               output is the next Linear's input as it stands.
+ * Any M >= 0 (ragged tails included).  N a multiple of 16 (32 with out_mx) and K a multiple of 128, else
+ * ANEMOI_ERR_UNSUPPORTED.  ldxq a multiple of 16 and ldxs of 4; ldy a multiple of 8 (bf16) or 16 (out_mx); ldr a multiple
+ * of 8; operands 16-byte (scales 4-byte) aligned, else ANEMOI_ERR_INVALID. */
+int anemoi_linear_mx(const uint8_t* xq, int64_t ldxq, const uint8_t* xs, int64_t ldxs, const uint8_t* wq,
+                     const uint8_t* ws, const float* bias, const void* residual, int64_t ldr, int out_mx, void* y,
+                     int64_t ldy, uint8_t* ys, int64_t ldys, int64_t M, int N, int K, int act, anemoi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
