@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: mesh-node updates/sec of one full encoder -> processor -> decoder forward step.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,13 +11,16 @@ config 3 (N320 -> ico-6, 16 GraphTransformer blocks, 1024 channels, 2 x 90 input
 state / weights, bf16 storage with f32 accumulation.  One process per GPU; with N > 1 the mesh is node-partitioned
 over the ranks of one model group (strong scaling: the same single forward step is shared by all ranks).
 
-The JSON line also carries
+A plain run does only what the headline needs: build, warm-up, the K timed steps, the ``--dump-outputs`` files if asked
+and the line.  ``--full`` adds every check and every other figure; its line also carries
   roofline      the dominant kernel (fused Linear, MFMA bound): algorithmic flops / measured kernel time, live,
                 from HIP events on the launch stream in a separate instrumented pass (not inside the timed region);
   roofline_edge the fused gather/scatter edge kernel against the HBM roofline (algorithmic bytes of section 8d);
   cpu_baseline  the CPU oracle (plain PyTorch, same algorithm as the reference) timed on this host's cores on the same
                 forward (all of it by default; --cpu-blocks N runs N of the identical processor blocks and scales), with
-                the parity of this run's device results against the oracle's outputs beside it.
+                the parity of this run's device results against the oracle's outputs beside it;
+  secondary     config 3 with the Transformer processor, config 2 and config 5, each timed with its own rooflines;
+  run_to_run_identical, and with N > 1 parity_vs_single (checked BEFORE the timed steps) and exchanges.
 ``value`` / ``ms_per_step`` come from the K-step bracket the driver's contract prescribes (mean); ``ms_per_step_median``
 / ``value_at_median`` are the per-step median (device events on the launch stream, rank 0) SURVEY section 8d asks for.
 """
@@ -86,7 +89,11 @@ def parse_args():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--processor", default="GraphTransformer", choices=["GraphTransformer", "GNN", "Transformer"],
                     help="processor family (BASELINE config 5 = --workload cfg2 --processor GNN)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline with its parity gates, the rooflines of an instrumented "
+                         "forward, the secondary workloads, run_to_run_identical and, with N > 1, parity_vs_single and "
+                         "the exchange timing (--no-cpu-baseline, --cpu-blocks, --detail and --no-secondary shape these)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and its parity gates")
     ap.add_argument("--cpu-blocks", type=int, default=None,
                     help="processor blocks the CPU-baseline sample runs (default: all of them -- at config 3 the whole "
                          "forward takes ~2.5 min on the GPU box's 128 host threads and doubles as the full-size parity check; "
@@ -94,18 +101,21 @@ def parse_args():
     ap.add_argument("--rollout", type=int, default=1,
                     help="autoregressive forecasts per step (BASELINE config 4 = --rollout 4): forward, then the "
                          "in-place input update anemoi_advance_input, repeated")
-    ap.add_argument("--detail", action="store_true", help="print a per-shape kernel table to stderr")
+    ap.add_argument("--detail", action="store_true", help="print a per-shape kernel table to stderr (with --full)")
     ap.add_argument("--hipgraph", action="store_true",
                     help="replay the forward as one captured HIP graph (single GPU; pays off on the small workloads)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the 'secondary' block of the default line (Transformer processor @ config 3 with the mesh "
+                    help="skip the 'secondary' block of the --full line (Transformer processor @ config 3 with the mesh "
                          "attention's MFMA roofline, config 2, config 5: 5 steps each, behind the timed region)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (the prediction; with --rollout, "
                          "the last lead time's) as DIR/output.npy in float32, rank 0 only; beyond 60 MiB a fixed, seeded "
                          "sample of its rows.  Inputs and weights are seeded: two builds run with the same arguments can be "
                          "compared output for output")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.detail and not args.full:
+        ap.error("--detail prints the kernel table of the instrumented forward, which runs with --full only")
+    return args
 
 
 def build(workload: str, device, processor: str = "GraphTransformer", graph=None):
@@ -526,7 +536,7 @@ SECONDARY_LEGS = (
 
 
 def secondary_leg(workload: str, processor: str, device, dtype_name: str, graph=None, steps: int = 5, warmup: int = 2):
-    """One secondary workload of the default line: ``warmup`` + ``steps`` forwards bracketed by device syncs, then one
+    """One secondary workload of the --full line: ``warmup`` + ``steps`` forwards bracketed by device syncs, then one
     instrumented forward for its roofline objects (same definitions as the headline's).  Reference for the Transformer leg:
     layers/attention.py:67-112 (mesh-node MultiHeadSelfAttention), 4 * S^2 * C flops per layer against the bf16 MFMA peak."""
     model, graph, x, _ = build(workload, device, processor, graph)
@@ -557,7 +567,7 @@ def secondary_leg(workload: str, processor: str, device, dtype_name: str, graph=
 
 
 def secondary_block(device, dtype_name: str, graph_cfg3=None):
-    """``secondary`` of the default line.  A leg that fails reports ``{"error": ...}`` under its own name and never removes
+    """``secondary`` of the --full line.  A leg that fails reports ``{"error": ...}`` under its own name and never removes
     the headline; ``ANEMOI_AMD_BENCH_SECONDARY`` (comma-separated leg names) restricts the legs (tests)."""
     only = os.environ.get("ANEMOI_AMD_BENCH_SECONDARY")
     only = None if only is None else {n.strip() for n in only.split(",") if n.strip()}
@@ -744,11 +754,11 @@ def _run(stage, args) -> int:
                 ops.advance_input(x_state, y, cmap)
         return y
 
-    # N > 1: before anything is timed, the partitioned forward is held against the SAME forward unsharded on one GPU
+    # N > 1, --full: before anything is timed, the partitioned forward is held against the SAME forward unsharded on one GPU
     # (rank 0 runs it; every rank's partitioned call returns the whole gathered output, so every rank checks its own copy
     # against rank 0's reference: a wrong halo list, gather offset or edge shard shows here, not as a fast wrong number)
     parity_vs_single = None
-    if group is not None:
+    if group is not None and args.full:
         import torch.distributed as dist
 
         stage[0] = "parity_vs_single"
@@ -813,17 +823,18 @@ def _run(stage, args) -> int:
     elapsed = time.perf_counter() - t0
     if args.dump_outputs is not None and rank == 0:  # before anything else runs step() again (--hipgraph: a static buffer)
         dump_outputs(args.dump_outputs, {"output": y_timed})
-    # reproducibility of the step (no kernel of the path uses atomics: identical calls give identical bits): the last timed
-    # output against two more steps, outside the timed region.  Reported, not gated -- a `false` is a hazard or a race.
+    # --full: reproducibility of the step (no kernel of the path uses atomics: identical calls give identical bits): the last
+    # timed output against two more steps, outside the timed region.  Reported, not gated -- a `false` is a hazard or a race.
     run_to_run_identical = None
-    try:
-        if isinstance(y_timed, torch.Tensor):
-            kept = y_timed.clone()
-            run_to_run_identical = bool(all(torch.equal(kept, step()) for _ in range(2)))
-            del kept
-        fence()
-    except Exception:  # noqa: BLE001 -- the check must never cost the measurement
-        run_to_run_identical = None
+    if args.full:
+        try:
+            if isinstance(y_timed, torch.Tensor):
+                kept = y_timed.clone()
+                run_to_run_identical = bool(all(torch.equal(kept, step()) for _ in range(2)))
+                del kept
+            fence()
+        except Exception:  # noqa: BLE001 -- the check must never cost the measurement
+            run_to_run_identical = None
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     median_ms = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1]
                                                                              + per_step[len(per_step) // 2])
@@ -837,14 +848,15 @@ def _run(stage, args) -> int:
         dist.all_gather(every, t)
         rank_ms = [float(e.item()) / args.steps * 1e3 for e in every]
         elapsed = max(float(e.item()) for e in every)  # the contract's MAX over ranks
-    stage[0] = "exchange timing"
-    exchanges = exchange_timing(model, x, group, elapsed / args.steps * 1e3, share_gpu) if group is not None else None
-    stage[0] = "profile pass"
-
     ms_per_step = elapsed / args.steps * 1e3
     value = n_mesh * layers * args.rollout / (elapsed / args.steps)
-    extra = profile_pass(model, x, group, args.dtype, args.detail and rank == 0,
-                         traffic_ok=args.workload == "cfg3" and args.processor == "GraphTransformer", step_ms=ms_per_step)
+    exchanges, extra = None, {}
+    if args.full:
+        stage[0] = "exchange timing"
+        exchanges = exchange_timing(model, x, group, ms_per_step, share_gpu) if group is not None else None
+        stage[0] = "profile pass"
+        extra = profile_pass(model, x, group, args.dtype, args.detail and rank == 0,
+                             traffic_ok=args.workload == "cfg3" and args.processor == "GraphTransformer", step_ms=ms_per_step)
 
     if rank == 0:
         line = {
@@ -854,7 +866,7 @@ def _run(stage, args) -> int:
             "value_at_median": round(n_mesh * layers * args.rollout / (median_ms * 1e-3), 1),
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "bf16" if args.dtype == "bf16" else "f32", "data": "synthetic",
-            "run_to_run_identical": run_to_run_identical,
+            **({"run_to_run_identical": run_to_run_identical} if args.full else {}),
             "config": {
                 "workload": WORKLOADS[args.workload][4] + ", batch 1, 2 x 90 input vars -> 80 output vars, "
                                                           "full encoder+processor+decoder forward",
@@ -871,7 +883,8 @@ def _run(stage, args) -> int:
             line["collective_backend"] = "gloo (host-staged, debug)" if share_gpu else "nccl (RCCL)"
             line["ms_per_step_ranks"] = {"min": round(min(rank_ms), 3), "max": round(max(rank_ms), 3),
                                          "all": [round(v, 3) for v in rank_ms]}
-            line["parity_vs_single"] = parity_vs_single
+            if parity_vs_single is not None:
+                line["parity_vs_single"] = parity_vs_single
             if exchanges is not None:
                 line["exchanges"] = exchanges
         if group is not None:  # what this rank puts on the wire per forward step (rank 0's numbers; xGMI all-to-all-v)
@@ -893,7 +906,7 @@ def _run(stage, args) -> int:
                 }
         if args.processor != "GraphTransformer":
             line["config"]["workload"] = line["config"]["workload"].replace("GT blocks", f"{args.processor} blocks")
-        if not args.no_cpu_baseline and world == 1 and args.processor == "GraphTransformer":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.processor == "GraphTransformer":
             stage[0] = "cpu baseline"
             n_cpu = args.cpu_blocks if args.cpu_blocks is not None else layers
             # the device's encoder output (mesh latent, internal Morton row order -> external node order) and prediction
@@ -919,8 +932,8 @@ def _run(stage, args) -> int:
         if parity_vs_single is not None and not (parity_vs_single["finite"] and parity_vs_single["max_rel_err"] <= bound):
             failure = {"error": f"parity: partitioned forward differs from the single-GPU forward by "
                                 f"{parity_vs_single['max_rel_err']:.3e} (bound {bound:g})", "parity_vs_single": parity_vs_single}
-        if (failure is None and world == 1 and not args.no_secondary and args.workload == "cfg3" and args.dtype == "bf16"
-                and args.processor == "GraphTransformer" and args.rollout == 1 and not args.hipgraph):
+        if (failure is None and args.full and world == 1 and not args.no_secondary and args.workload == "cfg3"
+                and args.dtype == "bf16" and args.processor == "GraphTransformer" and args.rollout == 1 and not args.hipgraph):
             stage[0] = "secondary"
             graph_cfg3 = graph
             del model, x, graphed, y_timed
@@ -1023,9 +1036,9 @@ def _backend_name(group) -> str:
 
 
 def main() -> int:
-    """Runs the benchmark; any failure (process-group init, a collective, a kernel status, parity beyond its bound) ends in
-    ONE JSON error line on stdout and a non-zero exit code -- never a bare traceback the driver would have to parse, never
-    a number printed for an output nobody compared with anything."""
+    """Runs the benchmark; any failure (process-group init, a collective, a kernel status, with --full parity beyond its
+    bound) ends in ONE JSON error line on stdout and a non-zero exit code -- never a bare traceback the driver would have to
+    parse, and with --full never a number printed for an output that failed its comparison."""
     stage = Stage()
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:

@@ -1,5 +1,6 @@
-"""``bench.py``'s own contract: one JSON line; N > 1 self-validating (``parity_vs_single``, ``rccl_ranks``, per-rank step
-times); every failure ONE JSON error line + a non-zero exit code.  The N > 1 cases run the real ``bench.main()`` with the
+"""``bench.py``'s own contract: one JSON line; a plain run carries the headline alone, ``--full`` the checks and the other
+figures; N > 1 with ``--full`` self-validating (``parity_vs_single``, ``rccl_ranks``, per-rank step times); every failure
+ONE JSON error line + a non-zero exit code.  The N > 1 cases run the real ``bench.main()`` with the
 ranks as processes sharing cuda:0 over host-staged gloo (``ANEMOI_AMD_BENCH_SHARE_GPU=1``): the code path the driver's
 8-GPU run takes, minus RCCL."""
 import json
@@ -84,10 +85,10 @@ def test_bench_watchdog_thread_prints_one_error_line_and_exits_4():
 
 @pytest.mark.gpu
 def test_bench_self_launch_on_a_shared_gpu():
-    """The same command on a GPU box (the two ranks share cuda:0 over host-staged gloo): one result line, exit code 0, with
-    the N > 1 self-checks and the per-exchange timing block."""
+    """The same command with ``--full`` on a GPU box (the two ranks share cuda:0 over host-staged gloo): one result line,
+    exit code 0, with the N > 1 self-checks and the per-exchange timing block."""
     res = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "cfg1",
-                          "--dtype", "fp32", "--no-cpu-baseline"], capture_output=True, text=True, timeout=1200,
+                          "--dtype", "fp32", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=1200,
                          env=_env_without_launcher(ANEMOI_AMD_BENCH_SHARE_GPU="1"))
     assert res.returncode == 0, res.stderr[-3000:]
     out = [ln for ln in res.stdout.splitlines() if ln.strip()]
@@ -106,8 +107,8 @@ def test_bench_parity_failure_prints_the_error_line_only():
     to 1e-6 of its value (test hook) a healthy config-2 run ends with exit code 3 and ONE JSON line that carries the error and
     the measured errors -- no "metric", no "value"."""
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", ANEMOI_AMD_BENCH_PARITY_BOUND_SCALE="1e-6")
-    res = subprocess.run([sys.executable, BENCH, "--steps", "2", "--warmup", "1", "--workload", "cfg2"], capture_output=True,
-                         text=True, timeout=900, env=env)
+    res = subprocess.run([sys.executable, BENCH, "--steps", "2", "--warmup", "1", "--workload", "cfg2", "--full"],
+                         capture_output=True, text=True, timeout=900, env=env)
     assert res.returncode == 3, (res.returncode, res.stderr[-2000:])
     out = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(out) == 1, res.stdout[-3000:]
@@ -140,14 +141,14 @@ def test_bench_watchdog_ends_a_rank_whose_peer_never_arrives():
     (4, "cfg2", []),
 ])
 def test_bench_main_world_n_ranks_sharing_one_gpu(world, workload, extra):
-    """``bench.py --gpus N`` end to end (ranks share cuda:0, gloo): the line carries ``parity_vs_single`` -- the partitioned
-    forward against the unsharded one, checked BEFORE timing on every rank --, the rank count the process group really has,
-    per-rank step times, the halo summary; exit code 0."""
+    """``bench.py --gpus N --full`` end to end (ranks share cuda:0, gloo): the line carries ``parity_vs_single`` -- the
+    partitioned forward against the unsharded one, checked BEFORE timing on every rank --, the rank count the process group
+    really has, per-rank step times, the halo summary; exit code 0."""
     port = 29100 + (os.getpid() % 400)
     env = dict(os.environ, WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                ANEMOI_AMD_BENCH_SHARE_GPU="1")
     cmd = [sys.executable, BENCH, "--gpus", str(world), "--steps", "3", "--warmup", "1", "--workload", workload,
-           "--no-cpu-baseline", *extra]
+           "--full", "--no-cpu-baseline", *extra]
     procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE,
                               stderr=subprocess.PIPE, text=True) for r in range(world)]
     outs = []
@@ -300,3 +301,39 @@ def test_bench_dump_outputs_same_across_runs(tmp_path):
         assert y.dtype == np.float32 and y.shape == (1, 1, line["config"]["grid_nodes"], 80) and np.isfinite(y).all()
         outs.append(y)
     assert np.array_equal(outs[0], outs[1])
+
+
+# what a plain run leaves out: every check and every figure beyond the headline (``--full`` adds them)
+FULL_ONLY = {"roofline", "roofline_edge", "roofline_mhsa", "kernel_time_ms", "cpu_baseline", "secondary",
+             "run_to_run_identical", "parity_vs_single", "exchanges"}
+
+
+def test_bench_detail_needs_full():
+    """``--detail`` prints the kernel table of ``--full``'s instrumented forward: without ``--full`` it is refused before
+    anything runs, rather than ignored."""
+    res = subprocess.run([sys.executable, BENCH, "--detail"], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 2 and "--full" in res.stderr
+    assert not [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_prints_the_headline_alone():
+    """A plain run's line: the headline with its step counts, and none of the checks or figures ``--full`` adds; the same
+    command with ``--full`` carries them (config 1 has no secondary legs; --no-cpu-baseline: the rooflines and
+    run_to_run_identical)."""
+    lines = {}
+    for mode in ([], ["--full", "--no-cpu-baseline"]):
+        res = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "1", "--workload", "cfg1", *mode],
+                             capture_output=True, text=True, timeout=900, env=dict(os.environ, WORLD_SIZE="1", RANK="0"))
+        assert res.returncode == 0, res.stderr[-3000:]
+        out = [ln for ln in res.stdout.splitlines() if ln.strip()]
+        assert len(out) == 1, res.stdout
+        lines[bool(mode)] = json.loads(out[0])
+    plain, full = lines[False], lines[True]
+    for line in (plain, full):
+        assert line["metric"] == "mesh-node updates/sec (fwd step)" and line["unit"] == "mesh-node updates/s"
+        assert line["higher_is_better"] is True and line["dtype"] == "bf16"
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert not FULL_ONLY & set(plain), sorted(FULL_ONLY & set(plain))
+    assert full["run_to_run_identical"] is True and full["roofline"]["bound"] == "mfma" and full["kernel_time_ms"]
+    assert "cpu_baseline" not in full and "secondary" not in full

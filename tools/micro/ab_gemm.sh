@@ -20,5 +20,5 @@ for lib in $LIBS; do
   echo "== $name (TFLOP/s, two passes)"
   paste <(grep act= $OUT/bench_${name}_1.txt | awk '{print $2,$4,$6,$7,$8,$11}') <(grep act= $OUT/bench_${name}_2.txt | awk '{print $11}')
 done
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --detail > $OUT/bench_step.txt 2>&1
+python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --detail > $OUT/bench_step.txt 2>&1
 tail -1 $OUT/bench_step.txt | cut -c1-300

@@ -70,7 +70,7 @@ def one(prefix):
 
 out = {
     "_source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes) on `python3 bench.py "
-               "--steps 2 --warmup 1 --no-cpu-baseline` (config 3, bf16), mean per dispatch over all launches of the "
+               "--full --steps 2 --warmup 1 --no-cpu-baseline` (config 3, bf16), mean per dispatch over all launches of the "
                "kernel (tools/refresh_profiles.sh). Corrections per MI355X_MICROARCH.md section HBM, calibrated on this "
                "repo's own add_kernel / layer_norm_kernel (known byte counts, 16 B/lane coalesced): FETCH_SIZE reads "
                "exactly 1/2 of the bytes (x2), WRITE_SIZE is exact (x1); both in KB.",
