@@ -32,7 +32,7 @@ BF16 = 1
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_RELU = 0, 1, 2, 3
 ACT_CODES = {"Identity": ACT_NONE, "GELU": ACT_GELU, "SiLU": ACT_SILU, "ReLU": ACT_RELU}
 
-ABI_VERSION = 42
+ABI_VERSION = 43
 
 
 class GtBlockArgs(ctypes.Structure):
@@ -206,6 +206,9 @@ SIGNATURES = {
                                    c_int64, c_int64, c_int, c_int, c_void_p]),
     "anemoi_linear_mx": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                  c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p]),
+    "anemoi_split_weight": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "anemoi_linear_split": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                    c_int64, c_int, c_int, c_int, c_void_p]),
 }
 
 _lib = None

@@ -128,7 +128,7 @@ class EmbeddedRows:
         t = self._packed.get((self._tag, "embstats", self.dtype, kp, self.one_col), [self.emb.weight, self.emb.bias],
                              lambda: runtime.embedding_stats_operator(self.emb.weight, self.emb.bias, kp, self.one_col,
                                                                       self.dtype))
-        return ops.row_stats(ops.linear(self.x_aug, t, None, stats_eps=eps), eps)
+        return ops.row_stats(runtime.linear(self.x_aug, t, None, stats_eps=eps), eps)
 
 
 class BaseBlock(nn.Module, ABC):
@@ -252,14 +252,14 @@ class GraphTransformerBaseBlock(BaseBlock, ABC):
                 list(params) + [ln.weight, ln.bias, xin.emb.weight, xin.emb.bias],
                 lambda: runtime.fold_embedded_layer_norm(*rows(), ln.weight, ln.bias, xin.emb.weight, xin.emb.bias,
                                                          xa.shape[1], xin.one_col, xa.dtype))
-            return ops.linear(xa, wf, bf, ln=(stats, zero), **kw)
+            return runtime.linear(xa, wf, bf, ln=(stats, zero), **kw)
         if stats is None:
             w, b = plain()
-            return ops.linear(xin, w, b, **kw)
+            return runtime.linear(xin, w, b, **kw)
         wf, bf, cs = self._packed.get(
             (tag, "lnfold", xin.dtype), list(params) + [ln.weight, ln.bias],
             lambda: runtime.fold_layer_norm(*rows(), ln.weight, ln.bias, xin.dtype))
-        return ops.linear(xin, wf, bf, ln=(stats, cs), **kw)
+        return runtime.linear(xin, wf, bf, ln=(stats, cs), **kw)
 
     def _cat_rows(self, layers):
         """f32 ``(cat of weights, cat of biases)`` of a list of Linear layers (input of the LayerNorm fold)."""
@@ -542,7 +542,7 @@ class GraphTransformerProcessorBlock(GraphTransformerBaseBlock):
                 return done
             att = folded_edge_phase(sq[:, c:2 * c], kv[:, :c], kv[:, c:], sq[:, :c], sq[:, 2 * c:], edge_attr_csr, plan,
                                     self.num_heads, up, ld_out=wpf.shape[1])
-            y = ops.linear(att, wpf, bp, residual=x, stats_eps=self._mlp_ln_eps("dst", dtype))
+            y = runtime.linear(att, wpf, bp, residual=x, stats_eps=self._mlp_ln_eps("dst", dtype))
             return self._node_mlp(y, "dst", 1, out_stats_eps=self._next_ln_eps(dtype))
         all4 = [self.lin_self, self.lin_query, self.lin_key, self.lin_value]
         if up is not None:
@@ -558,7 +558,7 @@ class GraphTransformerProcessorBlock(GraphTransformerBaseBlock):
                                     edge_attr_csr, plan, self.num_heads, up, ld_out=wpf.shape[1])
             # projection(out + x_r) + x_skip, lin_edge part via W_t; the statistics of the MLP's LayerNorm ride on the
             # epilogue, those of the next block's layer_norm1 on the MLP's last Linear
-            y = ops.linear(att, wpf, bp, residual=x, stats_eps=self._mlp_ln_eps("dst", dtype))
+            y = runtime.linear(att, wpf, bp, residual=x, stats_eps=self._mlp_ln_eps("dst", dtype))
             return self._node_mlp(y, "dst", 1, out_stats_eps=self._next_ln_eps(dtype))
         wp, bp = self._cat_linear("proj", [self.projection], dtype)
         we, be = self._edge_params()
@@ -566,7 +566,7 @@ class GraphTransformerProcessorBlock(GraphTransformerBaseBlock):
                                [l.weight for l in all4] + [l.bias for l in all4])  # [N, 4C] = x_r | q | k | v
         att = self.conv.fused(sqkv[:, c:2 * c], sqkv[:, 2 * c:3 * c], sqkv[:, 3 * c:], sqkv[:, :c], edge_attr_csr,
                               self.edge_dim, we, be, plan, self.num_heads)
-        y = ops.linear(att, wp, bp, residual=x, stats_eps=self._mlp_ln_eps("dst", dtype))  # projection(out + x_r) + x
+        y = runtime.linear(att, wp, bp, residual=x, stats_eps=self._mlp_ln_eps("dst", dtype))  # projection(out + x_r) + x
         return self._node_mlp(y, "dst", 1, out_stats_eps=self._next_ln_eps(dtype))
 
     # ANEMOI_AMD_MXFP8=1 runs the x_r | q | k | v | u product on MXFP8 only when this is set; off by default, it costs the
@@ -729,7 +729,7 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
             att = self.conv.fused(sq[:, c:], kv[:, :c], kv[:, c:], sq[:, :c], edge_attr_csr, self.edge_dim, we, be,
                                   plan, self.num_heads)
         del sq, kv
-        y = ops.linear(att, wp, bp, residual=h_dst,
+        y = runtime.linear(att, wp, bp, residual=h_dst,
                        stats_eps=self._mlp_ln_eps("dst", dtype) if num_chunks <= 1 else None)
         del att
         if mx:
@@ -856,16 +856,16 @@ class GraphConvProcessorBlock(GraphConvBaseBlock):
                                    lambda: runtime.pack_weight([lin1.weight[:, 2 * c:]], dtype))
         b1 = None if lin1.bias is None else runtime.f32c(lin1.bias)
         if halo is None:
-            p = ops.linear(x, w_nodes, None)  # [N, 2C] = W1a x | W1b x
+            p = runtime.linear(x, w_nodes, None)  # [N, 2C] = W1a x | W1b x
             p_dst, p_src = p[:, :c], p[:, c:]
-            t = ops.linear(e_csr, w_edges, b1)
+            t = runtime.linear(e_csr, w_edges, b1)
         else:
             n_own = x.shape[0]
             p_src = torch.empty((n_own + halo.n_recv, c), dtype=dtype, device=x.device)
-            ops.linear(x, w_nodes[c:], None, out=p_src[:n_own])  # W1b x of the own rows, halo rows appended below
+            runtime.linear(x, w_nodes[c:], None, out=p_src[:n_own])  # W1b x of the own rows, halo rows appended below
             pending = halo.start(p_src, n_own)
-            p_dst = ops.linear(x, w_nodes[:c], None)
-            t = ops.linear(e_csr, w_edges, b1)
+            p_dst = runtime.linear(x, w_nodes[:c], None)
+            t = runtime.linear(e_csr, w_edges, b1)
             halo.finish(pending)
             p = None
         h = ops.gather_add_act(t, p_dst, p_src, plan.dst, plan.col, act=act1, out=t)
@@ -930,15 +930,15 @@ class GraphConvMapperBlock(GraphConvBaseBlock):
         w_edges = self._packed.get(("w1_edges", dtype), [lin1.weight],
                                    lambda: runtime.pack_weight([lin1.weight[:, 2 * c:]], dtype))
         if halo is None:
-            p_src = ops.linear(x_src, w_src, None)
+            p_src = runtime.linear(x_src, w_src, None)
             pending = None
         else:
             n_own = x_src.shape[0]
             p_src = torch.empty((n_own + halo.n_recv, c), dtype=dtype, device=x_dst.device)
-            ops.linear(x_src, w_src, None, out=p_src[:n_own])
+            runtime.linear(x_src, w_src, None, out=p_src[:n_own])
             pending = halo.start(p_src, n_own)
-        p_dst = ops.linear(x_dst, w_dst, None)
-        t = ops.linear(e_csr, w_edges, None if lin1.bias is None else runtime.f32c(lin1.bias))
+        p_dst = runtime.linear(x_dst, w_dst, None)
+        t = runtime.linear(e_csr, w_edges, None if lin1.bias is None else runtime.f32c(lin1.bias))
         if pending is not None:
             halo.finish(pending)
         h = ops.gather_add_act(t, p_dst, p_src, plan.dst, plan.col, act=act1, out=t)
@@ -1062,6 +1062,8 @@ class TransformerProcessorBlock(BaseBlock):
         mult = ops.k_multiple(dtype)
         if (not self.block_abi or ops.PROFILE is not None or not x.is_cuda or rows == 0 or x.stride(1) != 1
                 or c != att.embed_dim or c % mult != 0 or rows % batch_size != 0):
+            return None
+        if runtime.f32_linear_split(dtype):  # the C entry point calls anemoi_linear itself: the split route runs op by op
             return None
         if self._mlp is None:
             self._mlp = NativeSequential(self.mlp)

@@ -333,7 +333,7 @@ class GraphTransformerBackwardMapper(BackwardMapperPostProcessMixin, GraphTransf
             wf, bf, cs = self._packed.get(("extract", "lnfold", x_dst.dtype), [lin.weight, lin.bias, ln.weight, ln.bias],
                                           lambda: runtime.fold_layer_norm(lin.weight.detach().float(), lin.bias,
                                                                           ln.weight, ln.bias, x_dst.dtype))
-            return ops.linear(x_dst, wf, bf, out_dtype=out_dtype, ln=(ops.row_stats(x_dst, ln.eps), cs))
+            return runtime.linear(x_dst, wf, bf, out_dtype=out_dtype, ln=(ops.row_stats(x_dst, ln.eps), cs))
         h = ops.layer_norm(x_dst, runtime.f32c(ln.weight), runtime.f32c(ln.bias), ln.eps)
         return linear_native(self._packed, "extract", lin, h, out_dtype=out_dtype)
 

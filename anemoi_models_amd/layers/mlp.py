@@ -95,7 +95,7 @@ class NativeSequential:
                  start: int = 0, out_stats_eps: Optional[float] = None) -> Tensor:
         """Run steps ``start..`` (``start`` > 0: the caller has already produced the output of the earlier steps).
         ``out_stats_eps``: the result feeds a LayerNorm with this epsilon next -- the last Linear's epilogue produces
-        its row statistics (``ops.linear(stats_eps=...)``)."""
+        its row statistics (``runtime.linear(stats_eps=...)``)."""
         dtype = x.dtype
         last_linear = max(i for i, s in enumerate(self.steps) if s[0] == "linear")
         ends_with_ln = self.steps[-1][0] != "linear"  # something (LayerNorm / torch activation) follows the last Linear
@@ -115,13 +115,13 @@ class NativeSequential:
                     wf, bf, cs = self.cache.get(("lnfold", i, dtype), [m.weight, m.bias, ln.weight, ln.bias],
                                                 lambda m=m, ln=ln: runtime.fold_layer_norm(
                                                     m.weight.detach().float(), m.bias, ln.weight, ln.bias, dtype))
-                    x = ops.linear(x, wf, bf, ln=(stats, cs), **kw)
+                    x = runtime.linear(x, wf, bf, ln=(stats, cs), **kw)
                     continue
                 w = self.cache.get(("w", i, dtype), [m.weight], lambda m=m: runtime.pack_weight([m.weight], dtype))
                 b = None if m.bias is None else runtime.f32c(m.bias)
                 if x.shape[1] != w.shape[1]:
                     x = ops.convert_pad(x, dtype, w.shape[1])
-                x = ops.linear(x, w, b, **kw)
+                x = runtime.linear(x, w, b, **kw)
             elif kind == "act":
                 x = m(x)
             else:
@@ -203,4 +203,4 @@ def linear_native(cache: runtime.PackedWeights, tag: str, lin: nn.Linear, x: Ten
         if x.shape[1] != lin.in_features:
             raise ValueError(f"{tag}: input has {x.shape[1]} features, expected {lin.in_features}")
         x = ops.convert_pad(x, dtype, w.shape[1])
-    return ops.linear(x, w, b, act=act, residual=residual, out_dtype=out_dtype, stats_eps=stats_eps)
+    return runtime.linear(x, w, b, act=act, residual=residual, out_dtype=out_dtype, stats_eps=stats_eps)

@@ -228,6 +228,73 @@ def linear(x: Tensor, w: Tensor, bias: Optional[Tensor] = None, *, act: str = "I
     return out
 
 
+class SplitWeight(NamedTuple):
+    """The split-bf16 planes of an f32 ``[N, K]`` weight (``include/anemoi_amd.h``, "Split-bf16"): ``hi = bf16(w)``,
+    ``lo = bf16(w - hi)``, both contiguous bf16 ``[N, K]``."""
+
+    hi: Tensor
+    lo: Tensor
+
+
+def split_weight(w: Tensor) -> SplitWeight:
+    """``(w_hi, w_lo)`` of the f32 weight ``w`` ``[N, K]`` (unit inner stride, K a multiple of ``k_multiple(float32)``)."""
+    _dev(w)
+    _rows(w)
+    if w.dtype != torch.float32:
+        raise ValueError("split_weight: the weight must be f32")
+    n, k = w.shape
+    hi = torch.empty((n, k), dtype=torch.bfloat16, device=w.device)
+    lo = torch.empty((n, k), dtype=torch.bfloat16, device=w.device)
+    if k % k_multiple(torch.float32) != 0:
+        raise ValueError(f"split_weight: K={k} must be a multiple of {k_multiple(torch.float32)} (pad with zeros)")
+    if n == 0:
+        return SplitWeight(hi, lo)
+    with _Timed("split_weight", bytes=n * k * 8, n=n, k=k):
+        st = _lib.load().anemoi_split_weight(w.data_ptr(), _ld(w), hi.data_ptr(), lo.data_ptr(), n, k, _stream())
+    _lib.check(st, "anemoi_split_weight")
+    return SplitWeight(hi, lo)
+
+
+def linear_split(x: Tensor, planes: SplitWeight, bias: Optional[Tensor] = None, *, act: str = "Identity",
+                 residual: Optional[Tensor] = None, out: Optional[Tensor] = None, n_out: Optional[int] = None) -> Tensor:
+    """``act(x @ w.T + bias) + residual`` in f32 storage with the split-bf16 product ``x_hi w_hi + x_hi w_lo + x_lo w_hi``
+    on the bf16 MFMA (``planes = split_weight(w)``; ``x`` is split inside the kernel).  ~4e-6 relative error per Linear;
+    finite inputs below 2^126 only (see the header)."""
+    w_hi, w_lo = planes
+    _dev(x, w_hi, w_lo, bias, residual, out)
+    _rows(x)
+    if x.dtype != torch.float32:
+        raise ValueError("linear_split: activations must be f32")
+    if (w_hi.dtype != torch.bfloat16 or w_lo.dtype != torch.bfloat16 or w_hi.shape != w_lo.shape or w_hi.dim() != 2
+            or not w_hi.is_contiguous() or not w_lo.is_contiguous()):
+        raise ValueError("linear_split: planes must be two contiguous bf16 [N, K] tensors (ops.split_weight)")
+    n = w_hi.shape[0] if n_out is None else n_out
+    k = w_hi.shape[1]
+    if x.shape[1] != k:
+        raise ValueError(f"linear_split: x has {x.shape[1]} columns, weight expects {k}")
+    if not 0 < n <= w_hi.shape[0]:
+        raise ValueError(f"linear_split: n_out={n} outside the weight's {w_hi.shape[0]} rows")
+    if k % k_multiple(torch.float32) != 0:
+        raise ValueError(f"linear_split: K={k} must be a multiple of {k_multiple(torch.float32)} (pad with zeros)")
+    for name, t in (("bias", bias), ("residual", residual), ("out", out)):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"linear_split: {name} must be f32")
+    if out is None:
+        out = torch.empty((x.shape[0], n), dtype=torch.float32, device=x.device)
+    if act not in _lib.ACT_CODES:
+        raise RuntimeError(f"activation {act} is not supported by the fused Linear kernel")
+    if x.shape[0] == 0:
+        return out
+    alg = (x.shape[0] * k + n * k) * 4 + x.shape[0] * n * (4 + (0 if residual is None else 4))
+    with _Timed("linear_split", flops=2 * x.shape[0] * n * k, bytes=alg, m=x.shape[0], n=n, k=k):
+        st = _lib.load().anemoi_linear_split(
+            x.data_ptr(), _ld(x), w_hi.data_ptr(), w_lo.data_ptr(), _ptr(bias), _ptr(residual),
+            0 if residual is None else _ld(_rows(residual)), out.data_ptr(), _ld(_rows(out)), x.shape[0], n, k,
+            _lib.ACT_CODES[act], _stream())
+    _lib.check(st, "anemoi_linear_split")
+    return out
+
+
 class MXTensor(NamedTuple):
     """MXFP8 rows (format: ``include/anemoi_amd.h``, "MXFP8"): ``q`` e4m3 bytes ``[rows, Kp]``, ``scales`` E8M0 bytes
     ``[rows, Kp / 32]``, ``k`` the logical width (columns ``k .. Kp-1`` are zero padding)."""

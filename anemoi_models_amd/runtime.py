@@ -644,6 +644,58 @@ def mx_weight(cache: "PackedWeights", key, params: Sequence[Optional[Tensor]], r
     return cache.get(("mxfp8",) + tuple(key), params, build)
 
 
+def f32_linear_split(dtype: torch.dtype) -> bool:
+    """``ANEMOI_AMD_F32_LINEAR=bf16x3``: the f32 inference route runs its Linears on the split-bf16 kernel (DESIGN.md
+    section 4.7).  Unset / ``exact``: the exact f32 MFMA.  Read per call; bf16 compute ignores the switch, and so does
+    everything under autograd (``autograd.py`` calls ``ops.linear`` itself)."""
+    mode = os.environ.get("ANEMOI_AMD_F32_LINEAR", "exact")
+    if mode not in ("exact", "bf16x3"):
+        raise ValueError(f"ANEMOI_AMD_F32_LINEAR={mode!r}: expected 'exact' or 'bf16x3'")
+    return mode == "bf16x3" and dtype == torch.float32
+
+
+def split_route(m: int, n: int, k: int) -> bool:
+    """The ONE shape rule of the split-bf16 route: which f32 Linears ``[m, k] x [n, k]`` take it when the switch is on
+    (DESIGN.md section 4.7 lists what it excludes and why)."""
+    return k >= SPLIT_MIN_K
+
+
+SPLIT_MIN_K = 32  # every K the f32 route pads to: nothing is excluded (profiles/r08_bf16x3.md)
+
+
+def split_planes(w: Tensor) -> "ops.SplitWeight":
+    """``ops.split_weight(w)`` of a packed f32 weight, made once per (storage pointer, in-place version) -- the idiom of
+    ``ops._carry_stats``.  The record lives on the packed tensor (on its base for a row slice), so it goes when
+    ``PackedWeights`` rebuilds the weight after an optimiser step / ``load_state_dict``; an in-place write to the packed
+    tensor itself bumps the version and the planes are rebuilt."""
+    owner = w._base if w._base is not None else w
+    store = owner.__dict__.get("_anemoi_split")
+    if store is None:
+        store = owner._anemoi_split = {}
+    key = (w.storage_offset(), tuple(w.shape), tuple(w.stride()))
+    hit = store.get(key)
+    if hit is not None and hit[0] == (w.data_ptr(), w._version):
+        return hit[1]
+    with torch.no_grad():
+        planes = ops.split_weight(w)
+    store[key] = ((w.data_ptr(), w._version), planes)
+    return planes
+
+
+def linear(x: Tensor, w: Tensor, bias: Optional[Tensor] = None, *, act: str = "Identity",
+           residual: Optional[Tensor] = None, out: Optional[Tensor] = None, out_dtype: Optional[torch.dtype] = None,
+           n_out: Optional[int] = None, ln=None, stats_eps: Optional[float] = None) -> Tensor:
+    """``ops.linear`` of the inference layers: with ``ANEMOI_AMD_F32_LINEAR=bf16x3`` an f32 product that ``split_route``
+    admits runs on ``ops.linear_split`` (planes from ``split_planes(w)``); ``stats_eps`` is dropped on that route
+    (``ops.row_stats`` then computes the statistics).  Everything else is ``ops.linear`` unchanged."""
+    if (x.dtype == torch.float32 and f32_linear_split(x.dtype) and ln is None and w.dtype == torch.float32
+            and out_dtype in (None, torch.float32) and (out is None or out.dtype == torch.float32)
+            and split_route(x.shape[0], w.shape[0] if n_out is None else n_out, w.shape[1])):
+        return ops.linear_split(x, split_planes(w), bias, act=act, residual=residual, out=out, n_out=n_out)
+    return ops.linear(x, w, bias, act=act, residual=residual, out=out, out_dtype=out_dtype, n_out=n_out, ln=ln,
+                      stats_eps=stats_eps)
+
+
 def embed_fold_enabled(dtype: torch.dtype) -> bool:
     """Embedding -> LayerNorm -> Linear chains of the mappers run as ONE narrow GEMM on the raw node features
     (``fold_embedded_layer_norm``; bf16 LayerNorm-fold path only; ``ANEMOI_AMD_EMBED_FOLD=0`` disables)."""

@@ -690,6 +690,27 @@ int anemoi_linear_mx(const uint8_t* xq, int64_t ldxq, const uint8_t* xs, int64_t
                      const uint8_t* ws, const float* bias, const void* residual, int64_t ldr, int out_mx, void* y,
                      int64_t ldy, uint8_t* ys, int64_t ldys, int64_t M, int N, int K, int act, anemoi_stream_t stream);
 
+/*
+ * Split-bf16 ("bf16x3") Linear -- opt-in arithmetic of the f32 inference route (csrc/gemm_split.hip).
+ *   split    v = hi + lo (+ a remainder below 2^-16 |v|): hi = bf16(v), lo = bf16(v - float(hi)), round to nearest even both.
+ *   product  x W^T ~= x_hi W_hi^T + x_hi W_lo^T + x_lo W_hi^T on the bf16 MFMA, one f32 accumulator (x_lo W_lo^T dropped):
+ *            ~4e-6 rms relative error per Linear (exact f32 kernel 3e-7, bf16 operands 2e-3).
+ *   domain   finite values with |v| < 2^126: bf16(v) of a value next to the f32 maximum is infinite and v - hi then NaN, and
+ *            +-infinity in x or W gives NaN where anemoi_linear gives +-infinity.  NaN in -> NaN out holds.
+ */
+
+/* The two bf16 planes w_hi, w_lo [N, K] (contiguous) of the f32 weight w [N, K] (ldw).  K a multiple of 32 (the f32 route's
+ * K padding), w and the planes 16-byte aligned, ldw a multiple of 4, else ANEMOI_ERR_INVALID.  N = 0 is a no-op. */
+int anemoi_split_weight(const float* w, int64_t ldw, void* w_hi, void* w_lo, int64_t N, int K, anemoi_stream_t stream);
+
+/* y = act(x W^T + bias) + residual with the split product above.  x f32 [M, K] (ldx) is split inside the kernel; w_hi / w_lo
+ * are the planes of anemoi_split_weight; bias f32 [N] or NULL; residual f32 [M, N] (ldr) or NULL; y f32 [M, N] (ldy); act an
+ * ANEMOI_ACT_* code (GELU in the erf form of the f32 kernel).  Any M >= 0 and N > 0 (ragged tiles included); K a multiple of
+ * 32, x and the planes 16-byte aligned and ldx a multiple of 4, else ANEMOI_ERR_INVALID (checked before any launch). */
+int anemoi_linear_split(const float* x, int64_t ldx, const void* w_hi, const void* w_lo, const float* bias,
+                        const float* residual, int64_t ldr, float* y, int64_t ldy, int64_t M, int N, int K, int act,
+                        anemoi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
