@@ -692,6 +692,9 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
         kv_args = ("kv", lambda: self._cat_linear("kv", kv_layers, dtype), lambda: self._cat_rows(kv_layers),
                    [l.weight for l in kv_layers] + [l.bias for l in kv_layers])
         xs = self._ln_begin(self.layer_norm1, x_src)
+        raw = None if (halo is not None or num_chunks > 1 or mx) else self._raw_source_weights(x_src, dtype)
+        if raw is not None:
+            return x_src.h, self._native_raw_sources(x_src, xs[1], x_dst, h_dst, edge_attr_csr, plan, raw, out_stats_eps)
         if halo is None:
             kv = self._ln_linear(xs, *kv_args)  # [N_src, 2C] = k | v
         else:
@@ -740,6 +743,77 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
             x_src = x_src.h
         new_src = self._node_mlp(x_src, "src", num_chunks) if self.update_src_nodes else x_src
         return new_src, new_dst
+
+    # ---- sources given as raw rows: k | v are never formed ("raw-row encoder")
+    RAW_ROWS_DEFAULT = "1"  # ANEMOI_AMD_EDGE_RAW=0: the k | v product on every source row + the folded edge kernel (A/B)
+
+    def _raw_source_weights(self, x_src, dtype):
+        """``(W_qt [H, Ks, D], W_g [H, D, Ks], sum_col)`` when this block can attend over the raw source rows, else ``None``.
+
+        With ``F = [F_k; F_v]`` and ``b' = [b_k; b_v]`` the embedding- and LayerNorm-folded k | v operator of
+        ``runtime.fold_embedded_layer_norm`` (``k_j = rstd_j F_k x_j + b_k``): ``W_qt[h] = F_k[h]^T`` carries a query to
+        the raw space, ``W_g[h] = F_v[h]`` brings the aggregate back, with ``b_v[h]`` in column ``sum_col`` -- a zero
+        column of the raw rows where the edge kernel leaves ``sum_j alpha_ij``.  They depend on parameters only."""
+        h, d = self.num_heads, self.out_channels_conv
+        if (not isinstance(x_src, EmbeddedRows) or x_src.h is not None or self.update_src_nodes
+                or dtype != torch.bfloat16 or not x_src.x_aug.is_cuda
+                or os.environ.get("ANEMOI_AMD_EDGE_RAW", self.RAW_ROWS_DEFAULT) == "0"):
+            return None
+        ks, k_in = x_src.x_aug.shape[1], x_src.emb.in_features
+        sum_col = ks - 1 if x_src.one_col != ks - 1 else ks - 2
+        if self.fold_width(dtype) is None or h != 16 or ks not in (64, 128, 256) or sum_col < k_in:
+            return None
+        kv_layers = [self.lin_key, self.lin_value]
+        ln, emb = self.layer_norm1, x_src.emb
+
+        def build():
+            f, b, _ = runtime.fold_embedded_layer_norm(*self._cat_rows(kv_layers), ln.weight, ln.bias, emb.weight,
+                                                       emb.bias, ks, x_src.one_col, torch.float32)
+            c = h * d
+            w_qt = f[:c].view(h, d, ks).transpose(1, 2)
+            w_g = f[c:].view(h, d, ks).clone()
+            w_g[:, :, sum_col] = b[c:].view(h, d)
+            if d % ops.k_multiple(dtype) != 0:
+                # heads narrower than a K slab: the same two products as block-diagonal weights of ONE plain Linear each
+                # ([H*Ks, C] and [C, H*Ks]; small models only -- the zeros cost H x the multiply-adds)
+                w_qt, w_g = torch.block_diag(*w_qt), torch.block_diag(*w_g)
+            return w_qt.to(dtype).contiguous(), w_g.to(dtype).contiguous(), sum_col
+
+        return self._packed.get(("kv", "rawrows", dtype, ks, x_src.one_col, x_src._tag),
+                                [l.weight for l in kv_layers] + [l.bias for l in kv_layers]
+                                + [ln.weight, ln.bias, emb.weight, emb.bias], build)
+
+    def _native_raw_sources(self, x_src, src_stats: Tensor, x_dst, h_dst: Tensor, edge_attr_csr: Tensor, plan, raw,
+                            out_stats_eps: Optional[float]) -> Tensor:
+        """The block on raw source rows: ``x_r | q | u`` as before, ``q -> qt`` (one launch over the heads), the raw-row
+        edge kernel, ``g -> sum alpha v`` (one launch over the heads) ``+ x_r``, then projection and node MLP unchanged."""
+        dtype = x_dst.dtype
+        c, h = self.num_heads * self.out_channels_conv, self.num_heads
+        w_qt, w_g, sum_col = raw
+        up = self.fold_width(dtype)
+        sq_layers = [self.lin_self, self.lin_query]
+        wp, bp = self._folded_out(dtype, up)
+        sq = self._ln_linear(self._ln_begin(self.layer_norm2, x_dst), "squ",
+                             lambda: self._folded_in("squ", sq_layers, dtype, up),
+                             lambda: self._folded_rows(sq_layers, up), self._fold_params(sq_layers))  # x_r | q | u
+        per_head = w_qt.dim() == 3
+        qt = ops.linear_heads(sq[:, c:2 * c], w_qt) if per_head else runtime.linear(sq[:, c:2 * c], w_qt)
+        att = torch.empty((sq.shape[0], wp.shape[1]), dtype=dtype, device=sq.device)
+        if wp.shape[1] > c + h * up:
+            att[:, c + h * up:].zero_()
+        g = ops.gt_edge_attention_raw(qt, x_src.x_aug, src_stats, sq[:, 2 * c:2 * c + h * up], edge_attr_csr, plan.rowptr,
+                                      plan.col, h, self.out_channels_conv, up, sum_col, att[:, c:c + h * up])
+        del qt
+        if per_head:
+            ops.linear_heads(g, w_g, out=att[:, :c])
+            ops.add(att[:, :c], sq[:, :c], out=att[:, :c])
+        else:
+            runtime.linear(g, w_g, residual=sq[:, :c], out=att[:, :c])
+        del g
+        del sq
+        y = runtime.linear(att, wp, bp, residual=h_dst, stats_eps=self._mlp_ln_eps("dst", dtype))
+        del att
+        return self._node_mlp(y, "dst", 1, out_stats_eps=out_stats_eps)
 
     def _sharded(self, x, edge_attr: Tensor, edge_index: Tensor, shapes: tuple, batch_size: int, model_comm_group, size=None):
         """The reference's module-level protocol across a model group (layers/block.py:479-550): row shards of the source

@@ -528,6 +528,74 @@ def gt_edge_attention_folded(q: Tensor, k: Tensor, v: Tensor, x_r: Optional[Tens
     return out
 
 
+def linear_heads(x: Tensor, w: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """``H`` independent products ``out[:, h*N:(h+1)*N] = x[:, h*K:(h+1)*K] @ w[h].T`` as ONE launch
+    (``anemoi_linear_batched``; no bias / activation).  ``w`` is contiguous ``[H, N, K]`` in x's dtype; ``x`` / ``out`` are
+    row-major ``[M, >= H*K]`` / ``[M, >= H*N]`` slices.  The small products on either side of the raw-row edge phase."""
+    _dev(x, w, out)
+    _rows(x)
+    if w.dim() != 3 or w.dtype != x.dtype or not w.is_contiguous():
+        raise ValueError("linear_heads: weight must be contiguous [H, N, K] in the activation dtype")
+    h, n, k = w.shape
+    if x.shape[1] < h * k:
+        raise ValueError(f"linear_heads: x has {x.shape[1]} columns, {h} heads of {k} expected")
+    if out is None:
+        out = torch.empty((x.shape[0], h * n), dtype=x.dtype, device=x.device)
+    if _rows(out).shape[1] < h * n or out.dtype != x.dtype or out.shape[0] != x.shape[0]:
+        raise ValueError("linear_heads: out must be [M, >= H*N] in the activation dtype")
+    m = x.shape[0]
+    if m == 0:
+        return out
+    code = dtype_code(x.dtype)
+    with _Timed("linear", flops=2 * m * h * n * k, bytes=(m * h * (k + n) + h * n * k) * x.element_size(), m=m, n=h * n,
+                k=k, heads=h):
+        st = _lib.load().anemoi_linear_batched(code, code, x.data_ptr(), _ld(x), k, w.data_ptr(), n * k, out.data_ptr(),
+                                               _ld(out), n, h, m, n, k, _stream())
+    _lib.check(st, "anemoi_linear_batched")
+    return out
+
+
+def gt_edge_attention_raw(qt: Tensor, x_raw: Tensor, src_stats: Tensor, u: Tensor, edge_attr: Tensor, rowptr: Tensor,
+                          col: Tensor, num_heads: int, head_dim: int, up: int, sum_col: int, t_out: Tensor,
+                          g: Optional[Tensor] = None) -> Tensor:
+    """Folded edge phase on RAW source rows (``anemoi_gt_edge_attention_raw``, bf16): returns ``g [n_dst, H*Ks]`` with
+    ``g[i, h] = sum_j alpha_ij,h rstd_j x_j`` (column ``sum_col`` of every head: ``sum_j alpha_ij,h``) and writes
+    ``t [n_dst, H*up]`` into ``t_out``.  ``qt [n_dst, H*Ks]`` are the queries carried to the raw space
+    (``linear_heads(q, A_k^T)``), ``x_raw [n_src, Ks]`` the raw rows, ``src_stats = row_stats`` of their embedding."""
+    _dev(qt, x_raw, src_stats, u, edge_attr, rowptr, col, t_out, g)
+    n_dst, ks = _rows(qt).shape[0], _rows(x_raw).shape[1]
+    if qt.dtype != torch.bfloat16 or x_raw.dtype != torch.bfloat16 or u.dtype != torch.bfloat16 or t_out.dtype != torch.bfloat16:
+        raise NotImplementedError("gt_edge_attention_raw: bf16 only")
+    if qt.shape[1] != num_heads * ks:
+        raise ValueError(f"gt_edge_attention_raw: qt has {qt.shape[1]} columns, {num_heads} heads of {ks} expected")
+    if (src_stats.shape != (x_raw.shape[0], 2) or src_stats.dtype != torch.float32 or not src_stats.is_contiguous()):
+        raise ValueError("gt_edge_attention_raw: src_stats must be the contiguous [n_src, 2] f32 result of row_stats")
+    if rowptr.dtype != torch.int32 or col.dtype != torch.int32 or rowptr.shape[0] != n_dst + 1:
+        raise ValueError("gt_edge_attention_raw: rowptr/col must be int32 with rowptr of length n_dst + 1")
+    if edge_attr.shape[0] != col.shape[0] or (col.shape[0] > 0 and (edge_attr.shape[1] != up or
+                                                                      not edge_attr.is_contiguous())):
+        raise ValueError("gt_edge_attention_raw: edge_attr must be contiguous [E, up]")
+    if _rows(u).shape != (n_dst, num_heads * up) or _rows(t_out).shape[0] != n_dst or t_out.shape[1] < num_heads * up:
+        raise ValueError("gt_edge_attention_raw: u / t_out must be [n_dst, H*up]")
+    if g is None:
+        g = torch.empty((n_dst, num_heads * ks), dtype=qt.dtype, device=qt.device)
+    if col.shape[0] == 0:
+        col = torch.zeros(1, dtype=torch.int32, device=qt.device)
+        edge_attr = torch.zeros((1, up), dtype=torch.float32, device=qt.device)
+    # algorithmic bytes: every edge gathers one raw row, its source's rstd, its attribute row and its source id; qt in,
+    # g out, the row pointers.  (+ u read, t written: the operands of the lin_edge fusion, as the other folded kernels)
+    alg_bytes = (col.shape[0] * (ks * 2 + 4 + up * 4 + 4) + 2 * n_dst * num_heads * ks * 2 + (n_dst + 1) * 4)
+    fused_bytes = alg_bytes + n_dst * 2 * num_heads * up * 2
+    with _Timed("gt_edge_attention", bytes=alg_bytes, fused_bytes=fused_bytes, n_dst=n_dst, n_src=x_raw.shape[0],
+                edges=col.shape[0], raw_rows=ks):
+        st = _lib.load().anemoi_gt_edge_attention_raw(
+            qt.data_ptr(), _ld(qt), x_raw.data_ptr(), _ld(x_raw), src_stats.data_ptr(), u.data_ptr(), _ld(u),
+            edge_attr.data_ptr(), up, rowptr.data_ptr(), col.data_ptr(), g.data_ptr(), _ld(_rows(g)), t_out.data_ptr(),
+            _ld(t_out), n_dst, num_heads, ks, head_dim, sum_col, _stream())
+    _lib.check(st, "anemoi_gt_edge_attention_raw")
+    return g
+
+
 def gt_conv(q: Tensor, k: Tensor, v: Tensor, edges_csr: Tensor, rowptr: Tensor, col: Tensor, num_heads: int,
             x_r: Optional[Tensor] = None, lse: Optional[Tensor] = None, dropout_p: float = 0.0, dropout_seed: int = 0,
             seed_dev: Optional[Tensor] = None) -> Tensor:

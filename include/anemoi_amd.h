@@ -169,6 +169,26 @@ int anemoi_gt_edge_attention_folded(int dtype, const void* q, int64_t ldq, const
                                     int64_t n_dst, int C, int H, anemoi_stream_t stream);
 
 /*
+ * The folded edge phase for sources given as the RAW rows they are embedded from (bf16; the encoder's grid nodes):
+ * with k_j,h = rstd_j A_k,h x_j + b_k,h and v_j,h = rstd_j A_v,h x_j + b_v,h (embedding and LayerNorm folded into the
+ * k | v weights, the mean removed algebraically), both products move to the destination side:
+ *   s_ij,h = (rstd_j qt_i,h . x_j + u_i,h . a'_ij) / sqrt(D)      qt_i,h = A_k,h^T q_i,h  (Ks values; q . b_k is constant
+ *                                                                over a destination's in-edges and drops out of alpha)
+ *   g_i,h  = sum_j alpha_ij,h rstd_j x_j                          -> sum_j alpha v_j,h = A_v,h g_i,h + b_v,h sum_j alpha
+ * qt [n_dst, H, Ks] (ldqt) and g [n_dst, H, Ks] (ldg) bracket the kernel; x [n_src, Ks] (ldx) are the raw rows,
+ * src_stats [n_src, 2] f32 their {rstd, -mean rstd} (anemoi_row_stats layout; only rstd is read).  Column sum_col of
+ * every head of g (a column where x is zero; -1: none) receives sum_j alpha_ij,h (1, or 0 without in-edges), so that
+ * b_v rides as one more weight column of the product that follows.  u, edge_attr, up, rowptr, col and t [n_dst, H, up]
+ * (ldt) = sum_j alpha a'_ij as in anemoi_gt_edge_attention_folded; alpha includes the 1e-16 of the normaliser.
+ * H = 16, Ks = 64, 128 or 256, up = 4, 8, 12 or 16; qt, x, g 16-byte aligned rows.  One wave per destination on MFMA, no
+ * atomics, run-to-run bit-identical.
+ */
+int anemoi_gt_edge_attention_raw(const void* qt, int64_t ldqt, const void* x, int64_t ldx, const float* src_stats,
+                                 const void* u, int64_t ldu, const float* edge_attr, int up, const int32_t* rowptr,
+                                 const int32_t* col, void* g, int64_t ldg, void* t, int64_t ldt, int64_t n_dst, int H,
+                                 int Ks, int D, int sum_col, anemoi_stream_t stream);
+
+/*
  * anemoi_gt_edge_attention_folded on a graph whose destinations all have exactly three in-edges, stored as CSR with
  * rowptr[d] = 3 d (the mesh -> grid decoder of the reference, layers/mapper.py:348-418, on anemoi-graphs' 3-nearest-neighbour
  * edges): consecutive destinations fed by the SAME three sources form a run and share one gather of the three k / v rows.
