@@ -28,11 +28,13 @@ ANEMOI_ERR_LAUNCH = 3
 
 F32 = 0
 BF16 = 1
+I32 = 2  # launch-trail records only
+U8 = 3
 
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_RELU = 0, 1, 2, 3
 ACT_CODES = {"Identity": ACT_NONE, "GELU": ACT_GELU, "SiLU": ACT_SILU, "ReLU": ACT_RELU}
 
-ABI_VERSION = 44
+ABI_VERSION = 45
 
 
 class GtBlockArgs(ctypes.Structure):
@@ -212,6 +214,11 @@ SIGNATURES = {
     "anemoi_split_weight": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "anemoi_linear_split": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
                                     c_int64, c_int, c_int, c_int, c_void_p]),
+    "anemoi_trail_begin": (c_int, [c_void_p, c_int64]),
+    "anemoi_trail_end": (c_int, [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
+    "anemoi_trail_entry": (c_int, [c_int64, ctypes.POINTER(c_char_p), ctypes.POINTER(c_int), ctypes.POINTER(c_int64),
+                                   ctypes.POINTER(c_int64)]),
+    "anemoi_trail_note": (c_int, [c_char_p, c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
 }
 
 _lib = None

@@ -20,6 +20,7 @@
 #include <utility>
 
 #include "common.hpp"
+#include "trail.hpp"
 
 #ifndef ANEMOI_LAB_MHSA8_PAD
 #define ANEMOI_LAB_MHSA8_PAD 0  // lab switch: full wait states behind the eight-wave kernel's S^T products (see there)
@@ -1750,6 +1751,7 @@ int anemoi_mhsa(int dtype, const void* qkv, int64_t ld, void* out, int64_t ldo, 
   ANEMOI_REQUIRE(ld >= 3 * (int64_t)C && ldo >= C, ANEMOI_ERR_INVALID, "anemoi_mhsa: leading dimension too small");
   hipStream_t st = as_stream(stream);
   const float scale = 1.0f / sqrtf((float)D);
+  const int64_t units_all = (int64_t)B * S * H;  // entries of lse
   ANEMOI_REQUIRE(dropout_p >= 0.f && dropout_p <= 1.f, ANEMOI_ERR_INVALID, "anemoi_mhsa: dropout_p %g outside [0, 1]",
                  (double)dropout_p);
   ANEMOI_REQUIRE(dropout_h0 >= 0 && (dropout_h_total == 0 || dropout_h0 + H <= dropout_h_total), ANEMOI_ERR_INVALID,
@@ -1824,7 +1826,11 @@ int anemoi_mhsa(int dtype, const void* qkv, int64_t ld, void* out, int64_t ldo, 
       else ANEMOI_MHSA_FWD(32, false);
     }
 #undef ANEMOI_MHSA_FWD
-    return check_launch("anemoi_mhsa(bf16, MFMA)");
+    {
+      int rc = trail::note(check_launch("anemoi_mhsa(bf16, MFMA)"), "anemoi_mhsa", "out", dtype, out, ldo, (int64_t)B * S, C, st);
+      if (lse != nullptr) rc = trail::note(rc, "anemoi_mhsa", "lse", ANEMOI_F32, lse, units_all, 1, units_all, st);
+      return rc;
+    }
   }
   ANEMOI_REQUIRE(D <= 128, ANEMOI_ERR_UNSUPPORTED, "anemoi_mhsa: head size %d > 128", D);
   const int64_t units = (int64_t)B * S * H;
@@ -1845,7 +1851,11 @@ int anemoi_mhsa(int dtype, const void* qkv, int64_t ld, void* out, int64_t ldo, 
     return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_mhsa: dtype %d", dtype);
   }
 #undef GEN
-  return check_launch("anemoi_mhsa(generic)");
+  {
+    int rc = trail::note(check_launch("anemoi_mhsa(generic)"), "anemoi_mhsa", "out", dtype, out, ldo, (int64_t)B * S, C, st);
+    if (lse != nullptr) rc = trail::note(rc, "anemoi_mhsa", "lse", ANEMOI_F32, lse, units_all, 1, units_all, st);
+    return rc;
+  }
 }
 
 #ifdef ATT_BWD_PROF
@@ -1926,7 +1936,10 @@ int anemoi_mhsa_backward(int dtype, const void* qkv, int64_t ld, const void* out
     }
 #undef ANEMOI_MHSA_BWD_
 #undef ANEMOI_MHSA_BWD
-    return check_launch("anemoi_mhsa_backward(bf16, MFMA)");
+    {
+      int rc = trail::note(check_launch("anemoi_mhsa_backward(bf16, MFMA)"), "anemoi_mhsa_backward", "dqkv", dtype, dqkv, lddq, (int64_t)B * S, 3 * (int64_t)C, st);
+      return trail::note(rc, "anemoi_mhsa_backward", "delta", ANEMOI_F32, delta, units, 1, units, st);
+    }
   }
   dim3 grid((unsigned)((units + 3) / 4)), block(256);
 #define BWD(T, DM)                                                                                                    \
@@ -1950,7 +1963,10 @@ int anemoi_mhsa_backward(int dtype, const void* qkv, int64_t ld, const void* out
     return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_mhsa_backward: dtype %d", dtype);
   }
 #undef BWD
-  return check_launch("anemoi_mhsa_backward");
+  {
+    int rc = trail::note(check_launch("anemoi_mhsa_backward"), "anemoi_mhsa_backward", "dqkv", dtype, dqkv, lddq, (int64_t)B * S, 3 * (int64_t)C, st);
+    return trail::note(rc, "anemoi_mhsa_backward", "delta", ANEMOI_F32, delta, units, 1, units, st);
+  }
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 //   LayerNorm: dx per row, d gamma / d beta as column sums           anemoi_layer_norm_backward
 // Everything here is bound by HBM bandwidth; no atomics (gradients are bit-reproducible run to run).
 #include "common.hpp"
+#include "trail.hpp"
 
 namespace anemoi {
 
@@ -489,7 +490,8 @@ int anemoi_transpose(int dtype, const void* src, int64_t ld_src, void* dst, int6
                        rows, cols, rows, static_cast<float*>(nullptr), 0);
   else
     return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_transpose: dtype %d", dtype);
-  return check_launch("anemoi_transpose");
+  // (the padding columns rows .. ld_dst-1 are written as zeros: the whole width is the output)
+  return trail::note(check_launch("anemoi_transpose"), "anemoi_transpose", "out", dtype, dst, ld_dst, cols, ld_dst, bw_stream(stream));
 }
 
 int64_t anemoi_transpose_colsum_rows(int64_t rows, int64_t chunk_rows) {
@@ -515,7 +517,12 @@ int anemoi_transpose_chunked(int dtype, const void* src, int64_t ld_src, void* d
                        rows, cols, chunk_rows, colsum_partial, (int)((chunk_rows + 63) / 64));
   else
     return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_transpose_chunked: dtype %d", dtype);
-  return check_launch("anemoi_transpose_chunked");
+  int rc = trail::note(check_launch("anemoi_transpose_chunked"), "anemoi_transpose_chunked", "out", dtype, dst, ld_dst,
+                       chunks * cols, ld_dst, bw_stream(stream));
+  if (colsum_partial != nullptr)
+    rc = trail::note(rc, "anemoi_transpose_chunked", "colsum_partial", ANEMOI_F32, colsum_partial, cols,
+                     anemoi_transpose_colsum_rows(rows, chunk_rows), cols, bw_stream(stream));
+  return rc;
 }
 
 int64_t anemoi_col_sum_workspace_floats(int64_t rows, int cols) {
@@ -528,13 +535,16 @@ int64_t anemoi_col_sum_workspace_floats(int64_t rows, int cols) {
 int anemoi_col_sum(int dtype, const void* x, int64_t ldx, int64_t rows, int cols, float* out, float* workspace,
                    int64_t workspace_floats, anemoi_stream_t stream) {
   ANEMOI_REQUIRE(x && out && rows >= 0 && cols > 0 && ldx >= cols, ANEMOI_ERR_INVALID, "anemoi_col_sum: bad argument");
+  int rc;
   if (dtype == ANEMOI_F32)
-    return col_sum_launch<float>(static_cast<const float*>(x), ldx, rows, cols, out, workspace, workspace_floats,
-                                 bw_stream(stream));
-  if (dtype == ANEMOI_BF16)
-    return col_sum_launch<bf16_t>(static_cast<const bf16_t*>(x), ldx, rows, cols, out, workspace, workspace_floats,
-                                  bw_stream(stream));
-  return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_col_sum: dtype %d", dtype);
+    rc = col_sum_launch<float>(static_cast<const float*>(x), ldx, rows, cols, out, workspace, workspace_floats,
+                               bw_stream(stream));
+  else if (dtype == ANEMOI_BF16)
+    rc = col_sum_launch<bf16_t>(static_cast<const bf16_t*>(x), ldx, rows, cols, out, workspace, workspace_floats,
+                                bw_stream(stream));
+  else
+    return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_col_sum: dtype %d", dtype);
+  return trail::note(rc, "anemoi_col_sum", "out", ANEMOI_F32, out, cols, 1, cols, bw_stream(stream));
 }
 
 int anemoi_act_backward(int dtype, int act, const void* pre, int64_t ldp, const void* dy, int64_t ldd, void* out,
@@ -564,7 +574,7 @@ int anemoi_act_backward(int dtype, int act, const void* pre, int64_t ldp, const 
                        static_cast<bf16_t*>(out), ldo, rows, cols, act);
   else
     return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_act_backward: dtype %d", dtype);
-  return check_launch("anemoi_act_backward");
+  return trail::note(check_launch("anemoi_act_backward"), "anemoi_act_backward", "out", dtype, out, ldo, rows, cols, bw_stream(stream));
 }
 
 int anemoi_act_forward(int dtype, int act, const void* pre, int64_t ldp, const void* residual, int64_t ldr, void* out,
@@ -587,7 +597,7 @@ int anemoi_act_forward(int dtype, int act, const void* pre, int64_t ldp, const v
                        static_cast<bf16_t*>(out), ldo, rows, cols, act);
   else
     return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_act_forward: dtype %d", dtype);
-  return check_launch("anemoi_act_forward");
+  return trail::note(check_launch("anemoi_act_forward"), "anemoi_act_forward", "out", dtype, out, ldo, rows, cols, bw_stream(stream));
 }
 
 int64_t anemoi_layer_norm_backward_workspace_floats(int64_t rows, int C) {
@@ -605,18 +615,23 @@ int anemoi_layer_norm_backward(int dtype, const void* x, int64_t ldx, const floa
                      ldo >= C && (dres == nullptr || ldr >= C),
                  ANEMOI_ERR_INVALID, "anemoi_layer_norm_backward: bad argument");
   ANEMOI_REQUIRE((uintptr_t)stats % 8 == 0, ANEMOI_ERR_INVALID, "anemoi_layer_norm_backward: stats must be 8-byte aligned");
+  int rc;
   if (dtype == ANEMOI_F32)
-    return layer_norm_backward_launch<float>(static_cast<const float*>(x), ldx, reinterpret_cast<const float2*>(stats),
+    rc = layer_norm_backward_launch<float>(static_cast<const float*>(x), ldx, reinterpret_cast<const float2*>(stats),
                                              gamma, static_cast<const float*>(dy), ldd, static_cast<float*>(dx), ldo,
                                              rows, C, dgamma, dbeta, workspace, workspace_floats, bw_stream(stream),
                                              static_cast<const float*>(dres), ldr);
-  if (dtype == ANEMOI_BF16)
-    return layer_norm_backward_launch<bf16_t>(static_cast<const bf16_t*>(x), ldx,
+  else if (dtype == ANEMOI_BF16)
+    rc = layer_norm_backward_launch<bf16_t>(static_cast<const bf16_t*>(x), ldx,
                                               reinterpret_cast<const float2*>(stats), gamma,
                                               static_cast<const bf16_t*>(dy), ldd, static_cast<bf16_t*>(dx), ldo, rows,
                                               C, dgamma, dbeta, workspace, workspace_floats, bw_stream(stream),
                                               static_cast<const bf16_t*>(dres), ldr);
-  return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_layer_norm_backward: dtype %d", dtype);
+  else
+    return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_layer_norm_backward: dtype %d", dtype);
+  rc = trail::note(rc, "anemoi_layer_norm_backward", "dx", dtype, dx, ldo, rows, C, bw_stream(stream));
+  rc = trail::note(rc, "anemoi_layer_norm_backward", "dgamma", ANEMOI_F32, dgamma, C, 1, C, bw_stream(stream));
+  return trail::note(rc, "anemoi_layer_norm_backward", "dbeta", ANEMOI_F32, dbeta, C, 1, C, bw_stream(stream));
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "trail.hpp"
 #include "edge_common.hpp"
 
 namespace anemoi {
@@ -1582,9 +1583,11 @@ extern "C" int anemoi_gt_edge_attention(int dtype, const void* q, int64_t ldq, c
   p.attr = edge_attr; p.w = w_edge; p.b = b_edge; p.rowptr = rowptr; p.col = col;
   p.n_dst = n_dst; p.C = C; p.D = C / H; p.ea_ld = ea_ld; p.edge_dim = edge_dim; p.n_slices = 1;
   p.scale = 1.0f / sqrtf((float)(C / H));
-  if (dtype == ANEMOI_F32) return edge_attention_launch<float>(p, as_stream(stream));
-  if (dtype == ANEMOI_BF16) return edge_attention_launch<bf16_t>(p, as_stream(stream));
-  return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_gt_edge_attention: dtype %d", dtype);
+  int rc;
+  if (dtype == ANEMOI_F32) rc = edge_attention_launch<float>(p, as_stream(stream));
+  else if (dtype == ANEMOI_BF16) rc = edge_attention_launch<bf16_t>(p, as_stream(stream));
+  else return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_gt_edge_attention: dtype %d", dtype);
+  return trail::note(rc, "anemoi_gt_edge_attention", "out", dtype, out, ldo, n_dst, C, as_stream(stream));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1746,7 +1749,9 @@ extern "C" int anemoi_gt_conv(int dtype, const void* q, int64_t ldq, const void*
   ANEMOI_REQUIRE(ok, ANEMOI_ERR_UNSUPPORTED,
                  "anemoi_gt_conv: head size %d is not 1, 2, 4, 8 or 16 lanes of %d channels (the host side zero-pads heads)",
                  C / H, vec);
-  return check_launch("anemoi_gt_conv");
+  int rt = trail::note(check_launch("anemoi_gt_conv"), "anemoi_gt_conv", "out", dtype, out, ldo, n_dst, C, as_stream(stream));
+  if (lse != nullptr) rt = trail::note(rt, "anemoi_gt_conv", "lse", ANEMOI_F32, lse, H, n_dst, H, as_stream(stream));
+  return rt;
 }
 
 extern "C" int anemoi_gt_edge_attention_folded(int dtype, const void* q, int64_t ldq, const void* k, const void* v,
@@ -1788,7 +1793,10 @@ extern "C" int anemoi_gt_edge_attention_folded(int dtype, const void* q, int64_t
   ANEMOI_REQUIRE(ok, ANEMOI_ERR_UNSUPPORTED,
                  "anemoi_gt_edge_attention_folded: unsupported shape (D=%d, UP=%d); use anemoi_gt_edge_attention", C / H,
                  up);
-  return check_launch("anemoi_gt_edge_attention_folded");
+  int rt = trail::note(check_launch("anemoi_gt_edge_attention_folded"), "anemoi_gt_edge_attention_folded", "out", dtype, out, ldo,
+                       n_dst, (int64_t)C + (int64_t)H * up, as_stream(stream));
+  if (lse != nullptr) rt = trail::note(rt, "anemoi_gt_edge_attention_folded", "lse", ANEMOI_F32, lse, H, n_dst, H, as_stream(stream));
+  return rt;
 }
 
 // Launch geometry of anemoi_gt_edge_attention_folded_sched for a destination count / channel width / dtype: wave slots
@@ -1856,7 +1864,9 @@ extern "C" int anemoi_gt_edge_attention_folded_groups(int dtype, const void* q, 
     ANEMOI_GROUPS_UP(4)
   }
 #undef ANEMOI_GROUPS_UP
-  return check_launch(who);
+  int rt = trail::note(check_launch(who), who, "out", dtype, out, ldo, n_dst, (int64_t)C + (int64_t)H * up, st);
+  if (lse != nullptr) rt = trail::note(rt, who, "lse", ANEMOI_F32, lse, H, n_dst, H, st);
+  return rt;
 }
 
 // anemoi_gt_edge_attention_folded with a destination schedule (gt_edge_attention_folded_sched_kernel above): the same
@@ -1916,7 +1926,9 @@ extern "C" int anemoi_gt_edge_attention_folded_sched(int dtype, const void* q, i
     ANEMOI_SCHED_UP(4)
   }
 #undef ANEMOI_SCHED_UP
-  return check_launch(who);
+  int rt = trail::note(check_launch(who), who, "out", dtype, out, ldo, n_dst, (int64_t)C + (int64_t)H * up, st);
+  if (lse != nullptr) rt = trail::note(rt, who, "lse", ANEMOI_F32, lse, H, n_dst, H, st);
+  return rt;
 }
 
 // anemoi_gt_edge_attention_folded on LDS TILES (gt_edge_attention_folded_tiles_kernel above): the same result bit for bit.
@@ -1981,7 +1993,9 @@ extern "C" int anemoi_gt_edge_attention_folded_tiles(int dtype, const void* q, i
   }
 #undef ANEMOI_TILES_UP
   if (rc != ANEMOI_OK) return rc;
-  return check_launch(who);
+  int rt = trail::note(check_launch(who), who, "out", dtype, out, ldo, n_dst, (int64_t)C + (int64_t)H * up, st);
+  if (lse != nullptr) rt = trail::note(rt, who, "lse", ANEMOI_F32, lse, H, n_dst, H, st);
+  return rt;
 }
 
 // The folded edge phase on a uniform-degree-3 graph with its runs of destinations that share their three sources
@@ -2033,5 +2047,7 @@ extern "C" int anemoi_gt_edge_attention_folded_runs(int dtype, const void* q, in
     ANEMOI_RUNS_UP(4)
   }
 #undef ANEMOI_RUNS_UP
-  return check_launch(who);
+  int rt = trail::note(check_launch(who), who, "out", dtype, out, ldo, n_dst, (int64_t)C + (int64_t)H * up, st);
+  if (lse != nullptr) rt = trail::note(rt, who, "lse", ANEMOI_F32, lse, H, n_dst, H, st);
+  return rt;
 }

@@ -26,6 +26,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "trail.hpp"
 
 namespace anemoi {
 
@@ -264,5 +265,7 @@ extern "C" int anemoi_gt_edge_attention_raw(const void* qt, int64_t ldqt, const 
                   : Ks == 128 ? dispatch_raw<128>(p, up, edge_attr, rowptr, col, as_stream(stream))
                               : dispatch_raw<64>(p, up, edge_attr, rowptr, col, as_stream(stream));
   ANEMOI_REQUIRE(ok, ANEMOI_ERR_UNSUPPORTED, "anemoi_gt_edge_attention_raw: up=%d", up);
-  return check_launch("anemoi_gt_edge_attention_raw");
+  int rc = trail::note(check_launch("anemoi_gt_edge_attention_raw"), "anemoi_gt_edge_attention_raw", "out", ANEMOI_BF16, g, ldg,
+                       n_dst, (int64_t)H * Ks, as_stream(stream));
+  return trail::note(rc, "anemoi_gt_edge_attention_raw", "t_out", ANEMOI_BF16, t, ldt, n_dst, (int64_t)H * up, as_stream(stream));
 }

@@ -21,6 +21,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "trail.hpp"
 #include "edge_common.hpp"
 
 namespace anemoi {
@@ -591,7 +592,12 @@ int anemoi_gt_edge_attention_folded_backward_dst(int dtype, const void* q, int64
   else if (dtype == ANEMOI_BF16) ok = dispatch_dst<bf16_t>(p, edge_attr, rowptr, col, C / H, up, st);
   ANEMOI_REQUIRE(ok, ANEMOI_ERR_UNSUPPORTED, "anemoi_gt_edge_attention_folded_backward_dst: unsupported D=%d UP=%d dtype=%d",
                  C / H, up, dtype);
-  return check_launch("anemoi_gt_edge_attention_folded_backward_dst");
+  // (alpha and w [E, H] are per-edge outputs too, but E is not an argument here: they show in the _src pass's dk / dv)
+  const char* who = "anemoi_gt_edge_attention_folded_backward_dst";
+  int rc = trail::note(check_launch(who), who, "dq", dtype, dq, lddq, n_dst, C, st);
+  rc = trail::note(rc, who, "du", dtype, du, lddu, n_dst, (int64_t)H * up, st);
+  if (dxr != nullptr) rc = trail::note(rc, who, "dxr", dtype, dxr, lddxr, n_dst, C, st);
+  return trail::note(rc, who, "dsum", ANEMOI_F32, dsum, H, n_dst, H, st);
 }
 
 int anemoi_gt_edge_attention_folded_backward_src(int dtype, const void* q, int64_t ldq, const void* dout, int64_t ldd,
@@ -619,7 +625,9 @@ int anemoi_gt_edge_attention_folded_backward_src(int dtype, const void* q, int64
   else if (dtype == ANEMOI_BF16) ok = dispatch_src<bf16_t>(p, rowptr_t, eid_t, dst_t, C / H, st);
   ANEMOI_REQUIRE(ok, ANEMOI_ERR_UNSUPPORTED, "anemoi_gt_edge_attention_folded_backward_src: unsupported D=%d dtype=%d", C / H,
                  dtype);
-  return check_launch("anemoi_gt_edge_attention_folded_backward_src");
+  const char* who = "anemoi_gt_edge_attention_folded_backward_src";
+  const int rc = trail::note(check_launch(who), who, "dk", dtype, dk, ldg, n_src, C, st);
+  return trail::note(rc, who, "dv", dtype, dv, ldg, n_src, C, st);
 }
 
 int anemoi_gt_edge_attr_grad(int dtype, const float* alpha, const float* w, const float* dsum, const void* u, int64_t ldu,
@@ -642,7 +650,7 @@ int anemoi_gt_edge_attr_grad(int dtype, const float* alpha, const float* w, cons
                        n_edges, H, up, scale);
   else
     return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_gt_edge_attr_grad: dtype %d", dtype);
-  return check_launch("anemoi_gt_edge_attr_grad");
+  return trail::note(check_launch("anemoi_gt_edge_attr_grad"), "anemoi_gt_edge_attr_grad", "out", ANEMOI_F32, dattr, up, n_edges, up, st);
 }
 
 int anemoi_gt_conv_backward_dst(int dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv,
@@ -685,7 +693,9 @@ int anemoi_gt_conv_backward_dst(int dtype, const void* q, int64_t ldq, const voi
   }
 #undef ANEMOI_CONV_DST
   ANEMOI_REQUIRE(ok, ANEMOI_ERR_UNSUPPORTED, "anemoi_gt_conv_backward_dst: unsupported D=%d dtype=%d", D, dtype);
-  return check_launch("anemoi_gt_conv_backward_dst");
+  // (alpha and w [E, H]: E is not an argument here, see anemoi_gt_edge_attention_folded_backward_dst)
+  const int rc = trail::note(check_launch("anemoi_gt_conv_backward_dst"), "anemoi_gt_conv_backward_dst", "dq", dtype, dq, lddq, n_dst, C, st);
+  return trail::note(rc, "anemoi_gt_conv_backward_dst", "dsum", ANEMOI_F32, dsum, H, n_dst, H, st);
 }
 
 int anemoi_gt_conv_backward_src(int dtype, const void* q, int64_t ldq, const void* dout, int64_t ldd, const float* alpha,
@@ -729,7 +739,9 @@ int anemoi_gt_conv_backward_src(int dtype, const void* q, int64_t ldq, const voi
   }
 #undef ANEMOI_CONV_SRC
   ANEMOI_REQUIRE(ok, ANEMOI_ERR_UNSUPPORTED, "anemoi_gt_conv_backward_src: unsupported D=%d dtype=%d", D, dtype);
-  return check_launch("anemoi_gt_conv_backward_src");
+  // (d edges [E, C] is an output too, but E is not an argument here)
+  const int rc = trail::note(check_launch("anemoi_gt_conv_backward_src"), "anemoi_gt_conv_backward_src", "dk", dtype, dk, ldg, n_src, C, st);
+  return trail::note(rc, "anemoi_gt_conv_backward_src", "dv", dtype, dv, ldg, n_src, C, st);
 }
 
 }  // extern "C"

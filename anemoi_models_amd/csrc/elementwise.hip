@@ -6,6 +6,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "trail.hpp"
 
 namespace anemoi {
 
@@ -602,9 +603,11 @@ int anemoi_layer_norm(int dtype, const void* x, int64_t ldx, const float* gamma,
                  "anemoi_layer_norm: bad shape rows=%lld C=%d ldx=%lld ldy=%lld", (long long)rows, C, (long long)ldx,
                  (long long)ldy);
   if (rows == 0) return ANEMOI_OK;
-  if (dtype == ANEMOI_F32) return layer_norm_launch<float>(x, ldx, gamma, beta, y, ldy, rows, C, eps, as_stream(stream));
-  if (dtype == ANEMOI_BF16) return layer_norm_launch<bf16_t>(x, ldx, gamma, beta, y, ldy, rows, C, eps, as_stream(stream));
-  return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_layer_norm: dtype %d", dtype);
+  int rc;
+  if (dtype == ANEMOI_F32) rc = layer_norm_launch<float>(x, ldx, gamma, beta, y, ldy, rows, C, eps, as_stream(stream));
+  else if (dtype == ANEMOI_BF16) rc = layer_norm_launch<bf16_t>(x, ldx, gamma, beta, y, ldy, rows, C, eps, as_stream(stream));
+  else return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_layer_norm: dtype %d", dtype);
+  return trail::note(rc, "anemoi_layer_norm", "out", dtype, y, ldy, rows, C, as_stream(stream));
 }
 
 int anemoi_layer_norm_residual(int dtype, const void* x, int64_t ldx, const float* gamma, const float* beta,
@@ -615,11 +618,14 @@ int anemoi_layer_norm_residual(int dtype, const void* x, int64_t ldx, const floa
                  "anemoi_layer_norm_residual: bad shape rows=%lld C=%d ldx=%lld ldr=%lld ldy=%lld", (long long)rows, C,
                  (long long)ldx, (long long)ldr, (long long)ldy);
   if (rows == 0) return ANEMOI_OK;
+  int rc;
   if (dtype == ANEMOI_F32)
-    return layer_norm_launch<float>(x, ldx, gamma, beta, y, ldy, rows, C, eps, as_stream(stream), nullptr, residual, ldr);
-  if (dtype == ANEMOI_BF16)
-    return layer_norm_launch<bf16_t>(x, ldx, gamma, beta, y, ldy, rows, C, eps, as_stream(stream), nullptr, residual, ldr);
-  return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_layer_norm_residual: dtype %d", dtype);
+    rc = layer_norm_launch<float>(x, ldx, gamma, beta, y, ldy, rows, C, eps, as_stream(stream), nullptr, residual, ldr);
+  else if (dtype == ANEMOI_BF16)
+    rc = layer_norm_launch<bf16_t>(x, ldx, gamma, beta, y, ldy, rows, C, eps, as_stream(stream), nullptr, residual, ldr);
+  else
+    return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_layer_norm_residual: dtype %d", dtype);
+  return trail::note(rc, "anemoi_layer_norm_residual", "out", dtype, y, ldy, rows, C, as_stream(stream));
 }
 
 int anemoi_layer_norm_stats(int dtype, const void* x, int64_t ldx, const float* gamma, const float* beta, void* y,
@@ -630,11 +636,15 @@ int anemoi_layer_norm_stats(int dtype, const void* x, int64_t ldx, const float* 
                  (long long)rows, C, (long long)ldx, (long long)ldy);
   if (rows == 0) return ANEMOI_OK;
   float2* sp = reinterpret_cast<float2*>(stats);
+  int rc;
   if (dtype == ANEMOI_F32)
-    return layer_norm_launch<float>(x, ldx, gamma, beta, y, ldy, rows, C, eps, as_stream(stream), sp);
-  if (dtype == ANEMOI_BF16)
-    return layer_norm_launch<bf16_t>(x, ldx, gamma, beta, y, ldy, rows, C, eps, as_stream(stream), sp);
-  return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_layer_norm_stats: dtype %d", dtype);
+    rc = layer_norm_launch<float>(x, ldx, gamma, beta, y, ldy, rows, C, eps, as_stream(stream), sp);
+  else if (dtype == ANEMOI_BF16)
+    rc = layer_norm_launch<bf16_t>(x, ldx, gamma, beta, y, ldy, rows, C, eps, as_stream(stream), sp);
+  else
+    return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_layer_norm_stats: dtype %d", dtype);
+  rc = trail::note(rc, "anemoi_layer_norm_stats", "out", dtype, y, ldy, rows, C, as_stream(stream));
+  return trail::note(rc, "anemoi_layer_norm_stats", "stats", ANEMOI_F32, stats, 2, rows, 2, as_stream(stream));
 }
 
 int anemoi_row_stats(int dtype, const void* x, int64_t ldx, float* stats, int64_t rows, int C, float eps,
@@ -644,12 +654,14 @@ int anemoi_row_stats(int dtype, const void* x, int64_t ldx, float* stats, int64_
                  (long long)rows, C, (long long)ldx);
   ANEMOI_REQUIRE((uintptr_t)stats % 8 == 0, ANEMOI_ERR_INVALID, "anemoi_row_stats: stats must be 8-byte aligned");
   if (rows == 0) return ANEMOI_OK;
-  if (dtype == ANEMOI_F32) return row_stats_launch<float>(x, ldx, stats, rows, C, eps, as_stream(stream));
-  if (dtype == ANEMOI_BF16) return row_stats_launch<bf16_t>(x, ldx, stats, rows, C, eps, as_stream(stream));
-  return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_row_stats: dtype %d", dtype);
+  int rc;
+  if (dtype == ANEMOI_F32) rc = row_stats_launch<float>(x, ldx, stats, rows, C, eps, as_stream(stream));
+  else if (dtype == ANEMOI_BF16) rc = row_stats_launch<bf16_t>(x, ldx, stats, rows, C, eps, as_stream(stream));
+  else return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_row_stats: dtype %d", dtype);
+  return trail::note(rc, "anemoi_row_stats", "stats", ANEMOI_F32, stats, 2, rows, 2, as_stream(stream));
 }
 
-static int assemble_nodes_impl(int dtype, const float* x, int B, int T, int Ens, int64_t G, int V, const float* latlons,
+static int assemble_nodes_impl(const char* who, int dtype, const float* x, int B, int T, int Ens, int64_t G, int V, const float* latlons,
                                int n_ll, const float* trainable, int n_tr, void* out, int64_t ldo, const float* in_mul,
                                const float* in_add, const int64_t* rows, int64_t n_rows, anemoi_stream_t stream) {
   ANEMOI_REQUIRE((in_mul == nullptr) == (in_add == nullptr), ANEMOI_ERR_INVALID,
@@ -677,7 +689,7 @@ static int assemble_nodes_impl(int dtype, const float* x, int B, int T, int Ens,
       else ANEMOI_ASM8(bf16_t, false);
     }
 #undef ANEMOI_ASM8
-    return check_launch("anemoi_assemble_nodes");
+    return trail::note(check_launch("anemoi_assemble_nodes"), who, "out", dtype, out, ldo, total / ldo, ldo, st);
   }
   if (dtype == ANEMOI_F32)
     hipLaunchKernelGGL((assemble_nodes_kernel<float>), dim3(flat_grid(total)), dim3(256), 0, st, x, B, T, Ens, G, V,
@@ -687,13 +699,13 @@ static int assemble_nodes_impl(int dtype, const float* x, int B, int T, int Ens,
                        latlons, n_ll, trainable, n_tr, static_cast<bf16_t*>(out), ldo, in_mul, in_add, rows, n_rows);
   else
     return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_assemble_nodes: dtype %d", dtype);
-  return check_launch("anemoi_assemble_nodes");
+  return trail::note(check_launch("anemoi_assemble_nodes"), who, "out", dtype, out, ldo, total / ldo, ldo, st);
 }
 
 int anemoi_assemble_nodes(int dtype, const float* x, int B, int T, int Ens, int64_t G, int V, const float* latlons,
                           int n_ll, const float* trainable, int n_tr, void* out, int64_t ldo, const float* in_mul,
                           const float* in_add, anemoi_stream_t stream) {
-  return assemble_nodes_impl(dtype, x, B, T, Ens, G, V, latlons, n_ll, trainable, n_tr, out, ldo, in_mul, in_add, nullptr, 0,
+  return assemble_nodes_impl("anemoi_assemble_nodes", dtype, x, B, T, Ens, G, V, latlons, n_ll, trainable, n_tr, out, ldo, in_mul, in_add, nullptr, 0,
                              stream);
 }
 
@@ -703,7 +715,7 @@ int anemoi_assemble_node_rows(int dtype, const float* x, int T, int64_t G, int V
   ANEMOI_REQUIRE(n_rows >= 0 && (rows != nullptr || n_rows == 0), ANEMOI_ERR_INVALID,
                  "anemoi_assemble_node_rows: null row list");
   if (n_rows == 0) return ANEMOI_OK;
-  return assemble_nodes_impl(dtype, x, 1, T, 1, G, V, latlons, n_ll, trainable, n_tr, out, ldo, in_mul, in_add, rows, n_rows,
+  return assemble_nodes_impl("anemoi_assemble_node_rows", dtype, x, 1, T, 1, G, V, latlons, n_ll, trainable, n_tr, out, ldo, in_mul, in_add, rows, n_rows,
                              stream);
 }
 
@@ -718,7 +730,8 @@ int anemoi_edge_attr_csr(const float* a0, int d0, const float* a1, int d1, int64
   if (n_edges == 0) return ANEMOI_OK;
   hipLaunchKernelGGL(edge_attr_csr_kernel, dim3(flat_grid(n_edges * ld_out)), dim3(256), 0, as_stream(stream), a0, d0,
                      a1, d1, rows0, perm, out, ld_out, one_col, n_edges);
-  return check_launch("anemoi_edge_attr_csr");
+  return trail::note(check_launch("anemoi_edge_attr_csr"), "anemoi_edge_attr_csr", "out", ANEMOI_F32, out, ld_out, n_edges, ld_out,
+                     as_stream(stream));
 }
 
 int anemoi_convert_pad(int src_dtype, const void* src, int64_t ld_src, int dst_dtype, void* dst, int64_t ld_dst,
@@ -737,7 +750,7 @@ int anemoi_convert_pad(int src_dtype, const void* src, int64_t ld_src, int dst_d
   else if (src_dtype == ANEMOI_BF16 && dst_dtype == ANEMOI_BF16) CP(bf16_t, bf16_t);
   else return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_convert_pad: dtypes %d -> %d", src_dtype, dst_dtype);
 #undef CP
-  return check_launch("anemoi_convert_pad");
+  return trail::note(check_launch("anemoi_convert_pad"), "anemoi_convert_pad", "out", dst_dtype, dst, ld_dst, rows, ld_dst, st);
 }
 
 int anemoi_row_scale(int dtype, const void* x, int64_t ldx, const float* s, float alpha, void* out, int64_t ldo,
@@ -756,7 +769,7 @@ int anemoi_row_scale(int dtype, const void* x, int64_t ldx, const float* s, floa
                        static_cast<bf16_t*>(out), ldo, rows, cols);
   else
     return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_row_scale: dtype %d", dtype);
-  return check_launch("anemoi_row_scale");
+  return trail::note(check_launch("anemoi_row_scale"), "anemoi_row_scale", "out", dtype, out, ldo, rows, cols, st);
 }
 
 int anemoi_row_dot(int dtype, const void* a, int64_t lda, const void* b, int64_t ldb, const float* shift, float* out,
@@ -775,7 +788,7 @@ int anemoi_row_dot(int dtype, const void* a, int64_t lda, const void* b, int64_t
                        static_cast<const bf16_t*>(b), ldb, shift, out, rows, cols);
   else
     return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_row_dot: dtype %d", dtype);
-  return check_launch("anemoi_row_dot");
+  return trail::note(check_launch("anemoi_row_dot"), "anemoi_row_dot", "out", ANEMOI_F32, out, 1, rows, 1, st);
 }
 
 int anemoi_add(int dtype, const void* a, int64_t lda, const void* b, int64_t ldb, void* y, int64_t ldy, int64_t rows,
@@ -792,7 +805,7 @@ int anemoi_add(int dtype, const void* a, int64_t lda, const void* b, int64_t ldb
                        static_cast<const bf16_t*>(b), ldb, static_cast<bf16_t*>(y), ldy, rows, cols);
   else
     return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_add: dtype %d", dtype);
-  return check_launch("anemoi_add");
+  return trail::note(check_launch("anemoi_add"), "anemoi_add", "out", dtype, y, ldy, rows, cols, st);
 }
 
 int anemoi_prognostic_residual(float* y, int V_out, const float* x, int B, int T, int Ens, int64_t G, int V_in,
@@ -804,7 +817,8 @@ int anemoi_prognostic_residual(float* y, int V_out, const float* x, int B, int T
   if (total == 0) return ANEMOI_OK;
   hipLaunchKernelGGL(prognostic_residual_kernel, dim3(flat_grid(total)), dim3(256), 0, as_stream(stream), y, V_out, x,
                      B, T, Ens, G, V_in, out_idx, in_idx, n_prog);
-  return check_launch("anemoi_prognostic_residual");
+  return trail::note(check_launch("anemoi_prognostic_residual"), "anemoi_prognostic_residual", "out", ANEMOI_F32, y, V_out,
+                     (int64_t)B * Ens * G, V_out, as_stream(stream));
 }
 
 int anemoi_advance_input(float* x, int B, int T, int Ens, int64_t G, int V_in, const float* y, int V_out,
@@ -815,10 +829,11 @@ int anemoi_advance_input(float* x, int B, int T, int Ens, int64_t G, int V_in, c
   if (total == 0) return ANEMOI_OK;
   hipLaunchKernelGGL(advance_input_kernel, dim3(flat_grid(total)), dim3(256), 0, as_stream(stream), x, B, T, Ens, G,
                      V_in, y, V_out, forcing, F, colmap);
-  return check_launch("anemoi_advance_input");
+  return trail::note(check_launch("anemoi_advance_input"), "anemoi_advance_input", "out", ANEMOI_F32, x, V_in,
+                     (int64_t)B * T * Ens * G, V_in, as_stream(stream));
 }
 
-static int finalize_output_impl(float* y, int V_out, const float* x, int B, int T, int Ens, int64_t G, int V_in,
+static int finalize_output_impl(const char* who, float* y, int V_out, const float* x, int B, int T, int Ens, int64_t G, int V_in,
                                 const int32_t* src, const float* in_mul, const float* in_add, const float* out_mul,
                                 const float* out_add, const int64_t* rows, int64_t n_rows, anemoi_stream_t stream) {
   ANEMOI_REQUIRE(y && x && src && B > 0 && T > 0 && Ens > 0 && G >= 0 && V_in > 0 && V_out > 0, ANEMOI_ERR_INVALID,
@@ -833,13 +848,14 @@ static int finalize_output_impl(float* y, int V_out, const float* x, int B, int 
   else
     hipLaunchKernelGGL(finalize_output_kernel<false>, dim3(flat_grid(total)), dim3(256), 0, as_stream(stream), y, V_out, x, B,
                        T, Ens, G, V_in, src, in_mul, in_add, out_mul, out_add, rows, n_rows);
-  return check_launch("anemoi_finalize_output");
+  return trail::note(check_launch("anemoi_finalize_output"), who, "out", ANEMOI_F32, y, V_out, total / V_out, V_out,
+                     as_stream(stream));
 }
 
 int anemoi_finalize_output(float* y, int V_out, const float* x, int B, int T, int Ens, int64_t G, int V_in,
                            const int32_t* src, const float* in_mul, const float* in_add, const float* out_mul,
                            const float* out_add, anemoi_stream_t stream) {
-  return finalize_output_impl(y, V_out, x, B, T, Ens, G, V_in, src, in_mul, in_add, out_mul, out_add, nullptr, 0, stream);
+  return finalize_output_impl("anemoi_finalize_output", y, V_out, x, B, T, Ens, G, V_in, src, in_mul, in_add, out_mul, out_add, nullptr, 0, stream);
 }
 
 int anemoi_finalize_output_rows(float* y, int V_out, const float* x, int T, int64_t G, int V_in, const int32_t* src,
@@ -848,7 +864,7 @@ int anemoi_finalize_output_rows(float* y, int V_out, const float* x, int T, int6
   ANEMOI_REQUIRE(n_rows >= 0 && (rows != nullptr || n_rows == 0), ANEMOI_ERR_INVALID,
                  "anemoi_finalize_output_rows: null row list");
   if (n_rows == 0) return ANEMOI_OK;
-  return finalize_output_impl(y, V_out, x, 1, T, 1, G, V_in, src, in_mul, in_add, out_mul, out_add, rows, n_rows, stream);
+  return finalize_output_impl("anemoi_finalize_output_rows", y, V_out, x, 1, T, 1, G, V_in, src, in_mul, in_add, out_mul, out_add, rows, n_rows, stream);
 }
 
 int anemoi_bound_output(float* y, int V_out, int64_t rows, int n_ops, const int32_t* op_col, const float* op_lo,
@@ -863,10 +879,11 @@ int anemoi_bound_output(float* y, int V_out, int64_t rows, int n_ops, const int3
   if (rows == 0 || (n_ops == 0 && n_fin == 0)) return ANEMOI_OK;
   hipLaunchKernelGGL(bound_output_kernel, dim3(flat_grid(rows)), dim3(256), 0, as_stream(stream), y, V_out, rows, n_ops,
                      op_col, op_lo, op_hi, op_mul, n_fin, fin_col, fin_mul, fin_add);
-  return check_launch("anemoi_bound_output");
+  return trail::note(check_launch("anemoi_bound_output"), "anemoi_bound_output", "out", ANEMOI_F32, y, V_out, rows, V_out,
+                     as_stream(stream));
 }
 
-int anemoi_abi_version(void) { return 44; }
+int anemoi_abi_version(void) { return 45; }
 
 #ifndef ANEMOI_HIPCC_VERSION
 #define ANEMOI_HIPCC_VERSION "unknown (built without anemoi_models_amd/_build.py)"

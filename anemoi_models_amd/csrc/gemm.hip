@@ -21,6 +21,7 @@
 #include <utility>
 
 #include "common.hpp"
+#include "trail.hpp"
 
 // Lab switches (tools/micro/ab_gemm.sh): cache-policy bits of the slab DMAs (buffer_load ... lds aux: 1 = sc0, 2 = nt,
 // 16 = sc1).  The product builds with 0 / 0.
@@ -1352,8 +1353,9 @@ static int linear_dispatch(const char* who, int dtype, int out_dtype, const void
 extern "C" int anemoi_linear(int dtype, int out_dtype, const void* x, int64_t ldx, const void* w, const float* bias,
                              const void* residual, int64_t ldr, void* y, int64_t ldy, int64_t M, int N, int K, int act,
                              anemoi_stream_t stream) {
-  return linear_dispatch("anemoi_linear", dtype, out_dtype, x, ldx, w, bias, LnFold{nullptr, nullptr}, residual, ldr, y,
-                         ldy, M, N, K, act, stream);
+  const int rc = linear_dispatch("anemoi_linear", dtype, out_dtype, x, ldx, w, bias, LnFold{nullptr, nullptr}, residual, ldr,
+                                 y, ldy, M, N, K, act, stream);
+  return trail::note(rc, "anemoi_linear", "out", out_dtype, y, ldy, M, N, as_stream(stream));
 }
 
 extern "C" int anemoi_linear_ln(int dtype, int out_dtype, const void* x, int64_t ldx, const void* w, const float* bias,
@@ -1361,9 +1363,10 @@ extern "C" int anemoi_linear_ln(int dtype, int out_dtype, const void* x, int64_t
                                 int64_t ldy, int64_t M, int N, int K, int act, anemoi_stream_t stream) {
   ANEMOI_REQUIRE(colsum && stats, ANEMOI_ERR_INVALID, "anemoi_linear_ln: null colsum / stats");
   ANEMOI_REQUIRE((uintptr_t)stats % 8 == 0, ANEMOI_ERR_INVALID, "anemoi_linear_ln: stats must be 8-byte aligned");
-  return linear_dispatch("anemoi_linear_ln", dtype, out_dtype, x, ldx, w, bias,
-                         LnFold{colsum, reinterpret_cast<const float2*>(stats)}, residual, ldr, y, ldy, M, N, K, act,
-                         stream);
+  const int rc = linear_dispatch("anemoi_linear_ln", dtype, out_dtype, x, ldx, w, bias,
+                                 LnFold{colsum, reinterpret_cast<const float2*>(stats)}, residual, ldr, y, ldy, M, N, K, act,
+                                 stream);
+  return trail::note(rc, "anemoi_linear_ln", "out", out_dtype, y, ldy, M, N, as_stream(stream));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1459,7 +1462,8 @@ extern "C" int anemoi_linear_dual(int dtype, const void* x, int64_t ldx, const v
   if (rc == ANEMOI_OK && M % BIG_M != 0 && !tail_done)
     return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_linear_dual: the ragged rows were not taken by the fast path");
   if (rc == W4_NEEDS_WHOLE_TILES) return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_linear_dual: shape not taken by the fast path");
-  return rc;
+  const int rt = trail::note(rc, "anemoi_linear_dual", "out", dtype, y, ldy, M, N, as_stream(stream));
+  return trail::note(rt, "anemoi_linear_dual", "pre", dtype, pre, ldp, M, N, as_stream(stream));
 }
 
 // y = (x W^T) * act'(pre): the backward's dX GEMM of the Linear behind an activation, delivering the gradient of the
@@ -1485,7 +1489,7 @@ extern "C" int anemoi_linear_actgrad(int dtype, const void* x, int64_t ldx, cons
     return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_linear_actgrad: the ragged rows were not taken by the fast path");
   if (rc == W4_NEEDS_WHOLE_TILES)
     return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_linear_actgrad: shape not taken by the fast path");
-  return rc;
+  return trail::note(rc, "anemoi_linear_actgrad", "out", dtype, y, ldy, M, N, as_stream(stream));
 }
 
 extern "C" int anemoi_linear_stats(int dtype, const void* x, int64_t ldx, const void* w, const float* bias,
@@ -1519,12 +1523,14 @@ extern "C" int anemoi_linear_stats(int dtype, const void* x, int64_t ldx, const 
     if (rl != ANEMOI_OK) return rl;
     rows_done += tail;
   }
+  int rs = ANEMOI_OK;
   if (rows_done < M) {  // rows the fused path did not cover (other kernels): statistics from y itself
     const int esz = dtype == ANEMOI_BF16 ? 2 : 4;
-    return anemoi_row_stats(dtype, static_cast<const char*>(y) + rows_done * ldy * esz, ldy, stats_out + 2 * rows_done,
-                            M - rows_done, N, eps, stream);
+    rs = anemoi_row_stats(dtype, static_cast<const char*>(y) + rows_done * ldy * esz, ldy, stats_out + 2 * rows_done,
+                          M - rows_done, N, eps, stream);
   }
-  return ANEMOI_OK;
+  rs = trail::note(rs, "anemoi_linear_stats", "out", dtype, y, ldy, M, N, as_stream(stream));
+  return trail::note(rs, "anemoi_linear_stats", "stats", ANEMOI_F32, stats_out, 2, M, 2, as_stream(stream));
 }
 
 
@@ -1533,9 +1539,9 @@ extern "C" int anemoi_linear_stats(int dtype, const void* x, int64_t ldx, const 
 // The weight-gradient GEMMs use it as a deterministic split of their long reduction (anemoi_models_amd/autograd.py):
 // dW = sum_b dpre[b]^T X[b] over row chunks b, so that a small [N, K] result still fills the chip.
 // ---------------------------------------------------------------------------------------------
-extern "C" int anemoi_linear_batched(int dtype, int out_dtype, const void* x, int64_t ldx, int64_t stride_x,
-                                     const void* w, int64_t stride_w, void* y, int64_t ldy, int64_t stride_y, int batch,
-                                     int64_t M, int N, int K, anemoi_stream_t stream) {
+static int linear_batched_impl(int dtype, int out_dtype, const void* x, int64_t ldx, int64_t stride_x, const void* w,
+                               int64_t stride_w, void* y, int64_t ldy, int64_t stride_y, int batch, int64_t M, int N, int K,
+                               anemoi_stream_t stream) {
   using namespace anemoi;
   ANEMOI_REQUIRE(x && w && y && batch > 0 && batch < 65536 && M >= 0 && N > 0 && K > 0 && ldx >= K && ldy >= N,
                  ANEMOI_ERR_INVALID, "anemoi_linear_batched: bad argument");
@@ -1569,4 +1575,19 @@ extern "C" int anemoi_linear_batched(int dtype, int out_dtype, const void* x, in
                                          batch, stride_x, stride_w, stride_y);
   }
   return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_linear_batched: dtype %d -> %d", dtype, out_dtype);
+}
+
+extern "C" int anemoi_linear_batched(int dtype, int out_dtype, const void* x, int64_t ldx, int64_t stride_x,
+                                     const void* w, int64_t stride_w, void* y, int64_t ldy, int64_t stride_y, int batch,
+                                     int64_t M, int N, int K, anemoi_stream_t stream) {
+  using namespace anemoi;
+  int rc = linear_batched_impl(dtype, out_dtype, x, ldx, stride_x, w, stride_w, y, ldy, stride_y, batch, M, N, K, stream);
+  if (M == 0 || trail::armed_state() == nullptr) return rc;
+  if (stride_y == M * ldy)  // the problems' outputs are one [batch * M, N] matrix
+    return trail::note(rc, "anemoi_linear_batched", "out", out_dtype, y, ldy, (int64_t)batch * M, N, as_stream(stream));
+  const int esz = out_dtype == ANEMOI_BF16 ? 2 : 4;
+  for (int b = 0; b < batch; ++b)
+    rc = trail::note(rc, "anemoi_linear_batched", "out", out_dtype, static_cast<const char*>(y) + b * stride_y * esz, ldy, M, N,
+                     as_stream(stream));
+  return rc;
 }

@@ -33,6 +33,7 @@
 //
 // MFMAs are the compiler builtins: the compiler owns their wait states (tools/isa_hazard_audit.py checks the listing).
 #include "common.hpp"
+#include "trail.hpp"
 
 namespace anemoi {
 namespace split {
@@ -245,7 +246,8 @@ extern "C" int anemoi_split_weight(const float* w, int64_t ldw, void* w_hi, void
   ANEMOI_REQUIRE(blocks < (int64_t)1 << 31, ANEMOI_ERR_UNSUPPORTED, "anemoi_split_weight: grid too large");
   hipLaunchKernelGGL(split::split_weight_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), w, ldw,
                      static_cast<bf16_t*>(w_hi), static_cast<bf16_t*>(w_lo), N, K);
-  return check_launch("anemoi_split_weight");
+  int rc = trail::note(check_launch("anemoi_split_weight"), "anemoi_split_weight", "w_hi", ANEMOI_BF16, w_hi, K, N, K, as_stream(stream));
+  return trail::note(rc, "anemoi_split_weight", "w_lo", ANEMOI_BF16, w_lo, K, N, K, as_stream(stream));
 }
 
 extern "C" int anemoi_linear_split(const float* x, int64_t ldx, const void* w_hi, const void* w_lo, const float* bias,
@@ -272,5 +274,5 @@ extern "C" int anemoi_linear_split(const float* x, int64_t ldx, const void* w_hi
   hipLaunchKernelGGL(split::linear_split_kernel, dim3((unsigned)(mt * nt)), dim3(256), 0, as_stream(stream), x, ldx,
                      static_cast<const bf16_t*>(w_hi), static_cast<const bf16_t*>(w_lo), bias, residual, ldr, y, ldy, M, N,
                      K, act, vec_ok ? 1 : 0);
-  return check_launch("anemoi_linear_split");
+  return trail::note(check_launch("anemoi_linear_split"), "anemoi_linear_split", "out", ANEMOI_F32, y, ldy, M, N, as_stream(stream));
 }

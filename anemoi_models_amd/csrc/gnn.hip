@@ -10,6 +10,7 @@
 //                           edges are in destination-sorted order, so a row is a contiguous range: no atomics,
 //                           f32 accumulation in CSR order = the reference's scatter_add_ order)
 #include "common.hpp"
+#include "trail.hpp"
 
 namespace anemoi {
 
@@ -120,7 +121,7 @@ int anemoi_gather_add_act(int dtype, const void* t, int64_t ldt, const void* p_d
     return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_gather_add_act: dtype %d", dtype);
   }
 #undef GAA
-  return check_launch("anemoi_gather_add_act");
+  return trail::note(check_launch("anemoi_gather_add_act"), "anemoi_gather_add_act", "out", dtype, out, ldo, n_edges, C, st);
 }
 
 static int segment_sum_impl(const char* who, int dtype, const void* v, int64_t ldv, const int32_t* rowptr, const void* x,
@@ -145,7 +146,7 @@ static int segment_sum_impl(const char* who, int dtype, const void* v, int64_t l
     return fail(ANEMOI_ERR_UNSUPPORTED, "%s: dtype %d", who, dtype);
   }
 #undef SEG
-  return check_launch(who);
+  return trail::note(check_launch(who), who, "out", dtype, out, ldo, n_dst, (x != nullptr ? 2 : 1) * (int64_t)C, st);
 }
 
 int anemoi_segment_sum(int dtype, const void* v, int64_t ldv, const int32_t* rowptr, void* out, int64_t ldo,

@@ -1,6 +1,7 @@
 // MXFP8 inference route: the quantiser (optionally behind a LayerNorm) and the Linear on the
 // block-scaled MFMA v_mfma_scale_f32_16x16x128_f8f6f4.  Number format and layout: include/anemoi_amd.h ("MXFP8").
 #include "common.hpp"
+#include "trail.hpp"
 
 namespace anemoi {
 namespace {
@@ -345,7 +346,8 @@ int anemoi_mx_quantize(int dtype, const void* x, int64_t ldx, const float* gamma
   }
 #undef MXQ_DISPATCH
 #undef MXQ_LAUNCH
-  return check_launch("anemoi_mx_quantize");
+  int rc = trail::note(check_launch("anemoi_mx_quantize"), "anemoi_mx_quantize", "q", ANEMOI_U8, q, ldq, rows, Kp, st);
+  return trail::note(rc, "anemoi_mx_quantize", "scales", ANEMOI_U8, s, lds, rows, Kp / 32, st);
 }
 
 int anemoi_linear_mx(const uint8_t* xq, int64_t ldxq, const uint8_t* xs, int64_t ldxs, const uint8_t* wq,
@@ -378,8 +380,11 @@ int anemoi_linear_mx(const uint8_t* xq, int64_t ldxq, const uint8_t* xs, int64_t
   if (M == 0) return ANEMOI_OK;
   ANEMOI_REQUIRE((M + 127) / 128 < ((int64_t)1 << 31), ANEMOI_ERR_UNSUPPORTED, "anemoi_linear_mx: M too large");
   // 128 x 128 block tiles (four waves of 64 x 64); the larger wave tiles measured slower (profiles/r07_mxfp8.md)
-  return launch_linear_mx<4, 4>(xq, ldxq, xs, ldxs, wq, ws, bias, residual, ldr, out_mx, y, ldy, ys, ldys, M, N, K, act,
-                                as_stream(stream));
+  int rc = launch_linear_mx<4, 4>(xq, ldxq, xs, ldxs, wq, ws, bias, residual, ldr, out_mx, y, ldy, ys, ldys, M, N, K, act,
+                                  as_stream(stream));
+  if (!out_mx) return trail::note(rc, "anemoi_linear_mx", "out", ANEMOI_BF16, y, ldy, M, N, as_stream(stream));
+  rc = trail::note(rc, "anemoi_linear_mx", "out", ANEMOI_U8, y, ldy, M, Np, as_stream(stream));
+  return trail::note(rc, "anemoi_linear_mx", "scales", ANEMOI_U8, ys, ldys, M, Np / 32, as_stream(stream));
 }
 
 }  // extern "C"

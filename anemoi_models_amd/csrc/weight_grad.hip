@@ -26,6 +26,7 @@
 #include <utility>
 
 #include "common.hpp"
+#include "trail.hpp"
 
 namespace anemoi {
 namespace {
@@ -422,5 +423,10 @@ extern "C" int anemoi_weight_grad_tn(const void* dy, int64_t ldy, const void* x,
     default: ANEMOI_TN_LAUNCH(4); break;
   }
 #undef ANEMOI_TN_LAUNCH
-  return check_launch("anemoi_weight_grad_tn");
+  int rc = trail::note(check_launch("anemoi_weight_grad_tn"), "anemoi_weight_grad_tn", "partial", ANEMOI_F32, partial,
+                       partial_stride, chunks, (int64_t)N * K, as_stream(stream));
+  if (bias_partial != nullptr)
+    rc = trail::note(rc, "anemoi_weight_grad_tn", "bias_partial", ANEMOI_F32, bias_partial, bias_stride, chunks, N,
+                     as_stream(stream));
+  return rc;
 }

@@ -37,6 +37,8 @@ extern "C" {
 
 #define ANEMOI_F32 0
 #define ANEMOI_BF16 1
+#define ANEMOI_I32 2 /* launch-trail records only (anemoi_trail_note): no kernel computes in these */
+#define ANEMOI_U8 3
 
 #define ANEMOI_ACT_NONE 0
 #define ANEMOI_ACT_GELU 1 /* exact erf form, nn.GELU() default */
@@ -730,6 +732,41 @@ int anemoi_split_weight(const float* w, int64_t ldw, void* w_hi, void* w_lo, int
 int anemoi_linear_split(const float* x, int64_t ldx, const void* w_hi, const void* w_lo, const float* bias,
                         const float* residual, int64_t ldr, float* y, int64_t ldy, int64_t M, int N, int K, int act,
                         anemoi_stream_t stream);
+
+/*
+ * Launch trail -- opt-in per-launch output digests (csrc/trail.hip).
+ *
+ * While a trail is armed on the calling thread, every entry point of this header that writes device memory appends one
+ * 32-byte record per OUTPUT buffer it wrote (workspaces are not recorded), computed on the device by a read-only kernel on
+ * the entry point's own stream, in call order; the block-level entry points record through the entry points they call.
+ * Record i of the buffer given to anemoi_trail_begin, for a [rows, cols] matrix with bit patterns b (zero-extended):
+ *   bytes  0.. 7  digest    u64  sum over i = r * cols + c of (b_i + 1) * m(i) mod 2^64,
+ *                                m(i) = ((i + 1) * 0x9E3779B97F4A7C15 mod 2^64) | 1   (padding beyond cols is never read)
+ *   bytes  8..15  nonfinite u64  number of NaN / +-Inf elements (0 for the integer dtypes)
+ *   bytes 16..19  absmax    u32  f32 bits of the largest |x| over the finite elements (bf16 widened), 0 if there is none
+ *   bytes 20..31  reserved, zero
+ * Integer arithmetic only: a record is the same on every run and can be recomputed on the host.  The records are complete
+ * once the streams the entry points ran on have been synchronised.  Unarmed, an entry point pays one thread-local load.
+ * Limits: the state is per host thread; launches captured into a HIP graph cannot be recorded (ANEMOI_ERR_UNSUPPORTED).
+ */
+
+/* Arm the trail of the calling thread: `records` is a device buffer of capacity * 32 bytes on the device the entry points
+ * will run on.  A null buffer, capacity <= 0 or a trail already armed: ANEMOI_ERR_INVALID (checked before any device call). */
+int anemoi_trail_begin(void* records, int64_t capacity);
+
+/* Disarm it.  n_written records were written (at most `capacity`); n_dropped further ones were counted and never written.
+ * Either pointer may be NULL.  ANEMOI_ERR_INVALID when no trail is armed. */
+int anemoi_trail_end(int64_t* n_written, int64_t* n_dropped);
+
+/* Host-side description of record i of this thread's last trail (valid until the next anemoi_trail_begin on the thread):
+ * name "<entry point>:<output>", e.g. "anemoi_mhsa:out" and "anemoi_mhsa:lse"; dtype an ANEMOI_F32 / BF16 / I32 / U8 code. */
+int anemoi_trail_entry(int64_t i, const char** name, int* dtype, int64_t* rows, int64_t* cols);
+
+/* The hook the entry points use, for callers that want their own buffers on the trail: one record of the [rows, cols]
+ * matrix at `ptr` (leading dimension ld elements, aligned to its element size) under `name`.  No trail armed: ANEMOI_OK,
+ * nothing is done.  Armed while `stream` is being captured: ANEMOI_ERR_UNSUPPORTED. */
+int anemoi_trail_note(const char* name, int dtype, const void* ptr, int64_t ld, int64_t rows, int64_t cols,
+                      anemoi_stream_t stream);
 
 #ifdef __cplusplus
 }
