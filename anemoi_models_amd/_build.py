@@ -21,7 +21,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-
 # Sources with inline-asm MFMAs or hand-padded wide stores: their device listing is kept next to the object (lib/obj/<name>-hip-amdgcn-amd-amdhsa-gfx950.s,
 # not shipped, not committed) so that tools/isa_hazard_audit.py -- and tests/test_host_logic.py -- can check that nothing
 # touches an MFMA result before its wait states have passed (hipcc pads nothing around such a statement).
-ASM_SOURCES = ("attention", "gemm", "gemm_split", "weight_grad", "edge_attention")
+ASM_SOURCES = ("attention", "gemm", "gemm_split", "weight_grad", "weight_grad_split", "edge_attention")
 
 
 def device_listing(name: str):

@@ -34,7 +34,7 @@ U8 = 3
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_RELU = 0, 1, 2, 3
 ACT_CODES = {"Identity": ACT_NONE, "GELU": ACT_GELU, "SiLU": ACT_SILU, "ReLU": ACT_RELU}
 
-ABI_VERSION = 45
+ABI_VERSION = 46
 
 
 class GtBlockArgs(ctypes.Structure):
@@ -214,6 +214,8 @@ SIGNATURES = {
     "anemoi_split_weight": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "anemoi_linear_split": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
                                     c_int64, c_int, c_int, c_int, c_void_p]),
+    "anemoi_weight_grad_split": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,
+                                         c_int, c_void_p]),
     "anemoi_trail_begin": (c_int, [c_void_p, c_int64]),
     "anemoi_trail_end": (c_int, [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
     "anemoi_trail_entry": (c_int, [c_int64, ctypes.POINTER(c_char_p), ctypes.POINTER(c_int), ctypes.POINTER(c_int64),

@@ -29,6 +29,7 @@ import torch
 from torch import Tensor
 
 from . import ops
+from . import runtime
 
 
 def _pack(w: Tensor, dtype: torch.dtype, k_pad: Optional[int] = None) -> Tensor:
@@ -40,6 +41,50 @@ def _pack(w: Tensor, dtype: torch.dtype, k_pad: Optional[int] = None) -> Tensor:
     out = torch.zeros((n, kp), dtype=dtype, device=w.device)
     out[:, :k] = w.detach().to(dtype)
     return out
+
+
+# ------------------------------------------------------------------------------------------ split-bf16 route (f32 training)
+# ``ANEMOI_AMD_F32_TRAIN_LINEAR=bf16x3`` (runtime.f32_train_linear_split): every Linear-type product
+# of dtype f32 below goes through these three helpers -- forward and dX on ``ops.linear_split`` (``runtime.train_split_route``),
+# dW on ``ops.weight_grad_split`` (``runtime.split_grad_route``); anything they do not admit, every bf16 product and every
+# call with the switch off takes the route it always took.
+def _split_linear(dtype: torch.dtype, m: int, n: int, k: int) -> bool:
+    return runtime.f32_train_linear_split(dtype) and runtime.train_split_route(m, n, k)
+
+
+def _weight_planes(weight: Tensor, kp: int, prep: Optional["WeightPrep"]):
+    """Planes of the packed weight ``[N, kp]`` (of ``prep.w`` when the processor prepared it)."""
+    if prep is not None:
+        return runtime.train_split_planes(prep.w, ("w", kp), lambda: prep.w)
+    return runtime.train_split_planes(weight, ("w", kp), lambda: _pack(weight, torch.float32, kp))
+
+
+def _transposed_planes(weight: Tensor, np_: int, prep: Optional["WeightPrep"]):
+    """Planes of ``W^T [K, np_]`` (N zero-padded to the K-slab multiple: the dX product reduces over it)."""
+    if prep is not None and prep.wt is not None and prep.wt.shape[1] == np_:
+        return runtime.train_split_planes(prep.wt, ("wt", np_), lambda: prep.wt)
+    return runtime.train_split_planes(
+        weight, ("wt", np_), lambda: ops.transpose(weight.detach().to(torch.float32).contiguous(), ld_out=np_))
+
+
+def _aligned16(t: Tensor) -> Tensor:
+    """``t`` if the split weight-gradient kernel can read it as it lies (16-byte rows), else a contiguous copy."""
+    return t if t.data_ptr() % 16 == 0 and ops._ld(t) % 4 == 0 else t.contiguous()
+
+
+def _weight_grad(dpre: Tensor, x: Tensor, k: int, want_bias: bool = False, out: Optional[Tensor] = None):
+    """``ops.weight_grad`` -- or, for f32 operands with the training switch on and a shape ``runtime.split_grad_route``
+    admits, ``ops.weight_grad_split``.  A ``k`` off the multiple of 4 is computed on the next multiple when ``x`` has the
+    (padding) columns for it, and cut."""
+    m, n = dpre.shape
+    if dpre.dtype == torch.float32 and x.dtype == torch.float32 and runtime.f32_train_linear_split(dpre.dtype):
+        k4 = ops.round_up(k, 4)
+        if k4 <= x.shape[1] and runtime.split_grad_route(m, n, k4) and (k4 == k or out is None):
+            got = ops.weight_grad_split(_aligned16(dpre), _aligned16(x), k4, want_bias=want_bias, out=out)
+            if k4 == k:
+                return got
+            return (got[0][:, :k].contiguous(), got[1]) if want_bias else got[:, :k].contiguous()
+    return ops.weight_grad(dpre, x, k, want_bias=want_bias, out=out)
 
 
 class GradSink:
@@ -142,9 +187,25 @@ class _Linear(torch.autograd.Function):
         if x.shape[1] not in (k, kp):
             raise ValueError(f"linear: x has {x.shape[1]} columns, weight expects {k}")
         xk = x if x.shape[1] == kp else ops.convert_pad(x, dtype, kp)
-        w = _pack(weight, dtype, kp) if prep is None else prep.w
         ctx.prep = prep
         b = None if bias is None else bias.detach().float().contiguous()
+        if _split_linear(dtype, xk.shape[0], weight.shape[0], kp) and (residual is None or residual.dtype == dtype):
+            planes = _weight_planes(weight, kp, prep)
+            if act == "Identity":
+                pre = None
+                y = ops.linear_split(xk, planes, b, residual=residual)
+            else:  # the pre-activation from the split kernel, the activation on the stored value (as the exact route below)
+                pre = ops.linear_split(xk, planes, b)
+                if pre.shape[1] % 4 == 0:
+                    y = ops.act_forward(pre, act, residual)
+                else:
+                    y = _TORCH_ACT[act](pre)
+                    if residual is not None:
+                        y = ops.add(y, residual)
+            ctx.save_for_backward(xk, weight, pre)
+            ctx.act, ctx.has_bias, ctx.has_res, ctx.k, ctx.x_cols = act, bias is not None, residual is not None, k, x.shape[1]
+            return y
+        w = _pack(weight, dtype, kp) if prep is None else prep.w
         if act == "Identity":
             pre = None
             y = ops.linear(xk, w, b, residual=residual)
@@ -180,21 +241,11 @@ class _Linear(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             # dX [M, K] = dpre [M, N] @ W [N, K]: a Linear whose weight is W^T [K, N] (N is the reduction dimension)
             np_ = ops.round_up(n, kmul)
-            if prep is not None and prep.wt is not None:
-                wt = prep.wt
-            else:
-                wt = ops.transpose(weight.detach().to(dtype).contiguous(), ld_out=np_)
             dp = dpre if n == np_ else ops.convert_pad(dpre, dtype, np_)
-            if (dtype == torch.bfloat16 and wt.shape[0] < 256 and dp.shape[0] >= 65536 and np_ >= 128
-                    and os.environ.get("ANEMOI_AMD_TRAIN_WIDE_DX", "1") != "0"):
-                # few input features on very many rows (the mappers' embeddings of the grid nodes: 542 080 x 1024 -> 192 at
-                # config 3): fewer than 256 output columns would take the 128 x 128 kernel (0.49 ms, 2.3 TB/s of the dpre
-                # it reads); with the transposed weight padded to 256 zero rows the persistent kernel runs it
-                wide = torch.zeros((256, np_), dtype=dtype, device=wt.device)
-                wide[: wt.shape[0]] = wt
-                dx = ops.linear(dp, wide)[:, : wt.shape[0]]
+            if _split_linear(dtype, dp.shape[0], k, np_):
+                dx = ops.linear_split(dp, _transposed_planes(weight, np_, prep))
             else:
-                dx = ops.linear(dp, wt)
+                dx = _Linear._exact_dx(dp, weight, prep, dtype, np_)
             if ctx.x_cols != k:
                 dx = ops.convert_pad(dx, dtype, ctx.x_cols)
         if ctx.needs_input_grad[1]:
@@ -202,17 +253,37 @@ class _Linear(torch.autograd.Function):
             want_b = ctx.has_bias and ctx.needs_input_grad[2]
             out = None if prep is None or weight.dtype != torch.float32 else prep.grad_out(ctx.has_bias, True, want_b)
             if want_b:
-                dw, db = ops.weight_grad(dpre, xk, k, want_bias=True, out=out)  # the bias gradient rides on dpre's transpose
+                # the bias gradient rides on dpre's transpose (split route: ops.col_sum over dpre, behind dW in ``out``)
+                dw, db = _weight_grad(dpre, xk, k, want_bias=True, out=out)
                 dw = dw.to(weight.dtype)
                 if out is not None and prep.sink.copy_bias:
                     db = db.clone()  # N floats; see GradSink.copy_bias
             else:
-                dw = ops.weight_grad(dpre, xk, k, out=out).to(weight.dtype)
+                dw = _weight_grad(dpre, xk, k, out=out).to(weight.dtype)
         if db is None and ctx.has_bias and ctx.needs_input_grad[2]:
             db = ops.col_sum(dpre)
         if ctx.has_res and ctx.needs_input_grad[4]:
             dres = dy
         return dx, dw, db, None, dres, None, None
+
+    @staticmethod
+    def _exact_dx(dp: Tensor, weight: Tensor, prep: Optional[WeightPrep], dtype: torch.dtype, np_: int) -> Tensor:
+        """``dp @ W`` on the exact kernels (``W^T`` from the processor's preparation, or transposed here)."""
+        if prep is not None and prep.wt is not None:
+            wt = prep.wt
+        else:
+            wt = ops.transpose(weight.detach().to(dtype).contiguous(), ld_out=np_)
+        if (dtype == torch.bfloat16 and wt.shape[0] < 256 and dp.shape[0] >= 65536 and np_ >= 128
+                and os.environ.get("ANEMOI_AMD_TRAIN_WIDE_DX", "1") != "0"):
+            # few input features on very many rows (the mappers' embeddings of the grid nodes: 542 080 x 1024 -> 192 at
+            # config 3): fewer than 256 output columns would take the 128 x 128 kernel (0.49 ms, 2.3 TB/s of the dpre
+            # it reads); with the transposed weight padded to 256 zero rows the persistent kernel runs it
+            wide = torch.zeros((256, np_), dtype=dtype, device=wt.device)
+            wide[: wt.shape[0]] = wt
+            dx = ops.linear(dp, wide)[:, : wt.shape[0]]
+        else:
+            dx = ops.linear(dp, wt)
+        return dx
 
 
 class _MLP2(torch.autograd.Function):
@@ -367,11 +438,16 @@ class _ScaledLinear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: Tensor, f: Tensor, s: Tensor, b: Tensor):
         dtype = x.dtype
-        fp = f.detach().to(dtype).contiguous()
         sd = s.detach().float()
-        stats = torch.stack([sd, torch.zeros_like(sd)], dim=1).contiguous()
-        zeros = torch.zeros(f.shape[0], dtype=torch.float32, device=x.device)
-        y = ops.linear(x, fp, b.detach().float().contiguous(), ln=(stats, zeros))
+        if _split_linear(dtype, x.shape[0], f.shape[0], f.shape[1]):
+            # s (x f^T) = (s x) f^T: the rows are scaled first (the K-narrow side, as the backward does for df)
+            y = ops.linear_split(ops.row_scale(x, sd.contiguous()), _weight_planes(f, f.shape[1], None),
+                                 b.detach().float().contiguous())
+        else:
+            fp = f.detach().to(dtype).contiguous()
+            stats = torch.stack([sd, torch.zeros_like(sd)], dim=1).contiguous()
+            zeros = torch.zeros(f.shape[0], dtype=torch.float32, device=x.device)
+            y = ops.linear(x, fp, b.detach().float().contiguous(), ln=(stats, zeros))
         ctx.save_for_backward(x, f, s, b)
         return y
 
@@ -386,9 +462,11 @@ class _ScaledLinear(torch.autograd.Function):
         dx = df = ds = db = None
         if need[0] or need[2]:
             np_ = ops.round_up(n, ops.k_multiple(dtype))
-            ft = ops.transpose(f.detach().to(dtype).contiguous(), ld_out=np_)
             dp = dy if n == np_ else ops.convert_pad(dy, dtype, np_)
-            g = ops.linear(dp, ft)
+            if _split_linear(dtype, dp.shape[0], kp, np_):
+                g = ops.linear_split(dp, _transposed_planes(f, np_, None))
+            else:
+                g = ops.linear(dp, ops.transpose(f.detach().to(dtype).contiguous(), ld_out=np_))
             if need[2]:
                 ds = ops.row_dot(g, x)
             if need[0]:
@@ -396,9 +474,9 @@ class _ScaledLinear(torch.autograd.Function):
         if need[1]:
             xs = ops.row_scale(x, sd)
             if need[3]:
-                df, db = ops.weight_grad(dy, xs, kp, want_bias=True)
+                df, db = _weight_grad(dy, xs, kp, want_bias=True)
             else:
-                df = ops.weight_grad(dy, xs, kp)
+                df = _weight_grad(dy, xs, kp)
             df = df.to(f.dtype)
         if db is None and need[3]:
             db = ops.col_sum(dy)
@@ -412,7 +490,10 @@ class _QuadForm(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x: Tensor, m: Tensor):
-        z = ops.linear(x, m.detach().to(x.dtype).contiguous())
+        if _split_linear(x.dtype, x.shape[0], m.shape[0], m.shape[1]):
+            z = ops.linear_split(x, _weight_planes(m, m.shape[1], None))
+        else:
+            z = ops.linear(x, m.detach().to(x.dtype).contiguous())
         ctx.save_for_backward(x, z)
         return ops.row_dot(z, x)
 
@@ -421,7 +502,7 @@ class _QuadForm(torch.autograd.Function):
         x, z = ctx.saved_tensors
         g = g.detach().float().contiguous()
         dx = ops.row_scale(z, g, 2.0) if ctx.needs_input_grad[0] else None
-        dm = ops.weight_grad(ops.row_scale(x, g), x, x.shape[1]) if ctx.needs_input_grad[1] else None
+        dm = _weight_grad(ops.row_scale(x, g), x, x.shape[1]) if ctx.needs_input_grad[1] else None
         return dx, dm
 
 

@@ -1148,3 +1148,59 @@ def weight_grad(dpre: Tensor, x: Tensor, k: int, want_bias: bool = False, transp
     if not want_bias:
         return dw
     return dw, (col_sum(partial) if partial is not None else col_sum(dpre))
+
+
+SPLIT_GRAD_WORKGROUPS = 512  # two 64 KiB-LDS workgroups per CU x 256 CUs: the chunk count fills them once
+
+
+def weight_grad_split_chunks(m: int, n: int, k: int):
+    """``(chunks, chunk_rows)`` of :func:`weight_grad_split`: the M reduction is cut so that chunks x 128 x 128 tiles fill the
+    chip, in chunks of at least 1024 rows (a multiple of the kernel's 32-row slab)."""
+    tiles = ((n + 127) // 128) * ((k + 127) // 128)
+    chunks = max(1, min(SPLIT_GRAD_WORKGROUPS // tiles if tiles <= SPLIT_GRAD_WORKGROUPS else 1, m // 1024))
+    chunk_rows = max(32, round_up((m + chunks - 1) // chunks, 32))
+    return max(1, (m + chunk_rows - 1) // chunk_rows), chunk_rows
+
+
+def weight_grad_split(dpre: Tensor, x: Tensor, k: int, want_bias: bool = False, out: Optional[Tensor] = None):
+    """``dW [N, k] = dpre^T @ x[:, :k]`` for f32 ``dpre [M, N]`` / ``x [M, >= k]`` with the split-bf16 product
+    ``dpre_hi^T x_hi + (dpre_hi^T x_lo + dpre_lo^T x_hi)`` on the bf16 MFMA (``anemoi_weight_grad_split``; both operands are
+    split inside the kernel and read as they lie).  Returns and ``out`` as the TN route of :func:`weight_grad`:
+    ``want_bias`` gives ``(dW, db)`` with ``db = dpre.sum(0)`` in exact f32 (``col_sum``); ``out`` (optional, f32
+    ``[N * k (+ N)]`` contiguous) receives ``dW`` and ``db`` behind it, the results are then views of it
+    (``autograd.GradSink``).  N and k multiples of 4, 16-byte aligned operands with row pitches that are multiples of 4,
+    else ``ValueError``.  ``M = 0`` gives zeros without a launch."""
+    _dev(dpre, x, out)
+    m, n = _rows(dpre).shape
+    xr = _rows(x)
+    if dpre.dtype != torch.float32 or xr.dtype != torch.float32:
+        raise ValueError("weight_grad_split: both operands must be f32")
+    if xr.shape[0] != m or xr.shape[1] < k or k <= 0 or n <= 0:
+        raise ValueError(f"weight_grad_split: dpre {tuple(dpre.shape)} and x {tuple(x.shape)} do not give a [{n}, {k}] gradient")
+    if n % 4 != 0 or k % 4 != 0:
+        raise ValueError(f"weight_grad_split: N={n} and K={k} must be multiples of 4")
+    width = n * k + (n if want_bias else 0)
+    if out is not None and (out.dtype != torch.float32 or out.numel() != width or not out.is_contiguous()):
+        raise ValueError(f"weight_grad_split: out must be a contiguous f32 vector of {width} elements")
+    total = torch.empty(width, dtype=torch.float32, device=dpre.device) if out is None else out.view(width)
+    lib = _lib.load()
+    if m == 0:
+        st = lib.anemoi_weight_grad_split(None, max(_ld(dpre), n), None, max(_ld(xr), k), total.data_ptr(), n * k, 0, n, k, 32,
+                                          _stream())
+        _lib.check(st, "anemoi_weight_grad_split")
+        if want_bias:
+            total[n * k:].zero_()
+    else:
+        chunks, chunk_rows = weight_grad_split_chunks(m, n, k)
+        part = total[: n * k].view(1, n * k) if chunks == 1 else torch.empty((chunks, n * k), dtype=torch.float32,
+                                                                             device=dpre.device)
+        with _Timed("weight_grad_split", flops=2 * m * n * k, bytes=(m * (n + k) + chunks * n * k) * 4, m=m, n=n, k=k):
+            st = lib.anemoi_weight_grad_split(dpre.data_ptr(), _ld(dpre), xr.data_ptr(), _ld(xr), part.data_ptr(), n * k, m, n,
+                                              k, chunk_rows, _stream())
+        _lib.check(st, "anemoi_weight_grad_split")
+        if chunks > 1:
+            col_sum(part, out=total[: n * k])
+        if want_bias:
+            col_sum(dpre, out=total[n * k:])
+    dw = total[: n * k].view(n, k)
+    return (dw, total[n * k:]) if want_bias else dw

@@ -682,6 +682,56 @@ def split_planes(w: Tensor) -> "ops.SplitWeight":
     return planes
 
 
+def f32_train_linear_split(dtype: torch.dtype) -> bool:
+    """``ANEMOI_AMD_F32_TRAIN_LINEAR=bf16x3``: the Linear-type products of an f32 TRAINING step (``autograd.py``: forward, dX
+    and dW) run on the split-bf16 kernels.  Unset / ``exact``: the exact f32 MFMA.  Read per call,
+    independent of ``ANEMOI_AMD_F32_LINEAR`` (which stays an inference switch); bf16 compute ignores it."""
+    mode = os.environ.get("ANEMOI_AMD_F32_TRAIN_LINEAR", "exact")
+    if mode not in ("exact", "bf16x3"):
+        raise ValueError(f"ANEMOI_AMD_F32_TRAIN_LINEAR={mode!r}: expected 'exact' or 'bf16x3'")
+    return mode == "bf16x3" and dtype == torch.float32
+
+
+def train_split_route(m: int, n: int, k: int) -> bool:
+    """Which f32 products ``[m, k] x [n, k]`` of a training step (forward and dX) take ``ops.linear_split`` when
+    ``ANEMOI_AMD_F32_TRAIN_LINEAR=bf16x3``: the inference rule plus the kernel's own K-slab multiple."""
+    return split_route(m, n, k) and k % ops.k_multiple(torch.float32) == 0
+
+
+def split_grad_route(m: int, n: int, k: int) -> bool:
+    """The ONE shape rule of the split-bf16 weight gradient ``dW [n, k] = dpre[m, n]^T x[m, k]``
+    (``ops.weight_grad_split``): the 16-byte column groups the kernel reads and writes.  No shape is excluded for speed
+    (profiles/r10_bf16x3_train.md); DESIGN.md section 4.7.1 lists what stays on the exact route."""
+    return n % 4 == 0 and k % 4 == 0
+
+
+def train_split_planes(owner: Tensor, key, build: Callable[[], Tensor]) -> "ops.SplitWeight":
+    """``ops.split_weight(build())`` -- the planes of a packed f32 weight ``[N, Kp]`` or of its transpose ``[K, Np]`` that
+    ``build`` derives from ``owner`` (a parameter, or a tensor the step assembled from parameters) -- kept on ``owner`` under
+    ``key`` until its storage pointer or in-place version changes, the idiom of :func:`split_planes`: an optimiser step,
+    ``load_state_dict`` or any in-place update is picked up, a parameter that did not change is split once.
+    While a HIP graph is being captured the planes are always rebuilt and not recorded: the split then is part of the
+    graph and every replay re-derives the planes from the parameters as they are (a replayed optimiser step changes them
+    without bumping any version), and an eager step after the capture finds no record pointing into the graph's pool."""
+    capturing = owner.is_cuda and torch.cuda.is_current_stream_capturing()
+    store = owner.__dict__.get("_anemoi_train_split")
+    ver = (owner.data_ptr(), owner._version)
+    if not capturing and store is not None:
+        hit = store.get(key)
+        if hit is not None and hit[0] == ver:
+            return hit[1]
+    with torch.no_grad():
+        planes = ops.split_weight(build())
+    if capturing:
+        if store is not None:
+            store.pop(key, None)
+    else:
+        if store is None:
+            store = owner._anemoi_train_split = {}
+        store[key] = (ver, planes)
+    return planes
+
+
 def linear(x: Tensor, w: Tensor, bias: Optional[Tensor] = None, *, act: str = "Identity",
            residual: Optional[Tensor] = None, out: Optional[Tensor] = None, out_dtype: Optional[torch.dtype] = None,
            n_out: Optional[int] = None, ln=None, stats_eps: Optional[float] = None) -> Tensor:

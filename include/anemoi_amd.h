@@ -713,7 +713,8 @@ int anemoi_linear_mx(const uint8_t* xq, int64_t ldxq, const uint8_t* xs, int64_t
                      int64_t ldy, uint8_t* ys, int64_t ldys, int64_t M, int N, int K, int act, anemoi_stream_t stream);
 
 /*
- * Split-bf16 ("bf16x3") Linear -- opt-in arithmetic of the f32 inference route (csrc/gemm_split.hip).
+ * Split-bf16 ("bf16x3") Linear -- opt-in arithmetic of the f32 inference route (csrc/gemm_split.hip) and, through
+ * anemoi_weight_grad_split below, of f32 training.
  *   split    v = hi + lo (+ a remainder below 2^-16 |v|): hi = bf16(v), lo = bf16(v - float(hi)), round to nearest even both.
  *   product  x W^T ~= x_hi W_hi^T + x_hi W_lo^T + x_lo W_hi^T on the bf16 MFMA, one f32 accumulator (x_lo W_lo^T dropped):
  *            ~4e-6 rms relative error per Linear (exact f32 kernel 3e-7, bf16 operands 2e-3).
@@ -732,6 +733,23 @@ int anemoi_split_weight(const float* w, int64_t ldw, void* w_hi, void* w_lo, int
 int anemoi_linear_split(const float* x, int64_t ldx, const void* w_hi, const void* w_lo, const float* bias,
                         const float* residual, int64_t ldr, float* y, int64_t ldy, int64_t M, int N, int K, int act,
                         anemoi_stream_t stream);
+
+/* Split-bf16 weight gradient (csrc/weight_grad_split.hip): the training counterpart of anemoi_linear_split, switched on by
+ * ANEMOI_AMD_F32_TRAIN_LINEAR=bf16x3.
+ *   partial[c][n * K + k] = sum over the rows m of chunk c of dy[m, n] * x[m, k]      (c = 0 .. ceil(M / chunk_rows) - 1)
+ * with BOTH f32 operands split inside the kernel (hi = bf16(v), lo = bf16(v - hi)) and each product formed as
+ * dy_hi^T x_hi + (dy_hi^T x_lo + dy_lo^T x_hi) on the bf16 MFMA with one f32 accumulator.  dy f32 [M, N] (ldy) and
+ * x f32 [M, >= K] (ldx) are row-major and read as they lie (no transposed copies, no planes in HBM); rows at and behind M
+ * and columns at and behind N / K are never read.  Chunk c covers rows c * chunk_rows .. min(M, (c + 1) * chunk_rows) - 1
+ * and starts partial_stride floats behind chunk c - 1; the caller sums the chunks (anemoi_col_sum over
+ * [chunks, partial_stride]): no atomics, the same bits on every run.  The bias gradient is not produced here
+ * (anemoi_col_sum over dy: exact f32 sums).
+ * Checked before any launch, else ANEMOI_ERR_INVALID: non-null pointers (dy / x may be NULL when M = 0); N and K
+ * multiples of 4; ldy >= N, ldx >= K, both multiples of 4; dy, x and partial 16-byte aligned; chunk_rows a positive
+ * multiple of 32; partial_stride >= N * K and a multiple of 4.  M = 0: partial[0 .. N * K) is zeroed by a memset and
+ * nothing is launched. */
+int anemoi_weight_grad_split(const float* dy, int64_t ldy, const float* x, int64_t ldx, float* partial,
+                             int64_t partial_stride, int64_t M, int N, int K, int chunk_rows, anemoi_stream_t stream);
 
 /*
  * Launch trail -- opt-in per-launch output digests (csrc/trail.hip).

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """One training step (forward, loss, backward) of the flat GraphTransformer model on the HIP kernels through its nn.Module
 at a bench workload:
-   python tools/train_step_bench.py [cfg1|cfg2|cfg3] [steps] [GraphTransformer|GNN|Transformer]"""
+   python tools/train_step_bench.py [cfg1|cfg2|cfg3] [steps] [GraphTransformer|GNN|Transformer]
+``TRAIN_BENCH_AB_SPLIT=1`` (with ``ANEMOI_AMD_DTYPE=fp32``): ``ANEMOI_AMD_F32_TRAIN_LINEAR`` exact / bf16x3 alternated step
+by step in this one process, medians over ``steps`` pairs."""
 import os
 import sys
 import time
@@ -53,6 +55,25 @@ if os.environ.get("TRAIN_BENCH_GRAPH") == "1":  # the whole step as one HIP grap
     print(f"{workload} {processor} (HIP graph): forward + backward {ms:.1f} ms / step (host {host:.2f} ms) = "
           f"{graph['hidden'].num_nodes * layers / ms * 1e3:.3e} mesh-node updates/s (loss {float(lg):.6f}, eager {eager_loss:.6f})",
           flush=True)
+    sys.exit(0)
+if os.environ.get("TRAIN_BENCH_AB_SPLIT") == "1":
+    import statistics
+
+    times, losses = {"exact": [], "bf16x3": []}, {}
+    for mode in times:  # plans, planes and allocator warm-up of both routes
+        os.environ["ANEMOI_AMD_F32_TRAIN_LINEAR"] = mode
+        step(), step()
+    for _ in range(steps):
+        for mode in times:
+            os.environ["ANEMOI_AMD_F32_TRAIN_LINEAR"] = mode
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            losses[mode] = step()  # (float(loss) synchronises)
+            times[mode].append((time.perf_counter() - t0) * 1e3)
+    te, ts = statistics.median(times["exact"]), statistics.median(times["bf16x3"])
+    print(f"{workload} {processor} {os.environ['ANEMOI_AMD_DTYPE']}: forward + backward exact {te:.1f} ms, "
+          f"ANEMOI_AMD_F32_TRAIN_LINEAR=bf16x3 {ts:.1f} ms (x{te / ts:.2f}; medians of {steps} alternated steps; loss "
+          f"{losses['exact']:.6f} / {losses['bf16x3']:.6f})", flush=True)
     sys.exit(0)
 step()
 torch.cuda.synchronize()
