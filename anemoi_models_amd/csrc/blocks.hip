@@ -3,6 +3,7 @@
 // validate the argument block and call the op-level entry points in the order the reference's block runs them
 // (layers/block.py:602-635).
 #include "common.hpp"
+#include "edge_common.hpp"
 
 using namespace anemoi;
 
@@ -40,25 +41,13 @@ int check_args(const anemoi_gt_block_args* a, const char* who, bool with_input) 
 }
 
 int run_tail(const anemoi_gt_block_args* a, anemoi_stream_t stream) {
-  int st;
-  if (a->tile_hdr != nullptr && a->run_ptr == nullptr)
-    st = anemoi_gt_edge_attention_folded_tiles(a->dtype, a->q, a->ldq, a->k, a->v, a->ldkv, a->x_r, a->ldr, a->u, a->ldu,
-                                               a->edge_attr, a->up, a->rowptr, a->col, a->tile_hdr, a->tile_dst, a->tile_src,
-                                               a->tile_slot, a->tile_xcd, a->tile_max_per_xcd, a->tile_src_cap,
-                                               a->tile_edge_cap, a->n_src, a->n_edges, a->att, a->ld_att, nullptr, a->n_dst,
-                                               a->C, a->H, stream);
-  else if (a->sched != nullptr && a->run_ptr == nullptr)
-    st = anemoi_gt_edge_attention_folded_sched(a->dtype, a->q, a->ldq, a->k, a->v, a->ldkv, a->x_r, a->ldr, a->u, a->ldu,
-                                               a->edge_attr, a->up, a->rowptr, a->col, a->sched, a->sched_slots, a->sched_steps,
-                                               a->n_src, a->n_edges, a->att, a->ld_att, nullptr, a->n_dst, a->C, a->H, stream);
-  else if (a->run_ptr != nullptr && a->run_dst != nullptr)
-    st = anemoi_gt_edge_attention_folded_groups(a->dtype, a->q, a->ldq, a->k, a->v, a->ldkv, a->x_r, a->ldr, a->u, a->ldu,
-                                                a->edge_attr, a->up, a->rowptr, a->col, a->run_ptr, a->run_dst, a->run_perm,
-                                                a->n_runs, a->n_src, a->att, a->ld_att, nullptr, a->n_dst, a->C, a->H, stream);
-  else
-    st = anemoi_gt_edge_attention_folded_runs(a->dtype, a->q, a->ldq, a->k, a->v, a->ldkv, a->x_r, a->ldr, a->u, a->ldu,
-                                              a->edge_attr, a->up, a->rowptr, a->col, a->run_ptr, a->run_perm, a->n_runs,
-                                              a->att, a->ld_att, nullptr, a->n_dst, a->C, a->H, stream);
+  // the edge phase into att, on whichever kernel the caller's lists select (edge_attention.hip::folded_edge_phase)
+  const FoldedOperands o = {a->q, a->k, a->v, a->x_r, a->u, a->edge_attr, a->rowptr, a->col, a->att, nullptr, a->ldq, a->ldkv,
+                            a->ldr, a->ldu, a->ld_att, a->n_dst, a->C, a->H, a->up};
+  const FoldedLists l = {a->run_ptr, a->run_perm, a->run_dst, a->n_runs, a->sched, a->sched_slots, a->sched_steps,
+                         a->tile_hdr, a->tile_dst, a->tile_src, a->tile_slot, a->tile_xcd, a->tile_max_per_xcd,
+                         a->tile_src_cap, a->tile_edge_cap, a->n_src, a->n_edges};
+  int st = folded_edge_phase(a->dtype, o, l, as_stream(stream));
   if (st != ANEMOI_OK) return st;
   // y = projection(att) + res, with { rstd, -mean rstd } of y's rows for the node MLP's LayerNorm
   st = anemoi_linear_stats(a->dtype, a->att, a->ld_att, a->w_proj, a->b_proj, nullptr, nullptr, a->res, a->ld_res, a->y,

@@ -13,6 +13,7 @@
 // so XCD x walks the contiguous destination range [x*N/8, (x+1)*N/8) and the k/v rows shared by
 // neighbouring destinations are re-used from that XCD's L2.
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.hpp"
 #include "trail.hpp"
@@ -1754,49 +1755,167 @@ extern "C" int anemoi_gt_conv(int dtype, const void* q, int64_t ldq, const void*
   return rt;
 }
 
+// The folded edge phase's host side: ONE place that checks the arguments, picks the kernel and launches it.  The five
+// anemoi_gt_edge_attention_folded* entry points and the block-level entry points (blocks.hip) all end here.
+namespace anemoi {
+
+enum FoldedRoute { ROUTE_PLAIN, ROUTE_GROUPS, ROUTE_RUNS, ROUTE_TILES, ROUTE_SCHED };
+// the entry point a route's kernel belongs to: what messages and the launch trail name
+static const char* const FOLDED_ENTRY[] = {"anemoi_gt_edge_attention_folded", "anemoi_gt_edge_attention_folded_groups",
+                                           "anemoi_gt_edge_attention_folded_runs", "anemoi_gt_edge_attention_folded_tiles",
+                                           "anemoi_gt_edge_attention_folded_sched"};
+
+// what the four list kernels are instantiated for: bf16, heads of 32 or 64 channels, UP in {4, 8, 12, 16}
+static bool list_kernel_shape(int dtype, const FoldedOperands& o) {
+  return dtype == ANEMOI_BF16 && o.H > 0 && o.C % o.H == 0 && (o.C / o.H == 64 || o.C / o.H == 32) &&
+         (o.up == 4 || o.up == 8 || o.up == 12 || o.up == 16) && o.n_dst != 0;
+}
+// every bf16 operand matrix below `lim` bytes: the kernels address rows as 32-bit byte offsets from the matrix bases
+static bool matrices_below(int64_t lim, const FoldedOperands& o, int64_t n_src) {
+  return n_src * o.ldkv * 2 < lim && o.n_dst * o.ldq * 2 < lim && o.n_dst * o.ldu * 2 < lim && o.n_dst * o.ldo * 2 < lim &&
+         (o.x_r == nullptr || o.n_dst * o.ldr * 2 < lim);
+}
+// Which shapes each list kernel covers; every other call takes the plain kernel.  (n_edges = rowptr[n_dst] lives on the
+// device: the caller states it, and with it the size of the attribute matrix [n_edges, up] f32.)
+static bool groups_cover(int dtype, const FoldedOperands& o, const FoldedLists& l) {
+  const int64_t lim = (int64_t)1 << 32;
+  return l.run_perm != nullptr && l.n_runs > 0 && list_kernel_shape(dtype, o) && matrices_below(lim, o, l.n_src) &&
+         3 * o.n_dst * (int64_t)o.up * 4 < lim;
+}
+static bool runs_cover(int dtype, const FoldedOperands& o, const FoldedLists& l) {
+  return l.run_perm != nullptr && l.n_runs > 0 && list_kernel_shape(dtype, o);
+}
+static bool sched_cover(int dtype, const FoldedOperands& o, const FoldedLists& l) {
+  const int64_t lim = (int64_t)1 << 32;
+  return list_kernel_shape(dtype, o) && l.n_src > 0 && matrices_below(lim, o, l.n_src) && l.n_edges > 0 &&
+         l.n_edges * (int64_t)o.up * 4 < lim;
+}
+static bool tiles_cover(int dtype, const FoldedOperands& o, const FoldedLists& l) {
+  const int64_t lim = (int64_t)1 << 31;  // (row offsets + lane offsets are formed as signed 32-bit voffsets)
+  return list_kernel_shape(dtype, o) && o.C % 128 == 0 && l.n_src > 0 && matrices_below(lim, o, l.n_src) && l.n_edges > 0 &&
+         l.tile_max_per_xcd > 0;
+}
+
+static EdgeFoldParams fold_params(const FoldedOperands& o, int vec) {
+  EdgeFoldParams p;
+  p.q = o.q; p.k = o.k; p.v = o.v; p.xr = o.x_r; p.u = o.u; p.out = o.out; p.lse = o.lse;
+  p.ldq = o.ldq; p.ldkv = o.ldkv; p.ldr = o.ldr; p.ldu = o.ldu; p.ldo = o.ldo;
+  p.attr = o.edge_attr; p.rowptr = o.rowptr; p.col = o.col;
+  p.n_dst = o.n_dst; p.C = o.C; p.D = o.C / o.H;
+  p.n_slices = (o.C + 64 * vec - 1) / (64 * vec);
+  p.scale = 1.0f / sqrtf((float)(o.C / o.H));
+  p.stream_hint = 1;  // nontemporal q / x_r / out (streamed once): -3 % on all three graphs of config 3
+  return p;
+}
+
+// the list kernels' instantiations (list_kernel_shape): launch(lanes per head, UP) with both as integral constants
+template <typename Launch>
+static void dispatch_list_kernel(int D, int up, Launch&& launch) {
+  auto with_lph = [&](auto lph) {
+    switch (up) {
+      case 4: launch(lph, std::integral_constant<int, 4>{}); break;
+      case 8: launch(lph, std::integral_constant<int, 8>{}); break;
+      case 12: launch(lph, std::integral_constant<int, 12>{}); break;
+      default: launch(lph, std::integral_constant<int, 16>{}); break;
+    }
+  };
+  if (D == 64) with_lph(std::integral_constant<int, 8>{});
+  else with_lph(std::integral_constant<int, 4>{});
+}
+
+int folded_edge_phase(int dtype, const FoldedOperands& o, const FoldedLists& l, hipStream_t st) {
+  FoldedRoute route = ROUTE_PLAIN;
+  if (l.run_ptr != nullptr && l.run_dst != nullptr) route = groups_cover(dtype, o, l) ? ROUTE_GROUPS : ROUTE_PLAIN;
+  else if (l.run_ptr != nullptr) route = runs_cover(dtype, o, l) ? ROUTE_RUNS : ROUTE_PLAIN;
+  else if (l.tile_hdr != nullptr) route = tiles_cover(dtype, o, l) ? ROUTE_TILES : ROUTE_PLAIN;
+  else if (l.sched != nullptr) route = sched_cover(dtype, o, l) ? ROUTE_SCHED : ROUTE_PLAIN;
+  const char* who = FOLDED_ENTRY[route];
+  // (the uniform-degree-3 kernels and the tile kernel never read rowptr; the tile kernel has its edges in its lists)
+  const bool reads_rowptr = route == ROUTE_PLAIN || route == ROUTE_SCHED, reads_col = route != ROUTE_TILES;
+  ANEMOI_REQUIRE(o.q && o.k && o.v && o.u && o.out && (o.rowptr || !reads_rowptr), ANEMOI_ERR_INVALID, "%s: null pointer", who);
+  ANEMOI_REQUIRE(o.C > 0 && o.H > 0 && o.C % o.H == 0, ANEMOI_ERR_INVALID, "%s: C=%d not divisible by H=%d", who, o.C, o.H);
+  ANEMOI_REQUIRE(o.ldq >= o.C && o.ldkv >= o.C && o.ldu >= (int64_t)o.H * o.up &&
+                     o.ldo >= (int64_t)o.C + (int64_t)o.H * o.up && (o.x_r == nullptr || o.ldr >= o.C),
+                 ANEMOI_ERR_INVALID, "%s: leading dimension too small", who);
+  ANEMOI_REQUIRE(o.n_dst >= 0, ANEMOI_ERR_INVALID, "%s: n_dst < 0", who);
+  if (o.n_dst == 0) return ANEMOI_OK;
+  ANEMOI_REQUIRE(o.edge_attr != nullptr && (o.col != nullptr || !reads_col), ANEMOI_ERR_INVALID, "%s: null edge arrays", who);
+  if (route == ROUTE_GROUPS) {
+    ANEMOI_REQUIRE(l.n_runs <= o.n_dst && EDGE_MAX_GROUP * l.n_runs >= o.n_dst && l.n_src > 0, ANEMOI_ERR_INVALID,
+                   "%s: %lld groups cannot cover %lld destinations with groups of 1 .. %d", who, (long long)l.n_runs,
+                   (long long)o.n_dst, EDGE_MAX_GROUP);
+  } else if (route == ROUTE_RUNS) {
+    ANEMOI_REQUIRE(l.n_runs <= o.n_dst && EDGE_MAX_RUN * l.n_runs >= o.n_dst, ANEMOI_ERR_INVALID,
+                   "%s: %lld runs cannot cover %lld destinations with runs of 1 or 2 (the kernel handles runs of at most two; "
+                   "rowptr[d] = 3 d is the caller's contract)", who, (long long)l.n_runs, (long long)o.n_dst);
+  } else if (route == ROUTE_SCHED) {
+    int want_slots = 0, want_steps = 0;
+    sched_shape(o.n_dst, (o.C + 511) / 512, &want_slots, &want_steps);
+    ANEMOI_REQUIRE(l.sched_slots == want_slots && l.sched_steps >= want_steps, ANEMOI_ERR_INVALID,
+                   "%s: schedule of %d slots x %d steps, this launch needs %d x >= %d (anemoi_edge_schedule_shape)", who,
+                   l.sched_slots, l.sched_steps, want_slots, want_steps);
+  } else if (route == ROUTE_TILES) {
+    ANEMOI_REQUIRE(l.tile_dst && l.tile_src && l.tile_slot && l.tile_xcd, ANEMOI_ERR_INVALID, "%s: null pointer", who);
+    // (the kernel stages sources in pieces of four: a cap that is no multiple of 4 would run the k region over into v's)
+    ANEMOI_REQUIRE(l.tile_src_cap > 0 && l.tile_src_cap <= 255 && l.tile_src_cap % 4 == 0 && l.tile_edge_cap > 0 &&
+                       l.tile_edge_cap % 16 == 0 && tiles_lds_bytes(l.tile_src_cap, l.tile_edge_cap, o.up) <= 64 * 1024,
+                   ANEMOI_ERR_INVALID,
+                   "%s: tile caps %d sources / %d edges (<= 255 and a multiple of 4, a multiple of 16, LDS <= 64 KiB)", who,
+                   l.tile_src_cap, l.tile_edge_cap);
+  }
+  const int esz = dtype == ANEMOI_BF16 ? 2 : 4;
+  const int vec = 16 / esz;
+  const bool aligned = ((uintptr_t)o.q % 16 == 0) && ((uintptr_t)o.k % 16 == 0) && ((uintptr_t)o.v % 16 == 0) &&
+                       ((uintptr_t)o.u % 16 == 0) && ((uintptr_t)o.out % 16 == 0) &&
+                       (o.x_r == nullptr || ((uintptr_t)o.x_r % 16 == 0 && o.ldr % vec == 0)) && o.ldq % vec == 0 &&
+                       o.ldkv % vec == 0 && o.ldu % vec == 0 && o.ldo % vec == 0 && ((uintptr_t)o.edge_attr % 16 == 0) &&
+                       ((int64_t)o.up * esz) % 8 == 0 && ((int64_t)o.C * esz) % 16 == 0 &&
+                       (route != ROUTE_TILES || (uintptr_t)l.tile_slot % 16 == 0);
+  ANEMOI_REQUIRE(aligned, ANEMOI_ERR_UNSUPPORTED, "%s: operands must be 16-byte aligned", who);
+  EdgeFoldParams p = fold_params(o, vec);
+  if (route == ROUTE_GROUPS) {
+    dispatch_list_kernel(p.D, o.up, [&](auto lph, auto up) {
+      launch_folded_groups3<bf16_t, 8, decltype(lph)::value, decltype(up)::value>(p, l.run_ptr, l.run_dst, l.run_perm, l.n_runs, st);
+    });
+  } else if (route == ROUTE_RUNS) {
+    dispatch_list_kernel(p.D, o.up, [&](auto lph, auto up) {
+      launch_folded_runs<bf16_t, 8, decltype(lph)::value, decltype(up)::value>(p, l.run_ptr, l.run_perm, l.n_runs, st);
+    });
+  } else if (route == ROUTE_TILES) {
+    p.n_slices = o.C / 128;  // a workgroup per tile and 128-channel slice
+    EdgeTileLists tl;
+    tl.hdr = l.tile_hdr; tl.dst = l.tile_dst; tl.src = l.tile_src; tl.slot = l.tile_slot; tl.xcd = l.tile_xcd;
+    tl.src_cap = l.tile_src_cap; tl.edge_cap = l.tile_edge_cap; tl.n_src = l.n_src;
+    dispatch_list_kernel(p.D, o.up, [&](auto lph, auto up) {
+      launch_folded_tiles<bf16_t, decltype(lph)::value, decltype(up)::value>(p, tl, l.tile_max_per_xcd, st);
+    });
+  } else if (route == ROUTE_SCHED) {
+    dispatch_list_kernel(p.D, o.up, [&](auto lph, auto up) {
+      launch_folded_sched<bf16_t, 8, decltype(lph)::value, decltype(up)::value>(p, l.sched, l.sched_slots, l.sched_steps, st);
+    });
+  } else {
+    bool ok = false;
+    if (dtype == ANEMOI_F32) ok = dispatch_folded<float>(p, o.up, st);
+    else if (dtype == ANEMOI_BF16) ok = dispatch_folded<bf16_t>(p, o.up, st);
+    else return fail(ANEMOI_ERR_UNSUPPORTED, "%s: dtype %d", who, dtype);
+    ANEMOI_REQUIRE(ok, ANEMOI_ERR_UNSUPPORTED, "%s: unsupported shape (D=%d, UP=%d); use anemoi_gt_edge_attention", who,
+                   o.C / o.H, o.up);
+  }
+  // the launch trail names the entry point whose kernel ran
+  int rt = trail::note(check_launch(who), who, "out", dtype, o.out, o.ldo, o.n_dst, (int64_t)o.C + (int64_t)o.H * o.up, st);
+  if (o.lse != nullptr) rt = trail::note(rt, who, "lse", ANEMOI_F32, o.lse, o.H, o.n_dst, o.H, st);
+  return rt;
+}
+
+}  // namespace anemoi
+
 extern "C" int anemoi_gt_edge_attention_folded(int dtype, const void* q, int64_t ldq, const void* k, const void* v,
                                                int64_t ldkv, const void* x_r, int64_t ldr, const void* u, int64_t ldu,
                                                const float* edge_attr, int up, const int32_t* rowptr,
                                                const int32_t* col, void* out, int64_t ldo, float* lse, int64_t n_dst,
                                                int C, int H, anemoi_stream_t stream) {
-  ANEMOI_REQUIRE(q && k && v && u && out && rowptr, ANEMOI_ERR_INVALID,
-                 "anemoi_gt_edge_attention_folded: null pointer");
-  ANEMOI_REQUIRE(C > 0 && H > 0 && C % H == 0, ANEMOI_ERR_INVALID,
-                 "anemoi_gt_edge_attention_folded: C=%d not divisible by H=%d", C, H);
-  ANEMOI_REQUIRE(ldq >= C && ldkv >= C && ldu >= (int64_t)H * up && ldo >= (int64_t)C + (int64_t)H * up &&
-                     (x_r == nullptr || ldr >= C),
-                 ANEMOI_ERR_INVALID, "anemoi_gt_edge_attention_folded: leading dimension too small");
-  ANEMOI_REQUIRE(n_dst >= 0, ANEMOI_ERR_INVALID, "anemoi_gt_edge_attention_folded: n_dst < 0");
-  if (n_dst == 0) return ANEMOI_OK;
-  ANEMOI_REQUIRE(col != nullptr && edge_attr != nullptr, ANEMOI_ERR_INVALID,
-                 "anemoi_gt_edge_attention_folded: null edge arrays");
-  const int esz = dtype == ANEMOI_BF16 ? 2 : 4;
-  const int vec = 16 / esz;
-  const bool aligned = ((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) &&
-                       ((uintptr_t)u % 16 == 0) && ((uintptr_t)out % 16 == 0) &&
-                       (x_r == nullptr || ((uintptr_t)x_r % 16 == 0 && ldr % vec == 0)) && ldq % vec == 0 &&
-                       ldkv % vec == 0 && ldu % vec == 0 && ldo % vec == 0 && ((uintptr_t)edge_attr % 16 == 0) &&
-                       ((int64_t)up * esz) % 8 == 0 && ((int64_t)C * esz) % 16 == 0;
-  ANEMOI_REQUIRE(aligned, ANEMOI_ERR_UNSUPPORTED, "anemoi_gt_edge_attention_folded: operands must be 16-byte aligned");
-  EdgeFoldParams p;
-  p.q = q; p.k = k; p.v = v; p.xr = x_r; p.u = u; p.out = out; p.lse = lse;
-  p.ldq = ldq; p.ldkv = ldkv; p.ldr = ldr; p.ldu = ldu; p.ldo = ldo;
-  p.attr = edge_attr; p.rowptr = rowptr; p.col = col;
-  p.n_dst = n_dst; p.C = C; p.D = C / H;
-  p.n_slices = (C + 64 * vec - 1) / (64 * vec);
-  p.scale = 1.0f / sqrtf((float)(C / H));
-  p.stream_hint = 1;  // nontemporal q / x_r / out (streamed once): -3 % on all three graphs of config 3
-  bool ok = false;
-  if (dtype == ANEMOI_F32) ok = dispatch_folded<float>(p, up, as_stream(stream));
-  else if (dtype == ANEMOI_BF16) ok = dispatch_folded<bf16_t>(p, up, as_stream(stream));
-  else return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_gt_edge_attention_folded: dtype %d", dtype);
-  ANEMOI_REQUIRE(ok, ANEMOI_ERR_UNSUPPORTED,
-                 "anemoi_gt_edge_attention_folded: unsupported shape (D=%d, UP=%d); use anemoi_gt_edge_attention", C / H,
-                 up);
-  int rt = trail::note(check_launch("anemoi_gt_edge_attention_folded"), "anemoi_gt_edge_attention_folded", "out", dtype, out, ldo,
-                       n_dst, (int64_t)C + (int64_t)H * up, as_stream(stream));
-  if (lse != nullptr) rt = trail::note(rt, "anemoi_gt_edge_attention_folded", "lse", ANEMOI_F32, lse, H, n_dst, H, as_stream(stream));
-  return rt;
+  return folded_edge_phase(dtype, {q, k, v, x_r, u, edge_attr, rowptr, col, out, lse, ldq, ldkv, ldr, ldu, ldo, n_dst, C, H, up},
+                           FoldedLists{}, as_stream(stream));
 }
 
 // Launch geometry of anemoi_gt_edge_attention_folded_sched for a destination count / channel width / dtype: wave slots
@@ -1821,119 +1940,33 @@ extern "C" int anemoi_gt_edge_attention_folded_groups(int dtype, const void* q, 
                                                       const int32_t* grp_perm, int64_t n_groups, int64_t n_src, void* out,
                                                       int64_t ldo, float* lse, int64_t n_dst, int C, int H,
                                                       anemoi_stream_t stream) {
-  const int64_t gib4 = (int64_t)1 << 32;
-  const bool small = n_dst * ldq * 2 < gib4 && n_dst * ldu * 2 < gib4 && n_dst * ldo * 2 < gib4 && n_src * ldkv * 2 < gib4 &&
-                     (x_r == nullptr || n_dst * ldr * 2 < gib4) && 3 * n_dst * (int64_t)up * 4 < gib4;
-  const bool plain = grp_ptr == nullptr || grp_dst == nullptr || grp_perm == nullptr || n_groups <= 0 || dtype != ANEMOI_BF16 ||
-                     H <= 0 || C % H != 0 || !((C / H) == 64 || (C / H) == 32) ||
-                     !(up == 4 || up == 8 || up == 12 || up == 16) || n_dst == 0 || !small;
-  if (plain)
-    return anemoi_gt_edge_attention_folded(dtype, q, ldq, k, v, ldkv, x_r, ldr, u, ldu, edge_attr, up, rowptr, col, out, ldo,
-                                           lse, n_dst, C, H, stream);
-  const char* who = "anemoi_gt_edge_attention_folded_groups";
-  ANEMOI_REQUIRE(q && k && v && u && out && col && edge_attr, ANEMOI_ERR_INVALID, "%s: null pointer", who);
-  ANEMOI_REQUIRE(ldq >= C && ldkv >= C && ldu >= (int64_t)H * up && ldo >= (int64_t)C + (int64_t)H * up &&
-                     (x_r == nullptr || ldr >= C) && n_groups <= n_dst && EDGE_MAX_GROUP * n_groups >= n_dst && n_src > 0,
-                 ANEMOI_ERR_INVALID,
-                 "%s: leading dimension too small, or %lld groups cannot cover %lld destinations with groups of 1 .. %d", who,
-                 (long long)n_groups, (long long)n_dst, EDGE_MAX_GROUP);
-  const bool aligned = ((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) &&
-                       ((uintptr_t)u % 16 == 0) && ((uintptr_t)out % 16 == 0) &&
-                       (x_r == nullptr || ((uintptr_t)x_r % 16 == 0 && ldr % 8 == 0)) && ldq % 8 == 0 && ldkv % 8 == 0 &&
-                       ldu % 8 == 0 && ldo % 8 == 0 && ((uintptr_t)edge_attr % 16 == 0) && C % 8 == 0;
-  ANEMOI_REQUIRE(aligned, ANEMOI_ERR_UNSUPPORTED, "%s: operands must be 16-byte aligned", who);
-  EdgeFoldParams p;
-  p.q = q; p.k = k; p.v = v; p.xr = x_r; p.u = u; p.out = out; p.lse = lse;
-  p.ldq = ldq; p.ldkv = ldkv; p.ldr = ldr; p.ldu = ldu; p.ldo = ldo;
-  p.attr = edge_attr; p.rowptr = rowptr; p.col = col;
-  p.n_dst = n_dst; p.C = C; p.D = C / H;
-  p.n_slices = (C + 511) / 512;
-  p.scale = 1.0f / sqrtf((float)(C / H));
-  p.stream_hint = 1;
-  hipStream_t st = as_stream(stream);
-#define ANEMOI_GROUPS_UP(LPH)                                                                                       \
-  switch (up) {                                                                                                     \
-    case 4: launch_folded_groups3<bf16_t, 8, LPH, 4>(p, grp_ptr, grp_dst, grp_perm, n_groups, st); break;           \
-    case 8: launch_folded_groups3<bf16_t, 8, LPH, 8>(p, grp_ptr, grp_dst, grp_perm, n_groups, st); break;           \
-    case 12: launch_folded_groups3<bf16_t, 8, LPH, 12>(p, grp_ptr, grp_dst, grp_perm, n_groups, st); break;         \
-    default: launch_folded_groups3<bf16_t, 8, LPH, 16>(p, grp_ptr, grp_dst, grp_perm, n_groups, st); break;         \
+  FoldedLists l{};
+  if (grp_dst != nullptr) {  // (without it the lists would read as consecutive runs)
+    l.run_ptr = grp_ptr; l.run_dst = grp_dst; l.run_perm = grp_perm; l.n_runs = n_groups; l.n_src = n_src;
   }
-  if (C / H == 64) {
-    ANEMOI_GROUPS_UP(8)
-  } else {
-    ANEMOI_GROUPS_UP(4)
-  }
-#undef ANEMOI_GROUPS_UP
-  int rt = trail::note(check_launch(who), who, "out", dtype, out, ldo, n_dst, (int64_t)C + (int64_t)H * up, st);
-  if (lse != nullptr) rt = trail::note(rt, who, "lse", ANEMOI_F32, lse, H, n_dst, H, st);
-  return rt;
+  return folded_edge_phase(dtype, {q, k, v, x_r, u, edge_attr, rowptr, col, out, lse, ldq, ldkv, ldr, ldu, ldo, n_dst, C, H, up},
+                           l, as_stream(stream));
 }
 
 // anemoi_gt_edge_attention_folded with a destination schedule (gt_edge_attention_folded_sched_kernel above): the same
 // result bit for bit.  ``sched`` int32 [8][slots][steps] as anemoi_edge_schedule_shape prescribes; every destination of
 // XCD x's range exactly once in XCD x's lists (the host builds it: runtime.EdgePlan.schedule); bf16 with 32- or 64-channel
-// heads -- every other shape takes the plain kernel.
+// heads, every matrix below 4 GiB -- every other shape takes the plain kernel.
 extern "C" int anemoi_gt_edge_attention_folded_sched(int dtype, const void* q, int64_t ldq, const void* k, const void* v,
                                                      int64_t ldkv, const void* x_r, int64_t ldr, const void* u, int64_t ldu,
                                                      const float* edge_attr, int up, const int32_t* rowptr,
                                                      const int32_t* col, const int32_t* sched, int slots, int steps,
                                                      int64_t n_src, int64_t n_edges, void* out, int64_t ldo, float* lse,
                                                      int64_t n_dst, int C, int H, anemoi_stream_t stream) {
-  // the kernel addresses rows as 32-bit byte offsets from the matrix bases (buffer loads): every matrix below 4 GiB, the
-  // attribute matrix [n_edges, up] f32 included (n_edges = rowptr[n_dst] lives on the device: the caller states it)
-  const int64_t lim = (int64_t)1 << 32;
-  const bool fits = n_src > 0 && n_src * ldkv * 2 < lim && n_dst * ldq * 2 < lim && n_dst * ldu * 2 < lim && n_dst * ldo * 2 < lim &&
-                    (x_r == nullptr || n_dst * ldr * 2 < lim) && n_edges > 0 && n_edges * (int64_t)up * 4 < lim;
-  const bool plain = sched == nullptr || dtype != ANEMOI_BF16 || H <= 0 || C % H != 0 || !((C / H) == 64 || (C / H) == 32) ||
-                     !(up == 4 || up == 8 || up == 12 || up == 16) || n_dst == 0 || !fits;
-  if (plain)
-    return anemoi_gt_edge_attention_folded(dtype, q, ldq, k, v, ldkv, x_r, ldr, u, ldu, edge_attr, up, rowptr, col, out, ldo,
-                                           lse, n_dst, C, H, stream);
-  const char* who = "anemoi_gt_edge_attention_folded_sched";
-  ANEMOI_REQUIRE(q && k && v && u && out && col && edge_attr && rowptr, ANEMOI_ERR_INVALID, "%s: null pointer", who);
-  ANEMOI_REQUIRE(ldq >= C && ldkv >= C && ldu >= (int64_t)H * up && ldo >= (int64_t)C + (int64_t)H * up &&
-                     (x_r == nullptr || ldr >= C),
-                 ANEMOI_ERR_INVALID, "%s: leading dimension too small", who);
-  int want_slots = 0, want_steps = 0;
-  sched_shape(n_dst, (C + 511) / 512, &want_slots, &want_steps);
-  ANEMOI_REQUIRE(slots == want_slots && steps >= want_steps, ANEMOI_ERR_INVALID,
-                 "%s: schedule of %d slots x %d steps, this launch needs %d x >= %d (anemoi_edge_schedule_shape)", who, slots,
-                 steps, want_slots, want_steps);
-  const bool aligned = ((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) &&
-                       ((uintptr_t)u % 16 == 0) && ((uintptr_t)out % 16 == 0) &&
-                       (x_r == nullptr || ((uintptr_t)x_r % 16 == 0 && ldr % 8 == 0)) && ldq % 8 == 0 && ldkv % 8 == 0 &&
-                       ldu % 8 == 0 && ldo % 8 == 0 && ((uintptr_t)edge_attr % 16 == 0) && C % 8 == 0;
-  ANEMOI_REQUIRE(aligned, ANEMOI_ERR_UNSUPPORTED, "%s: operands must be 16-byte aligned", who);
-  EdgeFoldParams p;
-  p.q = q; p.k = k; p.v = v; p.xr = x_r; p.u = u; p.out = out; p.lse = lse;
-  p.ldq = ldq; p.ldkv = ldkv; p.ldr = ldr; p.ldu = ldu; p.ldo = ldo;
-  p.attr = edge_attr; p.rowptr = rowptr; p.col = col;
-  p.n_dst = n_dst; p.C = C; p.D = C / H;
-  p.n_slices = (C + 511) / 512;
-  p.scale = 1.0f / sqrtf((float)(C / H));
-  p.stream_hint = 1;
-  hipStream_t st = as_stream(stream);
-#define ANEMOI_SCHED_UP(LPH)                                                                                   \
-  switch (up) {                                                                                                \
-    case 4: launch_folded_sched<bf16_t, 8, LPH, 4>(p, sched, slots, steps, st); break;                         \
-    case 8: launch_folded_sched<bf16_t, 8, LPH, 8>(p, sched, slots, steps, st); break;                         \
-    case 12: launch_folded_sched<bf16_t, 8, LPH, 12>(p, sched, slots, steps, st); break;                       \
-    default: launch_folded_sched<bf16_t, 8, LPH, 16>(p, sched, slots, steps, st); break;                       \
-  }
-  if (C / H == 64) {
-    ANEMOI_SCHED_UP(8)
-  } else {
-    ANEMOI_SCHED_UP(4)
-  }
-#undef ANEMOI_SCHED_UP
-  int rt = trail::note(check_launch(who), who, "out", dtype, out, ldo, n_dst, (int64_t)C + (int64_t)H * up, st);
-  if (lse != nullptr) rt = trail::note(rt, who, "lse", ANEMOI_F32, lse, H, n_dst, H, st);
-  return rt;
+  FoldedLists l{};
+  l.sched = sched; l.sched_slots = slots; l.sched_steps = steps; l.n_src = n_src; l.n_edges = n_edges;
+  return folded_edge_phase(dtype, {q, k, v, x_r, u, edge_attr, rowptr, col, out, lse, ldq, ldkv, ldr, ldu, ldo, n_dst, C, H, up},
+                           l, as_stream(stream));
 }
 
 // anemoi_gt_edge_attention_folded on LDS TILES (gt_edge_attention_folded_tiles_kernel above): the same result bit for bit.
 // The tile lists are the host's (anemoi_models_amd/runtime.py::EdgeTiles); bf16, 32- or 64-channel heads, C a multiple of 128,
-// every operand matrix below 4 GiB -- every other case (or tile_hdr == NULL) runs the plain kernel.
+// every operand matrix below 2 GiB -- every other case (or tile_hdr == NULL) runs the plain kernel.
 extern "C" int anemoi_gt_edge_attention_folded_tiles(int dtype, const void* q, int64_t ldq, const void* k, const void* v,
                                                      int64_t ldkv, const void* x_r, int64_t ldr, const void* u, int64_t ldu,
                                                      const float* edge_attr, int up, const int32_t* rowptr,
@@ -1942,60 +1975,12 @@ extern "C" int anemoi_gt_edge_attention_folded_tiles(int dtype, const void* q, i
                                                      const int32_t* tile_xcd, int max_tiles_per_xcd, int src_cap,
                                                      int edge_cap, int64_t n_src, int64_t n_edges, void* out, int64_t ldo,
                                                      float* lse, int64_t n_dst, int C, int H, anemoi_stream_t stream) {
-  const int64_t lim = (int64_t)1 << 31;  // (row offsets + lane offsets are formed as signed 32-bit voffsets)
-  const bool fits = n_src > 0 && n_src * ldkv * 2 < lim && n_dst * ldq * 2 < lim && n_dst * ldu * 2 < lim && n_dst * ldo * 2 < lim &&
-                    (x_r == nullptr || n_dst * ldr * 2 < lim) && n_edges > 0;
-  const bool plain = tile_hdr == nullptr || dtype != ANEMOI_BF16 || H <= 0 || C % H != 0 || !((C / H) == 64 || (C / H) == 32) ||
-                     C % 128 != 0 || !(up == 4 || up == 8 || up == 12 || up == 16) || n_dst == 0 || !fits ||
-                     max_tiles_per_xcd <= 0;
-  if (plain)
-    return anemoi_gt_edge_attention_folded(dtype, q, ldq, k, v, ldkv, x_r, ldr, u, ldu, edge_attr, up, rowptr, col, out, ldo,
-                                           lse, n_dst, C, H, stream);
-  const char* who = "anemoi_gt_edge_attention_folded_tiles";
-  ANEMOI_REQUIRE(q && k && v && u && out && edge_attr && tile_dst && tile_src && tile_slot && tile_xcd, ANEMOI_ERR_INVALID,
-                 "%s: null pointer", who);
-  ANEMOI_REQUIRE(ldq >= C && ldkv >= C && ldu >= (int64_t)H * up && ldo >= (int64_t)C + (int64_t)H * up &&
-                     (x_r == nullptr || ldr >= C),
-                 ANEMOI_ERR_INVALID, "%s: leading dimension too small", who);
-  ANEMOI_REQUIRE(src_cap > 0 && src_cap <= 255 && edge_cap > 0 && edge_cap % 16 == 0 &&
-                     tiles_lds_bytes(src_cap, edge_cap, up) <= 64 * 1024,
-                 ANEMOI_ERR_INVALID, "%s: tile caps %d sources / %d edges (<= 255, a multiple of 16, LDS <= 64 KiB)", who, src_cap,
-                 edge_cap);
-  const bool aligned = ((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) &&
-                       ((uintptr_t)u % 16 == 0) && ((uintptr_t)out % 16 == 0) &&
-                       (x_r == nullptr || ((uintptr_t)x_r % 16 == 0 && ldr % 8 == 0)) && ldq % 8 == 0 && ldkv % 8 == 0 &&
-                       ldu % 8 == 0 && ldo % 8 == 0 && ((uintptr_t)edge_attr % 16 == 0) && ((uintptr_t)tile_slot % 16 == 0);
-  ANEMOI_REQUIRE(aligned, ANEMOI_ERR_UNSUPPORTED, "%s: operands must be 16-byte aligned", who);
-  EdgeFoldParams p;
-  p.q = q; p.k = k; p.v = v; p.xr = x_r; p.u = u; p.out = out; p.lse = lse;
-  p.ldq = ldq; p.ldkv = ldkv; p.ldr = ldr; p.ldu = ldu; p.ldo = ldo;
-  p.attr = edge_attr; p.rowptr = rowptr; p.col = col;
-  p.n_dst = n_dst; p.C = C; p.D = C / H;
-  p.n_slices = C / 128;
-  p.scale = 1.0f / sqrtf((float)(C / H));
-  p.stream_hint = 1;
-  EdgeTileLists tl;
-  tl.hdr = tile_hdr; tl.dst = tile_dst; tl.src = tile_src; tl.slot = tile_slot; tl.xcd = tile_xcd;
-  tl.src_cap = src_cap; tl.edge_cap = edge_cap; tl.n_src = n_src;
-  hipStream_t st = as_stream(stream);
-  int rc = ANEMOI_OK;
-#define ANEMOI_TILES_UP(LPH)                                                                        \
-  switch (up) {                                                                                     \
-    case 4: rc = launch_folded_tiles<bf16_t, LPH, 4>(p, tl, max_tiles_per_xcd, st); break;          \
-    case 8: rc = launch_folded_tiles<bf16_t, LPH, 8>(p, tl, max_tiles_per_xcd, st); break;          \
-    case 12: rc = launch_folded_tiles<bf16_t, LPH, 12>(p, tl, max_tiles_per_xcd, st); break;        \
-    default: rc = launch_folded_tiles<bf16_t, LPH, 16>(p, tl, max_tiles_per_xcd, st); break;        \
-  }
-  if (C / H == 64) {
-    ANEMOI_TILES_UP(8)
-  } else {
-    ANEMOI_TILES_UP(4)
-  }
-#undef ANEMOI_TILES_UP
-  if (rc != ANEMOI_OK) return rc;
-  int rt = trail::note(check_launch(who), who, "out", dtype, out, ldo, n_dst, (int64_t)C + (int64_t)H * up, st);
-  if (lse != nullptr) rt = trail::note(rt, who, "lse", ANEMOI_F32, lse, H, n_dst, H, st);
-  return rt;
+  FoldedLists l{};
+  l.tile_hdr = tile_hdr; l.tile_dst = tile_dst; l.tile_src = tile_src; l.tile_slot = tile_slot; l.tile_xcd = tile_xcd;
+  l.tile_max_per_xcd = max_tiles_per_xcd; l.tile_src_cap = src_cap; l.tile_edge_cap = edge_cap;
+  l.n_src = n_src; l.n_edges = n_edges;
+  return folded_edge_phase(dtype, {q, k, v, x_r, u, edge_attr, rowptr, col, out, lse, ldq, ldkv, ldr, ldu, ldo, n_dst, C, H, up},
+                           l, as_stream(stream));
 }
 
 // The folded edge phase on a uniform-degree-3 graph with its runs of destinations that share their three sources
@@ -2007,47 +1992,8 @@ extern "C" int anemoi_gt_edge_attention_folded_runs(int dtype, const void* q, in
                                                     const int32_t* col, const int32_t* run_ptr, const int32_t* run_perm,
                                                     int64_t n_runs, void* out, int64_t ldo, float* lse, int64_t n_dst, int C,
                                                     int H, anemoi_stream_t stream) {
-  const bool plain = run_ptr == nullptr || run_perm == nullptr || n_runs <= 0 || dtype != ANEMOI_BF16 || H <= 0 || C % H != 0 ||
-                     !((C / H) == 64 || (C / H) == 32) || !(up == 4 || up == 8 || up == 12 || up == 16) || n_dst == 0;
-  if (plain)
-    return anemoi_gt_edge_attention_folded(dtype, q, ldq, k, v, ldkv, x_r, ldr, u, ldu, edge_attr, up, rowptr, col, out, ldo,
-                                           lse, n_dst, C, H, stream);
-  const char* who = "anemoi_gt_edge_attention_folded_runs";
-  ANEMOI_REQUIRE(q && k && v && u && out && col && edge_attr, ANEMOI_ERR_INVALID, "%s: null pointer", who);
-  ANEMOI_REQUIRE(ldq >= C && ldkv >= C && ldu >= (int64_t)H * up && ldo >= (int64_t)C + (int64_t)H * up &&
-                     (x_r == nullptr || ldr >= C) && n_runs <= n_dst && 2 * n_runs >= n_dst,
-                 ANEMOI_ERR_INVALID,
-                 "%s: leading dimension too small, or %lld runs cannot cover %lld destinations with runs of 1 or 2 (the kernel "
-                 "handles runs of at most two; rowptr[d] = 3 d is the caller's contract)", who, (long long)n_runs,
-                 (long long)n_dst);
-  const bool aligned = ((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) &&
-                       ((uintptr_t)u % 16 == 0) && ((uintptr_t)out % 16 == 0) &&
-                       (x_r == nullptr || ((uintptr_t)x_r % 16 == 0 && ldr % 8 == 0)) && ldq % 8 == 0 && ldkv % 8 == 0 &&
-                       ldu % 8 == 0 && ldo % 8 == 0 && ((uintptr_t)edge_attr % 16 == 0) && C % 8 == 0;
-  ANEMOI_REQUIRE(aligned, ANEMOI_ERR_UNSUPPORTED, "%s: operands must be 16-byte aligned", who);
-  EdgeFoldParams p;
-  p.q = q; p.k = k; p.v = v; p.xr = x_r; p.u = u; p.out = out; p.lse = lse;
-  p.ldq = ldq; p.ldkv = ldkv; p.ldr = ldr; p.ldu = ldu; p.ldo = ldo;
-  p.attr = edge_attr; p.rowptr = rowptr; p.col = col;
-  p.n_dst = n_dst; p.C = C; p.D = C / H;
-  p.n_slices = (C + 511) / 512;
-  p.scale = 1.0f / sqrtf((float)(C / H));
-  p.stream_hint = 1;
-  hipStream_t st = as_stream(stream);
-#define ANEMOI_RUNS_UP(LPH)                                                                                     \
-  switch (up) {                                                                                                 \
-    case 4: launch_folded_runs<bf16_t, 8, LPH, 4>(p, run_ptr, run_perm, n_runs, st); break;                     \
-    case 8: launch_folded_runs<bf16_t, 8, LPH, 8>(p, run_ptr, run_perm, n_runs, st); break;                     \
-    case 12: launch_folded_runs<bf16_t, 8, LPH, 12>(p, run_ptr, run_perm, n_runs, st); break;                   \
-    default: launch_folded_runs<bf16_t, 8, LPH, 16>(p, run_ptr, run_perm, n_runs, st); break;                   \
-  }
-  if (C / H == 64) {
-    ANEMOI_RUNS_UP(8)
-  } else {
-    ANEMOI_RUNS_UP(4)
-  }
-#undef ANEMOI_RUNS_UP
-  int rt = trail::note(check_launch(who), who, "out", dtype, out, ldo, n_dst, (int64_t)C + (int64_t)H * up, st);
-  if (lse != nullptr) rt = trail::note(rt, who, "lse", ANEMOI_F32, lse, H, n_dst, H, st);
-  return rt;
+  FoldedLists l{};
+  l.run_ptr = run_ptr; l.run_perm = run_perm; l.n_runs = n_runs;
+  return folded_edge_phase(dtype, {q, k, v, x_r, u, edge_attr, rowptr, col, out, lse, ldq, ldkv, ldr, ldu, ldo, n_dst, C, H, up},
+                           l, as_stream(stream));
 }

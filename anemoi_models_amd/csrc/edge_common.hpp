@@ -6,6 +6,37 @@
 
 namespace anemoi {
 
+// The folded edge phase as its host side sees it (edge_attention.hip::folded_edge_phase): what every entry point of the
+// anemoi_gt_edge_attention_folded family and the block-level entry points (blocks.hip) hand over.
+struct FoldedOperands {
+  const void *q, *k, *v, *x_r, *u;
+  const float* edge_attr;
+  const int32_t *rowptr, *col;
+  void* out;
+  float* lse;
+  int64_t ldq, ldkv, ldr, ldu, ldo;
+  int64_t n_dst;
+  int C, H, up;
+};
+
+// The optional host-built lists; all zero: the plain kernel.  Field for field the list part of anemoi_gt_block_args
+// (run_ptr / run_perm / n_runs are the group lists when run_dst is set).
+struct FoldedLists {
+  const int32_t *run_ptr, *run_perm, *run_dst;
+  int64_t n_runs;
+  const int32_t* sched;
+  int sched_slots, sched_steps;
+  const int32_t *tile_hdr, *tile_dst, *tile_src;
+  const uint8_t* tile_slot;
+  const int32_t* tile_xcd;
+  int tile_max_per_xcd, tile_src_cap, tile_edge_cap;
+  int64_t n_src, n_edges;
+};
+
+// Checks the arguments, picks the kernel (groups, runs, tiles, schedule, plain -- the first whose list is given; a list
+// kernel that does not cover the shape hands over to the plain one) and launches it.
+int folded_edge_phase(int dtype, const FoldedOperands& o, const FoldedLists& l, hipStream_t st);
+
 template <typename T, int VEC>
 struct RawVec;
 template <>

@@ -53,46 +53,9 @@ def folded_edge_phase(q: Tensor, k: Tensor, v: Tensor, x_r: Optional[Tensor], u:
                       num_heads: int, up: int, ld_out: Optional[int] = None) -> Tensor:
     """The folded edge phase (``anemoi_gt_edge_attention_folded``: one fused gather -> score -> segment softmax -> weighted
     sum -> ``+ x_r`` pass over the destination-sorted CSR)."""
-    runs = edge_runs(plan, q.dtype)
-    tiles = None if runs is not None else edge_tiles(plan, q, num_heads, up)
-    return ops.gt_edge_attention_folded(q, k, v, x_r, u, edge_attr_csr, plan.rowptr, plan.col, num_heads, up,
-                                        ld_out=ld_out, runs=runs, tiles=tiles,
-                                        sched=None if runs is not None or tiles is not None else edge_schedule(plan, q))
-
-
-TILES_DEFAULT = "0"  # ANEMOI_AMD_EDGE_TILES: the LDS-tile edge kernel for mesh graphs (A/B switch; DESIGN 4.2 for the numbers)
-
-
-def edge_tiles(plan, q: Tensor, num_heads: int, up: int):
-    """The tile lists of a plan for the LDS-tile bf16 edge kernel (``EdgePlan.tiles``), else ``None``."""
-    if (q.dtype != torch.bfloat16 or not hasattr(plan, "tiles")
-            or os.environ.get("ANEMOI_AMD_EDGE_TILES", TILES_DEFAULT) == "0"):
-        return None
-    return plan.tiles(q.dtype, q.shape[-1], num_heads, up)
-
-
-def edge_schedule(plan, q: Tensor):
-    """The destination schedule of a plan for the scheduled bf16 edge kernel (``EdgePlan.schedule``), else ``None``
-    (``ANEMOI_AMD_EDGE_SCHED=0``: the round-robin kernel, A/B)."""
-    if q.dtype != torch.bfloat16 or not hasattr(plan, "schedule") or os.environ.get("ANEMOI_AMD_EDGE_SCHED", "1") == "0":
-        return None
-    return plan.schedule(q.dtype, q.shape[-1])
-
-
-def set_tile_args(a, tiles, n_src: int, n_edges: int) -> None:
-    """The tile fields of an ``anemoi_gt_block_args`` block."""
-    a.tile_hdr, a.tile_dst, a.tile_src = tiles.hdr.data_ptr(), tiles.dst.data_ptr(), tiles.src.data_ptr()
-    a.tile_slot, a.tile_xcd = tiles.slot.data_ptr(), tiles.xcd.data_ptr()
-    a.tile_max_per_xcd, a.tile_src_cap, a.tile_edge_cap = tiles.max_tiles_per_xcd, tiles.src_cap, tiles.edge_cap
-    a.n_src, a.n_edges = n_src, n_edges
-
-
-def edge_runs(plan, dtype):
-    """The group (or run) lists of a uniform-degree-3 plan for the bf16 kernels that share source gathers between
-    destinations (``EdgePlan.runs3``), else ``None``."""
-    if dtype != torch.bfloat16 or not hasattr(plan, "runs3") or os.environ.get("ANEMOI_AMD_EDGE_RUNS", "1") == "0":
-        return None
-    return plan.runs3()
+    lists = runtime.edge_lists(plan, q.dtype, q.shape[-1], num_heads, up)
+    return ops.gt_edge_attention_folded(q, k, v, x_r, u, edge_attr_csr, plan.rowptr, plan.col, num_heads, up, ld_out=ld_out,
+                                        **lists._asdict())
 
 
 class EmbeddedRows:
@@ -414,19 +377,7 @@ class GraphTransformerBaseBlock(BaseBlock, ABC):
         a.q, a.k, a.v, a.x_r, a.u = q.data_ptr(), k.data_ptr(), v.data_ptr(), x_r.data_ptr(), u.data_ptr()
         a.ldq, a.ldkv, a.ldr, a.ldu = ops._ld(q), ops._ld(k), ops._ld(x_r), ops._ld(u)
         a.edge_attr, a.rowptr, a.col = edge_attr_csr.data_ptr(), plan.rowptr.data_ptr(), plan.col.data_ptr()
-        runs = edge_runs(plan, dtype)
-        if runs is not None:
-            a.run_ptr, a.run_perm, a.n_runs = runs[0].data_ptr(), runs[1].data_ptr(), runs[0].shape[0] - 1
-            if len(runs) == 3:  # groups: the destination list, and the row count of k / v for the 4-GiB check
-                a.run_dst, a.n_src = runs[2].data_ptr(), k.shape[0]
-        else:  # (beyond 32-bit attribute-row offsets the entry point takes the plain kernel by itself: n_edges states the size)
-            tiles = edge_tiles(plan, q, h, up)
-            if tiles is not None:
-                set_tile_args(a, tiles, k.shape[0], edge_attr_csr.shape[0])
-            sched = None if tiles is not None else edge_schedule(plan, q)
-            if sched is not None:
-                a.sched, a.sched_slots, a.sched_steps, a.n_src = sched.data_ptr(), sched.shape[1], sched.shape[2], k.shape[0]
-                a.n_edges = edge_attr_csr.shape[0]
+        runtime.set_edge_list_args(a, runtime.edge_lists(plan, dtype, c, h, up), k.shape[0], edge_attr_csr.shape[0])
         a.att, a.ld_att = att.data_ptr(), wp.shape[1]
         a.w_proj, a.b_proj = wp.data_ptr(), ops._ptr(bp)
         a.res, a.ld_res, a.y, a.y_stats = res.data_ptr(), ops._ld(res), y.data_ptr(), stats[0].data_ptr()
@@ -440,6 +391,19 @@ class GraphTransformerBaseBlock(BaseBlock, ABC):
         return out
 
     block_abi = True  # False: op by op (tests compare the two routes)
+
+    def _folded_tail(self, q: Tensor, k: Tensor, v: Tensor, x_r: Tensor, u: Tensor, edge_attr_csr: Tensor, plan, res: Tensor,
+                     up: int, out_stats_eps: Optional[float]) -> Tensor:
+        """What follows the folded input products on every route: ``_block_tail``, or the same launches op by op."""
+        done = self._block_tail(q, k, v, x_r, u, edge_attr_csr, plan, res, up, out_stats_eps)
+        if done is not None:
+            return done
+        wp, bp = self._folded_out(q.dtype, up)
+        att = folded_edge_phase(q, k, v, x_r, u, edge_attr_csr, plan, self.num_heads, up, ld_out=wp.shape[1])
+        # projection(out + x_r) + res, lin_edge part via W_t; the statistics of the MLP's LayerNorm ride on the epilogue,
+        # those of the LayerNorm that reads the new nodes next on the MLP's last Linear
+        y = runtime.linear(att, wp, bp, residual=res, stats_eps=self._mlp_ln_eps("dst", q.dtype))
+        return self._node_mlp(y, "dst", 1, out_stats_eps=out_stats_eps)
 
     def _node_mlp(self, y: Tensor, which: str, num_chunks: int, out_stats_eps: Optional[float] = None) -> Tensor:
         """``mlp(y) + y`` with mlp = LayerNorm, Linear, act, Linear; optionally in row chunks (bounded hidden buffer)."""
@@ -531,35 +495,19 @@ class GraphTransformerProcessorBlock(GraphTransformerBaseBlock):
                             lambda: self._cat_rows(kv_layers), [l.weight for l in kv_layers] + [l.bias for l in kv_layers],
                             out=kv[:n_own])
             pending = halo.start(kv, n_own)  # xGMI transfer of the halo k|v rows ...
-            wpf, bp = self._folded_out(dtype, up)
             sq = self._ln_linear(xh, "squ", lambda: self._folded_in("squ", sq_layers, dtype, up),
                                  lambda: self._folded_rows(sq_layers, up),
                                  self._fold_params(sq_layers))  # ... overlapped with the x_r | q | u GEMM
             halo.finish(pending)
-            done = self._block_tail(sq[:, c:2 * c], kv[:, :c], kv[:, c:], sq[:, :c], sq[:, 2 * c:], edge_attr_csr, plan, x, up,
-                                    self._next_ln_eps(dtype))
-            if done is not None:
-                return done
-            att = folded_edge_phase(sq[:, c:2 * c], kv[:, :c], kv[:, c:], sq[:, :c], sq[:, 2 * c:], edge_attr_csr, plan,
-                                    self.num_heads, up, ld_out=wpf.shape[1])
-            y = runtime.linear(att, wpf, bp, residual=x, stats_eps=self._mlp_ln_eps("dst", dtype))
-            return self._node_mlp(y, "dst", 1, out_stats_eps=self._next_ln_eps(dtype))
+            return self._folded_tail(sq[:, c:2 * c], kv[:, :c], kv[:, c:], sq[:, :c], sq[:, 2 * c:], edge_attr_csr, plan, x, up,
+                                     self._next_ln_eps(dtype))
         all4 = [self.lin_self, self.lin_query, self.lin_key, self.lin_value]
         if up is not None:
-            wpf, bp = self._folded_out(dtype, up)
             sq = self._ln_linear(xh, "sqkvu", lambda: self._folded_in("sqkvu", all4, dtype, up),
                                  lambda: self._folded_rows(all4, up),
                                  self._fold_params(all4))  # [N, 4C + H*up] = x_r | q | k | v | u
-            done = self._block_tail(sq[:, c:2 * c], sq[:, 2 * c:3 * c], sq[:, 3 * c:4 * c], sq[:, :c], sq[:, 4 * c:],
-                                    edge_attr_csr, plan, x, up, self._next_ln_eps(dtype))
-            if done is not None:
-                return done
-            att = folded_edge_phase(sq[:, c:2 * c], sq[:, 2 * c:3 * c], sq[:, 3 * c:4 * c], sq[:, :c], sq[:, 4 * c:],
-                                    edge_attr_csr, plan, self.num_heads, up, ld_out=wpf.shape[1])
-            # projection(out + x_r) + x_skip, lin_edge part via W_t; the statistics of the MLP's LayerNorm ride on the
-            # epilogue, those of the next block's layer_norm1 on the MLP's last Linear
-            y = runtime.linear(att, wpf, bp, residual=x, stats_eps=self._mlp_ln_eps("dst", dtype))
-            return self._node_mlp(y, "dst", 1, out_stats_eps=self._next_ln_eps(dtype))
+            return self._folded_tail(sq[:, c:2 * c], sq[:, 2 * c:3 * c], sq[:, 3 * c:4 * c], sq[:, :c], sq[:, 4 * c:],
+                                     edge_attr_csr, plan, x, up, self._next_ln_eps(dtype))
         wp, bp = self._cat_linear("proj", [self.projection], dtype)
         we, be = self._edge_params()
         sqkv = self._ln_linear(xh, "sqkv", lambda: self._cat_linear("sqkv", all4, dtype), lambda: self._cat_rows(all4),
@@ -714,10 +662,9 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
             if halo is not None:
                 halo.finish(pending)
             if num_chunks <= 1 and not self.update_src_nodes and not mx:
-                done = self._block_tail(sq[:, c:2 * c], kv[:, :c], kv[:, c:], sq[:, :c], sq[:, 2 * c:], edge_attr_csr, plan,
-                                        h_dst, up, out_stats_eps)
-                if done is not None:
-                    return (x_src.h if isinstance(x_src, EmbeddedRows) else x_src), done
+                new_dst = self._folded_tail(sq[:, c:2 * c], kv[:, :c], kv[:, c:], sq[:, :c], sq[:, 2 * c:], edge_attr_csr, plan,
+                                            h_dst, up, out_stats_eps)
+                return (x_src.h if isinstance(x_src, EmbeddedRows) else x_src), new_dst
             att = folded_edge_phase(sq[:, c:2 * c], kv[:, :c], kv[:, c:], sq[:, :c], sq[:, 2 * c:], edge_attr_csr, plan,
                                     self.num_heads, up, ld_out=wp.shape[1])
         else:

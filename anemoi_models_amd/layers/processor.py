@@ -223,11 +223,8 @@ class _BlockAbiPlan:
         if x.shape[1] != c or any(o["w_in"].shape != operands[0]["w_in"].shape or o["w_fc1"].shape[0] != hidden
                                   or o["act"] not in _lib.ACT_CODES for o in operands):
             return self
-        from .block import edge_schedule, edge_tiles, set_tile_args
-
-        tiles = edge_tiles(plan, x, h, up)
-        sched = None if tiles is not None else edge_schedule(plan, x)  # (n_edges below: the entry point declines it beyond 32-bit attribute-row offsets)
-        self.keep = [operands, ea, plan, sched, tiles]  # the packed weights, edge attributes, CSR and schedule the templates point at
+        lists = runtime.edge_lists(plan, dtype, c, h, up)  # (the op-by-op route's choice: block.folded_edge_phase)
+        self.keep = [operands, ea, plan, lists.sched, lists.tiles, lists.runs]  # what the templates point at: packed weights, ...
         self.dims = (n, c, h, up, n_in, k_proj, hidden)
         lib = _lib.load()
         self.ws_bytes = n * max(c // 128, 1) * 8  # row-sum partials of anemoi_linear_stats
@@ -246,11 +243,7 @@ class _BlockAbiPlan:
             a.b_in = None if o["b_in"] is None else o["b_in"].data_ptr()
             a.ld_sq = n_in
             a.edge_attr, a.rowptr, a.col = ea.data_ptr(), plan.rowptr.data_ptr(), plan.col.data_ptr()
-            if tiles is not None:
-                set_tile_args(a, tiles, plan.n_src, ea.shape[0])
-            if sched is not None:
-                a.sched, a.sched_slots, a.sched_steps, a.n_src = sched.data_ptr(), sched.shape[1], sched.shape[2], plan.n_src
-                a.n_edges = ea.shape[0]
+            runtime.set_edge_list_args(a, lists, plan.n_src, ea.shape[0])
             a.ld_att = k_proj
             a.w_proj = o["w_proj"].data_ptr()
             a.b_proj = None if o["b_proj"] is None else o["b_proj"].data_ptr()
@@ -351,7 +344,7 @@ class GraphTransformerProcessor(GraphEdgeMixin, BaseProcessor):
             params = self.__dict__["_abi_params"] = [p for p in self.parameters()]
         # any in-place change of a parameter (optimiser step, load_state_dict, .normal_()) bumps its version counter
         sig = (sum(p._version for p in params), params[0].data_ptr(), x.shape[0], str(x.device), ea.data_ptr(), id(plan),
-               os.environ.get("ANEMOI_AMD_EDGE_TILES"), os.environ.get("ANEMOI_AMD_EDGE_SCHED"),  # (A/B switches of the edge
+               runtime.edge_list_switches(),  # (A/B switches of the edge
                os.environ.get("ANEMOI_AMD_LN_FOLD"))  # kernel; the fold the plan's operands are built for: a model that ran
         # with the fold and is then asked without it kept the folded blocks between unfolded mappers until round 6)
         fast = self.__dict__.get("_abi_plan")

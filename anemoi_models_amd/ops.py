@@ -479,6 +479,12 @@ def gt_edge_attention_folded(q: Tensor, k: Tensor, v: Tensor, x_r: Optional[Tens
     #  not count: reported beside the roofline fraction, never instead of it)
     fused_bytes = alg_bytes + n_dst * ((0 if x_r is None else c) + 2 * num_heads * up) * q.element_size()
     with _Timed("gt_edge_attention", bytes=alg_bytes, fused_bytes=fused_bytes, n_dst=n_dst, n_src=k.shape[0], edges=col.shape[0]):
+        lib = _lib.load()
+        head = (dtype_code(q.dtype), q.data_ptr(), _ld(q), k.data_ptr(), v.data_ptr(), _ld(_rows(k)), _ptr(x_r),
+                0 if x_r is None else _ld(_rows(x_r)), u.data_ptr(), _ld(_rows(u)), edge_attr.data_ptr(), up,
+                rowptr.data_ptr(), col.data_ptr())
+        tail = (out.data_ptr(), _ld(_rows(out)), _ptr(lse), n_dst, c, num_heads, _stream())
+        n_src, n_edges = _rows(k).shape[0], col.shape[0]
         if runs is not None and len(runs) == 3:  # groups of destinations that share their three sources
             grp_ptr, grp_perm, grp_dst = runs
             _dev(grp_ptr, grp_perm, grp_dst)
@@ -486,44 +492,27 @@ def gt_edge_attention_folded(q: Tensor, k: Tensor, v: Tensor, x_r: Optional[Tens
                     or grp_perm.shape[0] != n_dst or grp_dst.shape[0] != n_dst):
                 raise ValueError("gt_edge_attention_folded: runs = (int32 grp_ptr [n_groups + 1], int32 grp_perm [n_dst], "
                                  "int32 grp_dst [n_dst])")
-            st = _lib.load().anemoi_gt_edge_attention_folded_groups(
-                dtype_code(q.dtype), q.data_ptr(), _ld(q), k.data_ptr(), v.data_ptr(), _ld(_rows(k)), _ptr(x_r),
-                0 if x_r is None else _ld(_rows(x_r)), u.data_ptr(), _ld(_rows(u)), edge_attr.data_ptr(), up,
-                rowptr.data_ptr(), col.data_ptr(), grp_ptr.data_ptr(), grp_dst.data_ptr(), grp_perm.data_ptr(),
-                grp_ptr.shape[0] - 1, _rows(k).shape[0], out.data_ptr(), _ld(_rows(out)), _ptr(lse), n_dst, c, num_heads,
-                _stream())
+            st = lib.anemoi_gt_edge_attention_folded_groups(*head, grp_ptr.data_ptr(), grp_dst.data_ptr(), grp_perm.data_ptr(),
+                                                            grp_ptr.shape[0] - 1, n_src, *tail)
         elif runs is not None:
             run_ptr, perm = runs
             _dev(run_ptr, perm)
             if run_ptr.dtype != torch.int32 or perm.dtype != torch.int32 or perm.shape[0] != run_ptr.shape[0] - 1:
                 raise ValueError("gt_edge_attention_folded: runs = (int32 run_ptr [n_runs + 1], int32 perm [n_runs])")
-            st = _lib.load().anemoi_gt_edge_attention_folded_runs(
-                dtype_code(q.dtype), q.data_ptr(), _ld(q), k.data_ptr(), v.data_ptr(), _ld(_rows(k)), _ptr(x_r),
-                0 if x_r is None else _ld(_rows(x_r)), u.data_ptr(), _ld(_rows(u)), edge_attr.data_ptr(), up,
-                rowptr.data_ptr(), col.data_ptr(), run_ptr.data_ptr(), perm.data_ptr(), run_ptr.shape[0] - 1,
-                out.data_ptr(), _ld(_rows(out)), _ptr(lse), n_dst, c, num_heads, _stream())
+            st = lib.anemoi_gt_edge_attention_folded_runs(*head, run_ptr.data_ptr(), perm.data_ptr(), run_ptr.shape[0] - 1, *tail)
         elif tiles is not None:
             _dev(tiles.hdr, tiles.dst, tiles.src, tiles.slot, tiles.xcd)
-            st = _lib.load().anemoi_gt_edge_attention_folded_tiles(
-                dtype_code(q.dtype), q.data_ptr(), _ld(q), k.data_ptr(), v.data_ptr(), _ld(_rows(k)), _ptr(x_r),
-                0 if x_r is None else _ld(_rows(x_r)), u.data_ptr(), _ld(_rows(u)), edge_attr.data_ptr(), up,
-                rowptr.data_ptr(), col.data_ptr(), tiles.hdr.data_ptr(), tiles.dst.data_ptr(), tiles.src.data_ptr(),
-                tiles.slot.data_ptr(), tiles.xcd.data_ptr(), tiles.max_tiles_per_xcd, tiles.src_cap, tiles.edge_cap,
-                _rows(k).shape[0], col.shape[0], out.data_ptr(), _ld(_rows(out)), _ptr(lse), n_dst, c, num_heads, _stream())
+            st = lib.anemoi_gt_edge_attention_folded_tiles(
+                *head, tiles.hdr.data_ptr(), tiles.dst.data_ptr(), tiles.src.data_ptr(), tiles.slot.data_ptr(),
+                tiles.xcd.data_ptr(), tiles.max_tiles_per_xcd, tiles.src_cap, tiles.edge_cap, n_src, n_edges, *tail)
         elif sched is not None:  # (the entry point itself falls back to the plain kernel beyond 32-bit row offsets)
             _dev(sched)
             if sched.dtype != torch.int32 or sched.dim() != 3 or sched.shape[0] != 8 or not sched.is_contiguous():
                 raise ValueError("gt_edge_attention_folded: sched = contiguous int32 [8, slots, steps]")
-            st = _lib.load().anemoi_gt_edge_attention_folded_sched(
-                dtype_code(q.dtype), q.data_ptr(), _ld(q), k.data_ptr(), v.data_ptr(), _ld(_rows(k)), _ptr(x_r),
-                0 if x_r is None else _ld(_rows(x_r)), u.data_ptr(), _ld(_rows(u)), edge_attr.data_ptr(), up,
-                rowptr.data_ptr(), col.data_ptr(), sched.data_ptr(), sched.shape[1], sched.shape[2], _rows(k).shape[0],
-                col.shape[0], out.data_ptr(), _ld(_rows(out)), _ptr(lse), n_dst, c, num_heads, _stream())
+            st = lib.anemoi_gt_edge_attention_folded_sched(*head, sched.data_ptr(), sched.shape[1], sched.shape[2], n_src,
+                                                           n_edges, *tail)
         else:
-            st = _lib.load().anemoi_gt_edge_attention_folded(
-                dtype_code(q.dtype), q.data_ptr(), _ld(q), k.data_ptr(), v.data_ptr(), _ld(_rows(k)), _ptr(x_r),
-                0 if x_r is None else _ld(_rows(x_r)), u.data_ptr(), _ld(_rows(u)), edge_attr.data_ptr(), up,
-                rowptr.data_ptr(), col.data_ptr(), out.data_ptr(), _ld(_rows(out)), _ptr(lse), n_dst, c, num_heads, _stream())
+            st = lib.anemoi_gt_edge_attention_folded(*head, *tail)
     _lib.check(st, "anemoi_gt_edge_attention_folded")
     return out
 

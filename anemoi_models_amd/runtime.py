@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass
-from typing import Callable, Optional, Sequence
+from typing import Callable, NamedTuple, Optional, Sequence
 
 import torch
 from torch import Tensor
@@ -232,15 +232,16 @@ class EdgeTiles:
 def edge_tile_lists(rowptr: Tensor, col: Tensor, src_cap: int = TILE_SRC_CAP, edge_cap: int = TILE_EDGE_CAP,
                     max_dst: int = TILE_MAX_DST):
     """The tile lists of :class:`EdgeTiles` for a destination-sorted CSR (host logic, CPU tensors), or ``None`` when one
-    destination alone exceeds a cap (in-degree > ``edge_cap`` / 255, more than ``src_cap`` distinct sources)."""
+    destination alone exceeds a cap (in-degree > ``edge_cap`` / 255, more than ``src_cap`` distinct sources) or the caps are
+    not the kernel's (``src_cap`` a multiple of 4 up to 255, ``edge_cap`` a multiple of 16)."""
     import numpy as np
 
     rp = rowptr.cpu().numpy().astype(np.int64)
     cl = col.cpu().numpy().astype(np.int64)
     n = rp.shape[0] - 1
     deg = rp[1:] - rp[:-1]
-    if (n == 0 or not 0 < src_cap <= 255 or edge_cap % 16 != 0 or max_dst > TILE_MAX_DST
-            or deg.max(initial=0) > min(edge_cap, 255)):
+    if (n == 0 or not 0 < src_cap <= 255 or src_cap % 4 != 0 or edge_cap % 16 != 0 or max_dst > TILE_MAX_DST
+            or deg.max(initial=0) > min(edge_cap, 255)):  # (the kernel stages sources in pieces of four)
         return None
     hdr, dst, srcs, slots, xcd = [], [], [], [], [0]
     src_off = slot_off = 0
@@ -293,6 +294,61 @@ def _edge_tiles(plan: "EdgePlan", channels: int, heads: int, up: int):
     edge_cap = int(os.environ.get("ANEMOI_AMD_EDGE_TILE_EDGES", TILE_EDGE_CAP))
     t = edge_tile_lists(plan.rowptr, plan.col, src_cap, edge_cap)
     return None if t is None else t.to(plan.col.device)
+
+
+# ---- which lists a folded edge phase runs with: the ONE place that decides (the C side: edge_attention.hip::folded_edge_phase)
+TILES_DEFAULT = "0"  # ANEMOI_AMD_EDGE_TILES: the LDS-tile edge kernel for mesh graphs (A/B switch; DESIGN 4.2 for the numbers)
+
+
+class EdgeLists(NamedTuple):
+    """The optional host-built lists of one folded edge phase; at most one is set, all ``None``: the plain kernel."""
+
+    runs: Optional[tuple] = None  # EdgePlan.runs3(): (grp_ptr, grp_perm, grp_dst) or (run_ptr, perm)
+    tiles: Optional[EdgeTiles] = None  # EdgePlan.tiles()
+    sched: Optional[Tensor] = None  # EdgePlan.schedule()
+
+
+def edge_list_switches() -> tuple:
+    """(runs, tiles, sched): the A/B switches ``ANEMOI_AMD_EDGE_RUNS`` / ``_TILES`` / ``_SCHED`` ("0": off), read at call time."""
+    return (os.environ.get("ANEMOI_AMD_EDGE_RUNS", "1") != "0", os.environ.get("ANEMOI_AMD_EDGE_TILES", TILES_DEFAULT) != "0",
+            os.environ.get("ANEMOI_AMD_EDGE_SCHED", "1") != "0")
+
+
+def edge_lists(plan, dtype: torch.dtype, channels: int, heads: int, up: int, *, training: bool = False) -> EdgeLists:
+    """The lists of ``plan`` for a folded edge phase of ``channels`` / ``heads`` / ``up`` in ``dtype``: bf16 only, runs (or
+    groups: uniform-degree-3 graphs) win over tiles win over the schedule.  ``training``: no tiles (the tile kernel is an
+    inference route)."""
+    if dtype != torch.bfloat16:
+        return EdgeLists()
+    want_runs, want_tiles, want_sched = edge_list_switches()
+    if want_runs and hasattr(plan, "runs3"):
+        runs = plan.runs3()
+        if runs is not None:
+            return EdgeLists(runs=runs)
+    if want_tiles and not training and hasattr(plan, "tiles"):
+        tiles = plan.tiles(dtype, channels, heads, up)
+        if tiles is not None:
+            return EdgeLists(tiles=tiles)
+    if want_sched and hasattr(plan, "schedule"):
+        return EdgeLists(sched=plan.schedule(dtype, channels))
+    return EdgeLists()
+
+
+def set_edge_list_args(a, lists: EdgeLists, n_src: int, n_edges: int) -> None:
+    """The list fields of an ``anemoi_gt_block_args`` block (``n_src`` / ``n_edges``: the row counts of k | v and of the
+    attribute matrix, by which the entry point declines a list kernel beyond its 32-bit offsets)."""
+    runs, tiles, sched = lists
+    a.n_src, a.n_edges = n_src, n_edges
+    if runs is not None:
+        a.run_ptr, a.run_perm, a.n_runs = runs[0].data_ptr(), runs[1].data_ptr(), runs[0].shape[0] - 1
+        if len(runs) == 3:  # groups: the destination list
+            a.run_dst = runs[2].data_ptr()
+    if tiles is not None:
+        a.tile_hdr, a.tile_dst, a.tile_src = tiles.hdr.data_ptr(), tiles.dst.data_ptr(), tiles.src.data_ptr()
+        a.tile_slot, a.tile_xcd = tiles.slot.data_ptr(), tiles.xcd.data_ptr()
+        a.tile_max_per_xcd, a.tile_src_cap, a.tile_edge_cap = tiles.max_tiles_per_xcd, tiles.src_cap, tiles.edge_cap
+    if sched is not None:
+        a.sched, a.sched_slots, a.sched_steps = sched.data_ptr(), sched.shape[1], sched.shape[2]
 
 
 def _runs3(plan: "EdgePlan", max_run: int = 2):

@@ -709,6 +709,112 @@ def test_model_on_the_tile_edge_kernel_is_the_default_route_bit_for_bit(monkeypa
     assert fast is not None and fast.ok and fast.keep[4] is not None and fast.keep[4].n_tiles > 100
 
 
+EDGE_ROUTES = {  # route -> (entry point whose kernel runs, switches)
+    "groups": ("anemoi_gt_edge_attention_folded_groups", {}),
+    "runs": ("anemoi_gt_edge_attention_folded_runs", {"ANEMOI_AMD_EDGE_GROUPS": "0"}),
+    "sched": ("anemoi_gt_edge_attention_folded_sched", {}),
+    "tiles": ("anemoi_gt_edge_attention_folded_tiles", {"ANEMOI_AMD_EDGE_TILES": "1"}),
+    "plain": ("anemoi_gt_edge_attention_folded", {"ANEMOI_AMD_EDGE_RUNS": "0", "ANEMOI_AMD_EDGE_TILES": "0",
+                                                  "ANEMOI_AMD_EDGE_SCHED": "0"}),
+}
+
+
+@pytest.mark.parametrize("channels,heads,edge_dim", [(128, 4, 3), (1024, 16, 7)])  # D = 32, one slice, up = 4; D = 64, two, up = 8
+@pytest.mark.parametrize("route", list(EDGE_ROUTES))
+def test_block_abi_and_op_by_op_take_the_same_edge_kernel(route, channels, heads, edge_dim, monkeypatch):
+    """One route choice (``runtime.edge_lists`` / ``folded_edge_phase`` in edge_attention.hip): a bf16 block forward through the
+    block-level entry point and op by op leaves, under an armed launch trail, ONE edge-phase record each -- of the entry point
+    whose kernel the route names, with the same digest.  Groups and runs: a mapper block on the three nearest mesh nodes of
+    1043 grid points (the list builders take graphs from 1024 destinations on); schedule, tiles and the plain kernel: a
+    processor block on a thinned multi-scale ico-3 mesh (642 nodes, in-degrees 1 .. 15, 4 on average).  Neither count is a multiple of
+    8: the XCD ranges and the last tile are ragged."""
+    from anemoi_models_amd import runtime, trail
+    from anemoi_models_amd.graphs import synthetic
+    from anemoi_models_amd.layers.block import GraphTransformerBaseBlock, GraphTransformerMapperBlock, GraphTransformerProcessorBlock
+
+    entry, switches = EDGE_ROUTES[route]
+    monkeypatch.setenv("ANEMOI_AMD_DTYPE", "bf16")
+    for name in ("ANEMOI_AMD_EDGE_RUNS", "ANEMOI_AMD_EDGE_TILES", "ANEMOI_AMD_EDGE_SCHED", "ANEMOI_AMD_EDGE_GROUPS"):
+        monkeypatch.delenv(name, raising=False)
+    for name, value in switches.items():
+        monkeypatch.setenv(name, value)
+    g = torch.Generator().manual_seed(channels + len(route))
+    torch.manual_seed(3)
+    mapper = route in ("groups", "runs")
+    if mapper:
+        mesh_xyz, _ = synthetic.icosphere(1)
+        grid_xyz = synthetic._to_xyz(synthetic.octahedral_grid(16))[:1043]
+        ei = torch.from_numpy(synthetic._knn_edges(grid_xyz, mesh_xyz, 3))
+        n_src, n_dst = mesh_xyz.shape[0], grid_xyz.shape[0]
+        blk = GraphTransformerMapperBlock(channels, 2 * channels, channels, edge_dim=edge_dim, num_heads=heads)
+        x = (torch.randn(n_src, channels, generator=g).to(DEV), torch.randn(n_dst, channels, generator=g).to(DEV))
+    else:
+        mesh_xyz, levels = synthetic.icosphere(3)
+        ei = torch.from_numpy(synthetic.multiscale_mesh_edges(levels))
+        order = torch.argsort(ei[1], stable=True)
+        ei = ei[:, order]
+        first = torch.ones(ei.shape[1], dtype=torch.bool)
+        first[1:] = ei[1, 1:] != ei[1, :-1]
+        ei = ei[:, first | (torch.rand(ei.shape[1], generator=g) < 0.45)]  # every node keeps an in-edge
+        n_src = n_dst = mesh_xyz.shape[0]
+        blk = GraphTransformerProcessorBlock(channels, 2 * channels, channels, edge_dim=edge_dim, num_heads=heads)
+        x = torch.randn(n_dst, channels, generator=g).to(DEV)
+    assert n_dst % 8 != 0 and n_dst >= 600
+    deg = torch.bincount(ei[1], minlength=n_dst)
+    assert (int(deg.min()), int(deg.max())) == (3, 3) if mapper else (int(deg.min()) == 1 and 8 <= int(deg.max()) <= 16)
+    blk = blk.to(DEV).eval()
+    ea = torch.randn(ei.shape[1], edge_dim, generator=g).to(DEV)
+    ei = ei.to(DEV)
+    lists = runtime.edge_lists(blk._plans.get(ei, n_src, n_dst), torch.bfloat16, channels, heads, blk.fold_width(torch.bfloat16))
+    want_lists = {"groups": "runs", "runs": "runs", "sched": "sched", "tiles": "tiles", "plain": None}[route]
+    assert [k for k, v in lists._asdict().items() if v is not None] == ([want_lists] if want_lists else [])
+    assert route not in ("groups", "runs") or len(lists.runs) == (3 if route == "groups" else 2)
+
+    def forward(block_abi: bool):
+        monkeypatch.setattr(GraphTransformerBaseBlock, "block_abi", block_abi)
+        with torch.no_grad(), trail.record() as t:
+            y, _ = blk(x, ea, ei, None, 1, size=(n_src, n_dst))
+        y = y[1] if mapper else y
+        edge = [e for e in t.entries if e.name.startswith("anemoi_gt_edge_attention")]
+        assert [e.name for e in edge] == [entry + ":out"], t.names()
+        assert (edge[0].rows, edge[0].cols, edge[0].nonfinite) == (n_dst, channels + heads * (edge_dim + 1), 0)
+        return y, edge[0]
+
+    y_abi, edge_abi = forward(True)
+    y_ops, edge_ops = forward(False)
+    assert edge_abi.same_as(edge_ops._replace(index=edge_abi.index)) and edge_abi.digest == edge_ops.digest
+    assert torch.equal(y_abi, y_ops)
+
+
+def test_tile_entry_point_refuses_a_source_cap_off_a_multiple_of_four():
+    """The tile kernel stages sources in pieces of four: with ``src_cap = 70`` the last piece of the k region would run over
+    into v's.  ``anemoi_gt_edge_attention_folded_tiles`` returns ANEMOI_ERR_INVALID (``ValueError``) and launches nothing."""
+    import dataclasses
+
+    from anemoi_models_amd import ops, runtime
+
+    g = torch.Generator().manual_seed(7)
+    n, c, h, up = 200, 128, 4, 4
+    deg = torch.randint(1, 9, (n,), generator=g)
+    dst = torch.repeat_interleave(torch.arange(n), deg)
+    src = (dst + torch.randint(-6, 7, dst.shape, generator=g)).clamp_(0, n - 1)
+    plan = runtime.build_edge_plan(torch.stack([src, dst]).to(DEV), n, n)
+    tiles = plan.tiles(torch.bfloat16, c, h, up)
+    assert tiles is not None and tiles.src_cap == 72
+    sq = (torch.randn(n, 4 * c + h * up, generator=g) * 0.5).bfloat16().to(DEV)
+    attr = torch.randn(plan.num_edges, up, generator=g).to(DEV)
+
+    def run(t):
+        out = torch.full((n, c + h * up), 7.0, dtype=torch.bfloat16, device=DEV)
+        ops.gt_edge_attention_folded(sq[:, c:2 * c], sq[:, 2 * c:3 * c], sq[:, 3 * c:4 * c], sq[:, :c], sq[:, 4 * c:], attr,
+                                     plan.rowptr, plan.col, h, up, out=out, tiles=t)
+        return out
+
+    with pytest.raises(ValueError, match="anemoi_gt_edge_attention_folded_tiles: tile caps 70 sources"):
+        run(dataclasses.replace(tiles, src_cap=70))
+    assert torch.equal(run(tiles), run(None))  # the cap of 72 runs, and is the plain kernel bit for bit
+
+
 def test_edge_plan_on_device_is_bit_exact_with_cpu():
     from anemoi_models_amd import runtime
 

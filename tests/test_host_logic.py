@@ -738,6 +738,63 @@ def test_edge_tile_lists_cover_every_destination_once_within_their_caps():
     assert runtime.edge_tile_lists(plan.rowptr, plan.col, src_cap=48, edge_cap=32) is None   # ... alone beyond either cap
 
 
+def test_edge_lists_is_the_one_route_choice(monkeypatch):
+    """``runtime.edge_lists`` (the one place that decides which lists a folded edge phase runs with), the full table: runs beat
+    tiles beat the schedule; a training forward never takes tiles; each of ``ANEMOI_AMD_EDGE_RUNS`` / ``_TILES`` / ``_SCHED``
+    at "0" removes exactly its list; tiles are off unless ``ANEMOI_AMD_EDGE_TILES`` is set; f32 takes no list.  And the tile
+    kernel stages sources in pieces of four: ``edge_tile_lists`` builds no lists for a source cap off a multiple of 4."""
+    import itertools
+
+    class Plan:
+        def __init__(self, has_runs):
+            self.has_runs = has_runs
+
+        def runs3(self):
+            return "RUNS" if self.has_runs else None
+
+        def tiles(self, dtype, channels, heads, up):
+            return ("TILES", dtype, channels, heads, up)
+
+        def schedule(self, dtype, channels):
+            return ("SCHED", dtype, channels)
+
+    bf16, c, h, up = torch.bfloat16, 256, 4, 8
+    tiles_of, sched_of = ("TILES", bf16, c, h, up), ("SCHED", bf16, c)
+    switches = ("ANEMOI_AMD_EDGE_RUNS", "ANEMOI_AMD_EDGE_TILES", "ANEMOI_AMD_EDGE_SCHED")
+    for env in itertools.product((None, "0", "1"), repeat=3):
+        for name, value in zip(switches, env):
+            if value is None:
+                monkeypatch.delenv(name, raising=False)
+            else:
+                monkeypatch.setenv(name, value)
+        runs_on, tiles_on, sched_on = env[0] != "0", env[1] == "1", env[2] != "0"  # (tiles: off by default)
+        for has_runs, training in itertools.product((True, False), repeat=2):
+            got = runtime.edge_lists(Plan(has_runs), bf16, c, h, up, training=training)
+            if runs_on and has_runs:
+                want = runtime.EdgeLists("RUNS", None, None)
+            elif tiles_on and not training:
+                want = runtime.EdgeLists(None, tiles_of, None)
+            elif sched_on:
+                want = runtime.EdgeLists(None, None, sched_of)
+            else:
+                want = runtime.EdgeLists(None, None, None)
+            assert got == want, (env, has_runs, training, got)
+            assert sum(x is not None for x in got) <= 1
+            assert runtime.edge_lists(Plan(has_runs), torch.float32, c, h, up, training=training) == (None, None, None)
+    assert runtime.EdgeLists._fields == ("runs", "tiles", "sched")
+    assert runtime.edge_lists(object(), bf16, c, h, up) == (None, None, None)  # a plan without lists (the CPU stand-ins)
+
+    g = torch.Generator().manual_seed(5)
+    n = 200
+    deg = torch.randint(0, 10, (n,), generator=g)
+    dst = torch.repeat_interleave(torch.arange(n), deg)
+    src = (dst + torch.randint(-6, 7, dst.shape, generator=g)).clamp_(0, n - 1)
+    plan = runtime.build_edge_plan(torch.stack([src, dst]), n, n)
+    assert runtime.edge_tile_lists(plan.rowptr, plan.col, src_cap=70) is None
+    t = runtime.edge_tile_lists(plan.rowptr, plan.col, src_cap=72)
+    assert t is not None and t.src_cap == 72 and int(t.hdr[:, 5].sum()) == n and int(t.hdr[:, 1].sum()) == plan.num_edges
+
+
 def test_grad_sink_hands_out_the_stacked_gradient_without_a_copy():
     """``autograd.GradSink`` / ``_Unstack`` (training route of a processor): when the gradient of block i's weight IS slot i of
     the sink, the gradient of the stacked weight is the sink's buffer itself (no ``torch.stack``); anything else -- a missing
