@@ -34,7 +34,7 @@ U8 = 3
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_RELU = 0, 1, 2, 3
 ACT_CODES = {"Identity": ACT_NONE, "GELU": ACT_GELU, "SiLU": ACT_SILU, "ReLU": ACT_RELU}
 
-ABI_VERSION = 46
+ABI_VERSION = 47
 
 
 class GtBlockArgs(ctypes.Structure):
@@ -172,6 +172,19 @@ SIGNATURES = {
                                            c_void_p, c_int, c_void_p]),
     "anemoi_advance_input": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_int, c_void_p, c_int,
                                      c_void_p, c_void_p]),
+    "anemoi_advance_state": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_int, c_void_p,
+                                     c_int, c_void_p, c_void_p]),
+    "anemoi_advance_state_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_int,
+                                              c_void_p, c_void_p, c_int, c_void_p]),
+    "anemoi_assemble_nodes_backward": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int64, c_int,
+                                               c_void_p]),
+    "anemoi_prognostic_residual_backward": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int,
+                                                    c_void_p, c_void_p]),
+    "anemoi_weighted_mse_workspace_floats": (c_int64, [c_int64, c_int]),
+    "anemoi_weighted_mse": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_float,
+                                    c_void_p, c_void_p, c_int64, c_void_p]),
+    "anemoi_weighted_mse_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p,
+                                             c_float, c_void_p, c_void_p, c_void_p]),
     "anemoi_transpose": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "anemoi_transpose_colsum_rows": (c_int64, [c_int64, c_int64]),
     "anemoi_transpose_chunked": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p,

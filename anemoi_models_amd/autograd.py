@@ -1291,3 +1291,73 @@ def model_forward(sd: dict, graph: dict, x: Tensor, *, num_heads: int, num_layer
     y = out.float().reshape(b, ens, g_, -1).clone()
     y[..., list(prognostic_out)] = y[..., list(prognostic_out)] + x[:, -1, :, :, list(prognostic_in)]
     return y
+
+
+# ------------------------------------------------------------------------------------------------ rollout training
+_INV_COLMAPS: dict = {}  # id(colmap) -> (colmap, its version, V_out, inverse map): the host builds an inverse once per map
+
+
+def _inverse_colmap(colmap: Tensor, v_out: int) -> Tensor:
+    hit = _INV_COLMAPS.get(id(colmap))
+    if hit is None or hit[0] is not colmap or hit[1] != colmap._version or hit[2] != v_out:
+        if len(_INV_COLMAPS) >= 64:
+            _INV_COLMAPS.clear()
+        hit = (colmap, colmap._version, v_out, ops.inverse_colmap(colmap, v_out))  # (holds colmap: its id stays its own)
+        _INV_COLMAPS[id(colmap)] = hit
+    return hit[3]
+
+
+class _AdvanceInput(torch.autograd.Function):
+    """The next model input of a rollout, out of place (``anemoi_advance_state``), with the gradients of the current input
+    and of the prediction from ONE pass (``anemoi_advance_state_backward``): pure copies, each gradient element written by
+    one thread -- where torch's ``roll`` + two index-puts would run its sort-based index accumulation."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, y: Tensor, colmap: Tensor, forcing: Optional[Tensor]):
+        ctx.colmap, ctx.v_out, ctx.has_forcing = colmap, y.shape[-1], forcing is not None
+        if any(ctx.needs_input_grad[:2]):  # refuse a map without an inverse in the forward, not in the middle of a backward
+            ctx.inv = _inverse_colmap(colmap, y.shape[-1])
+        return ops.advance_state(x, y, colmap, forcing)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dx_out: Tensor):
+        dx, dy = ops.advance_state_backward(dx_out.contiguous(), ctx.v_out, ctx.colmap, ctx.inv, ctx.has_forcing)
+        return (dx if ctx.needs_input_grad[0] else None), (dy if ctx.needs_input_grad[1] else None), None, None
+
+
+def advance_input(x: Tensor, y: Tensor, colmap: Tensor, forcing: Optional[Tensor] = None) -> Tensor:
+    """Differentiable, out-of-place ``ops.advance_input``: a new state ``[B, T, Ens, G, V_in]`` (f32) with the time axis
+    shifted by one and the last slice filled from the prediction ``y`` / the new ``forcing`` by ``colmap``; gradients for
+    ``x`` and ``y`` (``forcing`` is data).  A ``colmap`` that writes one output column into two input columns is refused."""
+    f = None if forcing is None else forcing.detach().float().contiguous()
+    return _AdvanceInput.apply(x.float().contiguous(), y.float().contiguous(), colmap, f)
+
+
+class _WeightedMSE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred: Tensor, target: Tensor, row_w: Tensor, col_w: Tensor, mask: Optional[Tensor], scale: float):
+        ctx.save_for_backward(pred, target, row_w, col_w, mask)
+        ctx.scale = scale
+        return ops.weighted_mse(pred, target, row_w, col_w, mask, scale)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g: Tensor):
+        pred, target, row_w, col_w, mask = ctx.saved_tensors
+        return ops.weighted_mse_backward(pred, target, row_w, col_w, mask, ctx.scale, g.float().contiguous()), None, None, \
+            None, None, None
+
+
+def weighted_mse(pred: Tensor, target: Tensor, row_w: Tensor, col_w: Tensor, mask: Optional[Tensor] = None,
+                 scale: float = 1.0) -> Tensor:
+    """``scale * sum_{..., g, v} keep * row_w[g] * col_w[v] * (pred - target)^2`` over ``pred`` ``[..., G, V]`` (any leading
+    axes: batch, ensemble, rollout steps) as an f32 scalar with a gradient for ``pred`` only.  ``mask`` ``[G, V]``: kept where
+    non-zero, by a select -- a masked element contributes exactly 0 to the loss and receives exactly 0 gradient even where
+    ``target`` or ``pred`` is NaN.  Deterministic: no atomics, the reduction order is a function of the shape alone."""
+    g, v = row_w.numel(), pred.shape[-1]
+    if pred.shape != target.shape or pred.dim() < 2 or pred.shape[-2] != g:
+        raise ValueError(f"weighted_mse: pred {tuple(pred.shape)} / target {tuple(target.shape)} do not end in [G = {g}, V]")
+    f32 = lambda t: None if t is None else t.detach().float().contiguous()  # noqa: E731
+    p2 = pred.float().contiguous().view(-1, v)
+    return _WeightedMSE.apply(p2, f32(target).view(-1, v), f32(row_w), f32(col_w), f32(mask), float(scale))

@@ -88,12 +88,9 @@ class AnemoiModelInterface(torch.nn.Module):
     def _advance_map(self, device) -> torch.Tensor:
         """int32 ``[V_in]`` column map of ``anemoi_advance_input``: prognostic inputs <- their output column, forcing
         inputs <- their position in the forcing tensor (-2 - k), everything else persists (-1)."""
-        idx = self.data_indices.internal_model
-        cmap = torch.full((len(idx.input),), -1, dtype=torch.int32)
-        cmap[idx.input.prognostic.long()] = idx.output.prognostic.to(torch.int32)
-        forcing = idx.input.forcing.long()
-        cmap[forcing] = -2 - torch.arange(forcing.numel(), dtype=torch.int32)
-        return cmap.to(device)
+        from ..utils.indices import advance_colmap
+
+        return advance_colmap(self.data_indices).to(device)
 
     def rollout(self, batch: torch.Tensor, n_steps: int, forcings: torch.Tensor = None, model_comm_group=None,
                 gather: str = "all"):

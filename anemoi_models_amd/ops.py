@@ -860,6 +860,151 @@ def advance_input(x: Tensor, y: Tensor, colmap: Tensor, forcing: Optional[Tensor
     return x
 
 
+# ------------------------------------------------------------------------------------------ rollout training
+def inverse_colmap(colmap: Tensor, v_out: int) -> Tensor:
+    """int32 ``[v_out]``: the input column ``v`` with ``colmap[v] == m``, or -1 -- what ``advance_state_backward`` reads.
+    Host work (one copy of the small map to the CPU): build it once per map.  A ``colmap`` whose non-negative entries
+    repeat (two input columns fed by one output column: their gradients would have to meet) is refused."""
+    cm = colmap.detach().to("cpu", torch.int64)
+    inv = torch.full((v_out,), -1, dtype=torch.int32)
+    for v, m in enumerate(cm.tolist()):
+        if m < 0:
+            continue
+        if m >= v_out:
+            raise ValueError(f"inverse_colmap: colmap[{v}] = {m} is not one of the {v_out} output columns")
+        if inv[m] >= 0:
+            raise ValueError(f"inverse_colmap: output column {m} feeds input columns {int(inv[m])} and {v}")
+        inv[m] = v
+    return inv.to(colmap.device)
+
+
+def _state_args(who: str, x: Tensor, y_shape, colmap: Tensor):
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() != 5:
+        raise ValueError(f"{who}: the state must be contiguous float32 [B, T, Ens, G, V_in]")
+    b, t, ens, g, v_in = x.shape
+    if tuple(y_shape[:3]) != (b, ens, g) or len(y_shape) != 4 or colmap.dtype != torch.int32 or colmap.numel() != v_in:
+        raise ValueError(f"{who}: y {tuple(y_shape)} / colmap do not match the state {tuple(x.shape)}")
+    return b, t, ens, g, v_in
+
+
+def advance_state(x: Tensor, y: Tensor, colmap: Tensor, forcing: Optional[Tensor] = None) -> Tensor:
+    """Out-of-place :func:`advance_input`: a NEW state with the bits ``advance_input`` would leave in a copy of ``x``
+    (include/anemoi_amd.h: anemoi_advance_state)."""
+    _dev(x, y, colmap, forcing)
+    b, t, ens, g, v_in = _state_args("advance_state", x, y.shape, colmap)
+    if y.dtype != torch.float32 or not y.is_contiguous():
+        raise ValueError("advance_state: y must be contiguous float32")
+    f = 0
+    if forcing is not None:
+        if forcing.dtype != torch.float32 or not forcing.is_contiguous() or tuple(forcing.shape[:3]) != (b, ens, g):
+            raise ValueError("advance_state: forcing must be contiguous float32 [B, Ens, G, F]")
+        f = forcing.shape[-1]
+    out = torch.empty_like(x)
+    st = _lib.load().anemoi_advance_state(x.data_ptr(), out.data_ptr(), b, t, ens, g, v_in, y.data_ptr(), y.shape[-1],
+                                          _ptr(forcing), f, colmap.data_ptr(), _stream())
+    _lib.check(st, "anemoi_advance_state")
+    return out
+
+
+def advance_state_backward(dx_out: Tensor, v_out: int, colmap: Tensor, inv_colmap: Tensor, has_forcing: bool):
+    """``(dx_in, dy)`` of :func:`advance_state` from the gradient of its result; ``inv_colmap`` = :func:`inverse_colmap`."""
+    _dev(dx_out, colmap, inv_colmap)
+    b, t, ens, g, v_in = _state_args("advance_state_backward", dx_out, (dx_out.shape[0], dx_out.shape[2], dx_out.shape[3], v_out),
+                                     colmap)
+    if inv_colmap.dtype != torch.int32 or inv_colmap.numel() != v_out:
+        raise ValueError("advance_state_backward: inv_colmap must be int32 with one entry per output column")
+    dx = torch.empty_like(dx_out)
+    dy = torch.empty((b, ens, g, v_out), dtype=torch.float32, device=dx_out.device)
+    st = _lib.load().anemoi_advance_state_backward(dx_out.data_ptr(), dx.data_ptr(), dy.data_ptr(), b, t, ens, g, v_in, v_out,
+                                                   colmap.data_ptr(), inv_colmap.data_ptr(), int(bool(has_forcing)), _stream())
+    _lib.check(st, "anemoi_advance_state_backward")
+    return dx, dy
+
+
+def assemble_nodes_backward(grad: Tensor, shape) -> Tensor:
+    """Input gradient of :func:`assemble_nodes`: ``dx`` f32 ``[B, T, Ens, G, V]`` (= ``shape``) from the leading ``T * V``
+    columns of ``grad``, the gradient of its ``[B * Ens * G, ld]`` result (f32 or bf16, any row pitch)."""
+    _dev(grad)
+    _rows(grad)
+    b, t, ens, g, v = (int(s) for s in shape)
+    if grad.shape[0] != b * ens * g or grad.shape[1] < t * v:
+        raise ValueError(f"assemble_nodes_backward: gradient {tuple(grad.shape)} does not belong to an input {tuple(shape)}")
+    dx = torch.empty((b, t, ens, g, v), dtype=torch.float32, device=grad.device)
+    if dx.numel() == 0:
+        return dx
+    st = _lib.load().anemoi_assemble_nodes_backward(dtype_code(grad.dtype), grad.data_ptr(), _ld(grad), dx.data_ptr(), b, t,
+                                                    ens, g, v, _stream())
+    _lib.check(st, "anemoi_assemble_nodes_backward")
+    return dx
+
+
+def prognostic_residual_backward(dy: Tensor, src: Tensor, shape) -> Tensor:
+    """Input gradient of the prognostic residual of :func:`finalize_output` (no affine maps): ``dx`` f32 ``[B, T, Ens, G,
+    V_in]`` (= ``shape``), zero except ``dx[:, -1, ..., src[c]] = dy[..., c]``."""
+    _dev(dy, src)
+    b, t, ens, g, v_in = (int(s) for s in shape)
+    if dy.dtype != torch.float32 or not dy.is_contiguous() or tuple(dy.shape[:3]) != (b, ens, g) or dy.dim() != 4:
+        raise ValueError(f"prognostic_residual_backward: dy must be contiguous float32 [B, Ens, G, V_out], got {tuple(dy.shape)}")
+    if src.dtype != torch.int32 or src.numel() != dy.shape[-1]:
+        raise ValueError("prognostic_residual_backward: src must be int32 with one entry per output column")
+    dx = torch.empty((b, t, ens, g, v_in), dtype=torch.float32, device=dy.device)
+    if dx.numel() == 0:
+        return dx
+    st = _lib.load().anemoi_prognostic_residual_backward(dy.data_ptr(), dy.shape[-1], dx.data_ptr(), b, t, ens, g, v_in,
+                                                         src.data_ptr(), _stream())
+    _lib.check(st, "anemoi_prognostic_residual_backward")
+    return dx
+
+
+def _wmse_args(who: str, pred: Tensor, target: Tensor, row_w: Tensor, col_w: Tensor, mask: Optional[Tensor]):
+    _dev(pred, target, row_w, col_w, mask)
+    _rows(pred)
+    if pred.shape != target.shape or not pred.is_contiguous() or not target.is_contiguous():
+        raise ValueError(f"{who}: pred and target must be contiguous [rows, V] of one shape")
+    tensors = [pred, target, row_w, col_w] + ([] if mask is None else [mask])
+    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
+        raise ValueError(f"{who}: every operand must be contiguous float32")
+    rows, v = pred.shape
+    g = row_w.numel()
+    if col_w.numel() != v or (mask is not None and tuple(mask.shape) != (g, v)):
+        raise ValueError(f"{who}: col_w [V] / mask [G, V] do not match pred {tuple(pred.shape)} and row_w [{g}]")
+    return rows, v, g
+
+
+def weighted_mse(pred: Tensor, target: Tensor, row_w: Tensor, col_w: Tensor, mask: Optional[Tensor] = None,
+                 scale: float = 1.0) -> Tensor:
+    """``scale * sum keep * row_w[r % G] * col_w[v] * (pred - target)^2`` as an f32 device scalar (``[rows, V]`` operands,
+    ``rows`` a multiple of ``G = len(row_w)``; ``mask`` ``[G, V]``, kept where non-zero): deterministic two-stage reduction."""
+    rows, v, g = _wmse_args("weighted_mse", pred, target, row_w, col_w, mask)
+    lib = _lib.load()
+    loss = torch.empty((), dtype=torch.float32, device=pred.device)
+    n_ws = lib.anemoi_weighted_mse_workspace_floats(rows, v)
+    ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=pred.device)
+    with _Timed("weighted_mse", bytes=2 * pred.numel() * 4):
+        st = lib.anemoi_weighted_mse(_ptr(pred) or ws.data_ptr(), _ptr(target) or ws.data_ptr(), rows, v, g, row_w.data_ptr(),
+                                     col_w.data_ptr(), _ptr(mask), float(scale), loss.data_ptr(), ws.data_ptr(), n_ws, _stream())
+    _lib.check(st, "anemoi_weighted_mse")
+    return loss
+
+
+def weighted_mse_backward(pred: Tensor, target: Tensor, row_w: Tensor, col_w: Tensor, mask: Optional[Tensor], scale: float,
+                          upstream: Tensor) -> Tensor:
+    """``d loss / d pred`` of :func:`weighted_mse`; ``upstream`` is the f32 DEVICE scalar gradient of the loss (read by the
+    kernel: no host synchronisation)."""
+    rows, v, g = _wmse_args("weighted_mse_backward", pred, target, row_w, col_w, mask)
+    _dev(upstream)
+    if upstream.dtype != torch.float32 or upstream.numel() != 1:
+        raise ValueError("weighted_mse_backward: upstream must be one float32 value on the device")
+    dpred = torch.empty_like(pred)
+    if rows == 0:
+        return dpred
+    st = _lib.load().anemoi_weighted_mse_backward(pred.data_ptr(), target.data_ptr(), rows, v, g, row_w.data_ptr(),
+                                                  col_w.data_ptr(), _ptr(mask), float(scale), upstream.data_ptr(),
+                                                  dpred.data_ptr(), _stream())
+    _lib.check(st, "anemoi_weighted_mse_backward")
+    return dpred
+
+
 def prognostic_residual(y: Tensor, x: Tensor, out_idx: Tensor, in_idx: Tensor) -> Tensor:
     """In place: ``y[..., out_idx] += x[:, -1, :, :, in_idx]`` (y f32 ``[B, Ens, G, V_out]`` contiguous)."""
     _dev(y, x, out_idx, in_idx)

@@ -23,6 +23,7 @@ keeps every activation instead (faster, config 3 then needs ~58 GiB per sample).
 
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Optional
 
@@ -43,6 +44,30 @@ def wants_grad(module: nn.Module, *tensors) -> bool:
     if any(isinstance(t, Tensor) and t.requires_grad for t in tensors):
         return True
     return any(p.requires_grad for p in module.parameters())
+
+
+_ROLLOUT_INPUT_GRAD = False
+
+
+@contextlib.contextmanager
+def rollout_input_grad():
+    """Inside this context ``model_forward`` / ``_finish`` keep the one-pass I/O kernels (:class:`_AssembleNodes`,
+    :class:`_PrognosticResidual`) for an input that requires a gradient -- steps 2.. of :class:`RolloutModel`, whose input is
+    the previous step's :func:`autograd.advance_input` -- and return ``dx`` from ``anemoi_assemble_nodes_backward`` /
+    ``anemoi_prognostic_residual_backward``.  Outside it (a direct ``model(x)`` with ``x.requires_grad``) the generic torch
+    route is kept as it was.  ``ANEMOI_AMD_ROLLOUT_FUSED=0`` switches the context off (A/B against the generic route)."""
+    global _ROLLOUT_INPUT_GRAD
+    outer, _ROLLOUT_INPUT_GRAD = _ROLLOUT_INPUT_GRAD, os.environ.get("ANEMOI_AMD_ROLLOUT_FUSED", "1") != "0"
+    try:
+        yield
+    finally:
+        _ROLLOUT_INPUT_GRAD = outer
+
+
+def _fused_io(x: Tensor) -> bool:
+    """May this input take the one-pass I/O kernels?  Always when it carries no gradient; with one, inside
+    :func:`rollout_input_grad` only."""
+    return not x.requires_grad or _ROLLOUT_INPUT_GRAD
 
 
 def _checkpoint(fn, *args, last: bool = False):
@@ -412,7 +437,8 @@ class _AssembleNodes(torch.autograd.Function):
     instead of permute / cat / cast here and one more concatenation per folded embedding (four passes over the 542 080 grid rows
     of config 3).  The constant 1 behind the features carries the embedding bias of the folded products
     (``autograd.folded_embedding_ln_linear(augmented=True)``) and meets zero weights everywhere else.  Backward: the columns of
-    the trainable tensor, summed over the batch; ``x`` carries no gradient on this route (the caller checks)."""
+    the trainable tensor, summed over the batch; ``x`` receives its gradient from ``anemoi_assemble_nodes_backward`` (one pass:
+    slice, cast and un-permute) when it requires one -- the rollout route, :func:`rollout_input_grad`."""
 
     @staticmethod
     def forward(ctx, x: Tensor, latlons: Tensor, trainable: Optional[Tensor], dtype: torch.dtype, ld: int):
@@ -423,21 +449,26 @@ class _AssembleNodes(torch.autograd.Function):
         ctx.off = x.shape[1] * x.shape[4] + latlons.shape[1]
         ctx.n_tr = 0 if trainable is None else trainable.shape[1]
         ctx.g, ctx.tr_dtype = g, (None if trainable is None else trainable.dtype)
+        ctx.x_shape = tuple(x.shape)
         return out
 
     @staticmethod
     def backward(ctx, grad: Tensor):
+        dx = ops.assemble_nodes_backward(grad if grad.stride(-1) == 1 else grad.contiguous(), ctx.x_shape) \
+            if ctx.needs_input_grad[0] else None
         if ctx.n_tr == 0 or not ctx.needs_input_grad[2]:
-            return None, None, None, None, None
+            return dx, None, None, None, None
         gt = grad[:, ctx.off:ctx.off + ctx.n_tr].float().reshape(-1, ctx.g, ctx.n_tr).sum(0)
-        return None, None, gt.to(ctx.tr_dtype), None, None
+        return dx, None, gt.to(ctx.tr_dtype), None, None
 
 
 class _PrognosticResidual(torch.autograd.Function):
     """``y = float(out)`` with ``y[..., prognostic] += x[:, -1, ..., prognostic_in]`` (reference
     models/encoder_processor_decoder.py:223-228) in the ONE pass of ``anemoi_finalize_output`` -- the inference route's
     kernel -- instead of zeros / index_select / index_put / add over the ``[grid, V_out]`` output (five passes over 173 MB at
-    config 3).  ``x`` carries no gradient on this route (the caller checks); the gradient of ``out`` is the incoming one."""
+    config 3).  The gradient of ``out`` is the incoming one; ``x`` receives its gradient -- the prognostic columns of the incoming
+    one in its last time slice, zeros elsewhere -- from ``anemoi_prognostic_residual_backward`` when it requires one (the rollout
+    route, :func:`rollout_input_grad`)."""
 
     @staticmethod
     def forward(ctx, out: Tensor, x: Tensor, src: Tensor, shape):
@@ -445,15 +476,17 @@ class _PrognosticResidual(torch.autograd.Function):
         y.view(out.shape).copy_(out)
         ops.finalize_output(y, x, src, None, None)
         ctx.out_shape, ctx.out_dtype = out.shape, out.dtype
+        ctx.src, ctx.x_shape = src, tuple(x.shape)
         return y
 
     @staticmethod
     def backward(ctx, g: Tensor):
-        return g.reshape(ctx.out_shape).to(ctx.out_dtype), None, None, None
+        dx = ops.prognostic_residual_backward(g.float().contiguous(), ctx.src, ctx.x_shape) if ctx.needs_input_grad[1] else None
+        return g.reshape(ctx.out_shape).to(ctx.out_dtype), dx, None, None
 
 
 def _finish(model, out: Tensor, x: Tensor, b: int, ens: int, g: int) -> Tensor:
-    if (out.is_cuda and not x.requires_grad and x.dtype == torch.float32 and x.dim() == 5
+    if (out.is_cuda and _fused_io(x) and x.dtype == torch.float32 and x.dim() == 5
             and os.environ.get("ANEMOI_AMD_TRAIN_FUSED_FINISH", "1") != "0"):
         key = ("residual_src", str(x.device))  # (the inference route's column map, models/encoder_processor_decoder.py::_finish)
         if key not in model._idx_cache:
@@ -497,7 +530,7 @@ def model_forward(model, x: Tensor) -> Tensor:
         na = model.node_attributes
         width = x.shape[1] * x.shape[4] + na.attr_ndims[data]
         # bf16 GraphTransformer mappers that fold their embedding: the input is written ONCE, in the layout of their first GEMMs
-        augmented = (x.is_cuda and not x.requires_grad and x.dtype == torch.float32 and dtype == torch.bfloat16
+        augmented = (x.is_cuda and _fused_io(x) and x.dtype == torch.float32 and dtype == torch.bfloat16
                      and isinstance(model.encoder, _GTMapper) and isinstance(model.decoder, _GTMapper)
                      and runtime.embed_fold_enabled(dtype) and hasattr(model.encoder, "emb_nodes_src")
                      and model.encoder.emb_nodes_src.in_features == width
@@ -586,3 +619,56 @@ def hierarchical_forward(model, x: Tensor) -> Tensor:
                 curr = model.up_level_processor[dst](curr, rows, None)
         out = first(run(model.decoder, curr, x_data, last=True))
         return _finish(model, out, x, b, ens, g)
+
+
+# ------------------------------------------------------------------------------------------------ rollout training
+class RolloutModel(nn.Module):
+    """``n_steps`` autoregressive applications of ``model`` with the gradient flowing through the whole chain -- what
+    anemoi-training's forecaster runs before it sums a loss over the steps.
+
+    ``forward(x, forcings=None)``: ``x`` normalised ``[B, T, Ens, G, V_in]``, ``forcings`` normalised ``[n_steps - 1, B, Ens,
+    G, F]`` (the forcing inputs valid at each step's output time, ordered like ``data_indices.internal_model.input.forcing``)
+    or ``None`` (the last forcing values persist); returns ``[n_steps, B, Ens, G, V_out]``.  Step 0 is the single-step route
+    as it is; between two steps the state advances through :func:`autograd.advance_input` (out of place, one kernel forward,
+    one backward), and the steps behind it -- whose input requires a gradient -- keep the one-pass I/O kernels
+    (:func:`rollout_input_grad`).  Under ``torch.no_grad()`` the same loop runs without a graph.  Works as the ``model`` of
+    ``runtime.GraphedTrainStep`` with the targets stacked like the result.  Single device: a model communication group is
+    refused (node-partitioned rollout training is not implemented)."""
+
+    def __init__(self, model: nn.Module, data_indices, n_steps: int) -> None:
+        super().__init__()
+        if n_steps < 1:
+            raise ValueError(f"RolloutModel: n_steps must be at least 1, got {n_steps}")
+        from .utils.indices import advance_colmap
+
+        self.model, self.n_steps = model, int(n_steps)
+        self._colmap_cpu = advance_colmap(data_indices)
+        self._n_forcing = int(data_indices.internal_model.input.forcing.numel())
+        self._colmaps: dict = {}  # per device (plain tensors, not buffers: the wrapped model's state_dict stays its own)
+
+    def _colmap(self, device) -> Tensor:
+        key = str(device)
+        if key not in self._colmaps:
+            self._colmaps[key] = self._colmap_cpu.to(device)
+        return self._colmaps[key]
+
+    def forward(self, x: Tensor, forcings: Optional[Tensor] = None, model_comm_group=None) -> Tensor:
+        if model_comm_group is not None:
+            raise NotImplementedError("RolloutModel runs on one device: node-partitioned rollout training is not implemented")
+        if forcings is not None and (forcings.dim() != 5 or forcings.shape[0] < self.n_steps - 1
+                                     or forcings.shape[-1] != self._n_forcing):
+            raise ValueError(f"RolloutModel: forcings must be [n_steps - 1 = {self.n_steps - 1}, B, Ens, G, "
+                             f"{self._n_forcing}], got {tuple(forcings.shape)}")
+        cmap = self._colmap(x.device)
+        outs = []
+        for step in range(self.n_steps):
+            if step == 0:
+                y = self.model(x)
+            else:
+                with rollout_input_grad():
+                    y = self.model(x)
+            outs.append(y)
+            if step + 1 < self.n_steps:
+                f = forcings[step] if forcings is not None and self._n_forcing > 0 else None
+                x = autograd.advance_input(x, y, cmap, f)
+        return torch.stack(outs)

@@ -74,3 +74,15 @@ class SimpleDataIndices:
         self.internal_data = self.data
         self.num_input = len(inp)
         self.num_output = len(out)
+
+
+def advance_colmap(data_indices) -> torch.Tensor:
+    """int32 ``[V_in]`` column map of the rollout's state advance (``anemoi_advance_input`` / ``anemoi_advance_state``), on
+    the CPU: prognostic inputs <- their output column, forcing inputs <- their position in the forcing tensor (-2 - k),
+    everything else persists (-1).  Shared by ``AnemoiModelInterface.rollout`` and ``training.RolloutModel``."""
+    idx = data_indices.internal_model
+    cmap = torch.full((len(idx.input),), -1, dtype=torch.int32)
+    cmap[idx.input.prognostic.long()] = idx.output.prognostic.to(torch.int32)
+    forcing = idx.input.forcing.long()
+    cmap[forcing] = -2 - torch.arange(forcing.numel(), dtype=torch.int32)
+    return cmap

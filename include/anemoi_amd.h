@@ -380,6 +380,71 @@ int anemoi_prognostic_residual(float* y, int V_out, const float* x, int B, int T
 int anemoi_advance_input(float* x, int B, int T, int Ens, int64_t G, int V_in, const float* y, int V_out,
                          const float* forcing, int F, const int32_t* colmap, anemoi_stream_t stream);
 
+/*
+ * Rollout training (ABI v47, csrc/rollout.hip): the differentiable state advance between two steps of a training rollout
+ * (anemoi-training sums a loss over the steps and lets the gradient flow through `advance_input`), the input gradients of
+ * the one-pass I/O kernels above, and the rollout loss.  Every output element is owned by exactly one thread: no atomics, the
+ * same bits on every run.  Outputs named "in full" are written completely (no zero-fill by the caller).
+ *
+ * anemoi_advance_state: the out-of-place form of anemoi_advance_input -- x_out (f32 [B, T, Ens, G, V_in], must not overlap
+ * x_in) receives what anemoi_advance_input would leave in a copy of x_in; same colmap / forcing / persist semantics, the
+ * same bits.
+ */
+int anemoi_advance_state(const float* x_in, float* x_out, int B, int T, int Ens, int64_t G, int V_in, const float* y,
+                         int V_out, const float* forcing, int F, const int32_t* colmap, anemoi_stream_t stream);
+
+/*
+ * Its backward.  dx_out is the gradient of x_out; dx_in (f32 [B, T, Ens, G, V_in], must not overlap dx_out) and dy (f32
+ * [B, Ens, G, V_out]) are written in full:
+ *   dx_in[:, 0] = 0 (T > 1);  dx_in[:, t] = dx_out[:, t-1] for t >= 1;
+ *   dx_in[:, T-1, .., v] += dx_out[:, T-1, .., v] in the persisting columns: colmap[v] == -1, or colmap[v] <= -2 when the
+ *   forward ran without forcing (has_forcing == 0);  with T == 1 only that term remains;
+ *   dy[.., m] = dx_out[:, T-1, .., inv_colmap[m]] where inv_colmap[m] >= 0, else 0.
+ * inv_colmap is int32 [V_out]: the input column v with colmap[v] == m, or -1 -- built once by the host, which refuses a
+ * colmap whose non-negative entries repeat.
+ */
+int anemoi_advance_state_backward(const float* dx_out, float* dx_in, float* dy, int B, int T, int Ens, int64_t G,
+                                  int V_in, int V_out, const int32_t* colmap, const int32_t* inv_colmap,
+                                  int has_forcing, anemoi_stream_t stream);
+
+/*
+ * Input gradient of anemoi_assemble_nodes: dx[b, t, ens, g, v] = float(grad[(b, ens, g), t * V + v]) -- the leading T * V
+ * columns of the gradient of its output (`dtype`, leading dimension ldg >= T * V).  dx is f32 [B, T, Ens, G, V], in full.
+ */
+int anemoi_assemble_nodes_backward(int dtype, const void* grad, int64_t ldg, float* dx, int B, int T, int Ens, int64_t G,
+                                   int V, anemoi_stream_t stream);
+
+/*
+ * Input gradient of the prognostic residual of anemoi_finalize_output (src int32 [V_out] as there, no affine maps): dx (f32
+ * [B, T, Ens, G, V_in], in full) is zero except dx[:, T-1, .., src[c]] = dy[.., c] where src[c] >= 0 (an input column that
+ * feeds several output columns receives their sum, in output-column order).  dy is f32 [B, Ens, G, V_out].  V_in <= 1024.
+ */
+int anemoi_prognostic_residual_backward(const float* dy, int V_out, float* dx, int B, int T, int Ens, int64_t G, int V_in,
+                                        const int32_t* src, anemoi_stream_t stream);
+
+/*
+ * Node-weighted, variable-scaled, masked squared error over pred / target (f32 [rows, V] contiguous; rows is a multiple of G
+ * and row r belongs to grid node r % G, so a stack of rollout steps, batch and ensemble members is one call):
+ *   loss = scale * sum_{r, v} keep(r, v) ? row_w[r % G] * col_w[v] * (pred - target)^2 : 0
+ * row_w f32 [G], col_w f32 [V], mask f32 [G, V] or NULL, keep = mask[r % G, v] != 0.  The mask is a SELECT: a masked element
+ * contributes exactly 0 even where pred or target is NaN (imputed values); an unmasked NaN propagates.  Two deterministic
+ * stages: one f32 partial per workgroup in `workspace` (anemoi_weighted_mse_workspace_floats(rows, V) floats -- the workgroup
+ * count is a function of rows * V alone, never of the device), then one workgroup sums the partials in a fixed order into
+ * loss (device f32 scalar).  rows == 0: loss = 0 by a memset.
+ */
+int64_t anemoi_weighted_mse_workspace_floats(int64_t rows, int V);
+int anemoi_weighted_mse(const float* pred, const float* target, int64_t rows, int V, int64_t G, const float* row_w,
+                        const float* col_w, const float* mask, float scale, float* loss, float* workspace,
+                        int64_t workspace_floats, anemoi_stream_t stream);
+
+/*
+ * Its gradient: dpred = upstream * scale * 2 * row_w * col_w * (pred - target) where kept, exactly 0 where masked.
+ * `upstream` is a DEVICE pointer to the f32 scalar gradient of loss: no host synchronisation (graph capture safe).
+ */
+int anemoi_weighted_mse_backward(const float* pred, const float* target, int64_t rows, int V, int64_t G,
+                                 const float* row_w, const float* col_w, const float* mask, float scale,
+                                 const float* upstream, float* dpred, anemoi_stream_t stream);
+
 /* dtype conversion / K-padding copy: dst[r, 0:cols] = src[r, 0:cols], dst[r, cols:ld_dst] = 0. */
 int anemoi_convert_pad(int src_dtype, const void* src, int64_t ld_src, int dst_dtype, void* dst, int64_t ld_dst,
                        int64_t rows, int cols, anemoi_stream_t stream);
