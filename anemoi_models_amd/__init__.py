@@ -1,4 +1,6 @@
-__all__ = ["WeightedMSELoss"]
+_LOSSES = ("WeightedMSELoss", "WeightedMAELoss", "WeightedHuberLoss", "WeightedLogCoshLoss", "WeightedRMSELoss",
+           "ValidationMetrics")
+__all__ = list(_LOSSES)
 
 
 def __getattr__(name):
@@ -6,6 +8,6 @@ def __getattr__(name):
 
     if name == "trail":  # anemoi_models_amd.trail: the launch trail (per-launch output digests), imported on first use
         return importlib.import_module(".trail", __name__)
-    if name == "WeightedMSELoss":  # anemoi_models_amd.losses: the rollout training loss, imported on first use
-        return importlib.import_module(".losses", __name__).WeightedMSELoss
+    if name in _LOSSES:  # anemoi_models_amd.losses: the training losses and validation metrics, imported on first use
+        return getattr(importlib.import_module(".losses", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -34,7 +34,10 @@ U8 = 3
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_RELU = 0, 1, 2, 3
 ACT_CODES = {"Identity": ACT_NONE, "GELU": ACT_GELU, "SiLU": ACT_SILU, "ReLU": ACT_RELU}
 
-ABI_VERSION = 47
+LOSS_MSE, LOSS_MAE, LOSS_HUBER, LOSS_LOGCOSH = 0, 1, 2, 3
+LOSS_KINDS = {"mse": LOSS_MSE, "mae": LOSS_MAE, "huber": LOSS_HUBER, "logcosh": LOSS_LOGCOSH}
+
+ABI_VERSION = 48
 
 
 class GtBlockArgs(ctypes.Structure):
@@ -185,6 +188,11 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_int64, c_void_p]),
     "anemoi_weighted_mse_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p,
                                              c_float, c_void_p, c_void_p, c_void_p]),
+    "anemoi_weighted_error_workspace_floats": (c_int64, [c_int64, c_int64, c_int]),
+    "anemoi_weighted_error": (c_int, [c_int, c_float, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
+    "anemoi_weighted_error_backward": (c_int, [c_int, c_float, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     "anemoi_transpose": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "anemoi_transpose_colsum_rows": (c_int64, [c_int64, c_int64]),
     "anemoi_transpose_chunked": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p,

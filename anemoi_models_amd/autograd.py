@@ -1361,3 +1361,42 @@ def weighted_mse(pred: Tensor, target: Tensor, row_w: Tensor, col_w: Tensor, mas
     f32 = lambda t: None if t is None else t.detach().float().contiguous()  # noqa: E731
     p2 = pred.float().contiguous().view(-1, v)
     return _WeightedMSE.apply(p2, f32(target).view(-1, v), f32(row_w), f32(col_w), f32(mask), float(scale))
+
+
+class _WeightedError(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred: Tensor, target: Tensor, row_w: Tensor, col_w: Optional[Tensor], mask: Optional[Tensor],
+                diff_scale: Optional[Tensor], kind: str, delta: float, n_groups: int, scale: float):
+        ctx.save_for_backward(pred, target, row_w, col_w, mask, diff_scale)
+        ctx.kw = dict(delta=delta, n_groups=n_groups, scale=scale)
+        ctx.kind = kind
+        return ops.weighted_error(pred, target, row_w, kind, col_w=col_w, mask=mask, diff_scale=diff_scale, **ctx.kw)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g: Tensor):
+        pred, target, row_w, col_w, mask, diff_scale = ctx.saved_tensors
+        dpred = ops.weighted_error_backward(pred, target, row_w, ctx.kind, col_w=col_w, mask=mask, diff_scale=diff_scale,
+                                            upstream=g.float().contiguous(), **ctx.kw)
+        dtarget = -dpred if ctx.needs_input_grad[1] else None
+        return (dpred if ctx.needs_input_grad[0] else None), dtarget, None, None, None, None, None, None, None, None
+
+
+def weighted_error(pred: Tensor, target: Tensor, row_w: Tensor, kind: str = "mse", *, delta: float = 1.0,
+                   col_w: Optional[Tensor] = None, mask: Optional[Tensor] = None, diff_scale: Optional[Tensor] = None,
+                   n_groups: int = 1, scale: float = 1.0) -> Tensor:
+    """``out[l, v] = scale * sum keep * row_w[g] * col_w[v] * f(diff_scale[v] * (pred - target))`` over ``pred`` ``[..., G,
+    V]`` flattened to rows and cut into ``n_groups`` equal groups of consecutive rows (the leading rollout axis, or 1): f32
+    ``[n_groups, V]`` with a gradient for ``pred`` (and ``target`` where it asks for one).  ``kind``: mse, mae, huber (with
+    ``delta``) or logcosh.  The mask is a select as in :func:`weighted_mse`.  What the caller composes on the small result --
+    a mean over the variables, a square root -- stays plain torch; its gradient reaches the backward kernel as a
+    per-variable upstream gradient on the device.  Deterministic: no atomics, every sum in an order fixed by the shape."""
+    g, v = row_w.numel(), pred.shape[-1]
+    if pred.shape != target.shape or pred.dim() < 2 or pred.shape[-2] != g:
+        raise ValueError(f"weighted_error: pred {tuple(pred.shape)} / target {tuple(target.shape)} do not end in [G = {g}, V]")
+    f32 = lambda t: None if t is None else t.detach().float().contiguous()  # noqa: E731
+    t2 = target.float().contiguous().view(-1, v)
+    if not target.requires_grad:
+        t2 = t2.detach()
+    return _WeightedError.apply(pred.float().contiguous().view(-1, v), t2, f32(row_w), f32(col_w), f32(mask), f32(diff_scale),
+                                str(kind), float(delta), int(n_groups), float(scale))

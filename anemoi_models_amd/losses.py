@@ -1,12 +1,20 @@
-"""Training losses on the HIP kernels.
+"""Training losses and validation metrics on the HIP kernels.
 
 ``WeightedMSELoss`` is anemoi-training's node-weighted, variable-scaled MSE with the imputers' loss mask: one deterministic
 reduction kernel forward (``anemoi_weighted_mse``), one element-wise kernel backward -- no atomics, the same bits on every run,
-like the rest of the training path."""
+like the rest of the training path.
+
+``WeightedMAELoss``, ``WeightedHuberLoss``, ``WeightedLogCoshLoss`` and ``WeightedRMSELoss`` -- and every loss with
+``squash=False`` or ``lead_dims > 0`` -- run on the per-variable reduction ``anemoi_weighted_error`` (``[rows, V] -> [groups,
+V]``, as deterministic); ``ValidationMetrics`` reports the same reductions in physical units per variable, variable group and
+rollout step, one launch pair per kind."""
 
 from __future__ import annotations
 
+import math
+from typing import Mapping
 from typing import Optional
+from typing import Sequence
 
 import torch
 from torch import Tensor
@@ -15,7 +23,57 @@ from torch import nn
 from . import autograd
 
 
-class WeightedMSELoss(nn.Module):
+class _NodeWeightedLoss(nn.Module):
+    """Node weights ``w^ = w / sum(w)``, optional per-variable weights, and the per-variable form shared by the family."""
+
+    kind = "mse"
+    delta = 1.0
+
+    def __init__(self, node_weights: Tensor, variable_weights: Optional[Tensor] = None) -> None:
+        super().__init__()
+        w = torch.as_tensor(node_weights).detach().double().reshape(-1)
+        if w.numel() == 0 or not bool((w >= 0).all()) or float(w.sum()) <= 0:
+            raise ValueError(f"{type(self).__name__}: node_weights must be non-negative with a positive sum")
+        self.register_buffer("node_weights", (w / w.sum()).float(), persistent=False)
+        s = None if variable_weights is None else torch.as_tensor(variable_weights).detach().float().reshape(-1).clone()
+        self.register_buffer("variable_weights", s, persistent=False)
+
+    def _check(self, pred: Tensor, mask: Optional[Tensor]):
+        name = type(self).__name__
+        g, v = self.node_weights.numel(), pred.shape[-1]
+        if pred.dim() < 2 or pred.shape[-2] != g:
+            raise ValueError(f"{name}: pred {tuple(pred.shape)} does not end in [G = {g}, V]")
+        s = self.variable_weights
+        if s is not None and s.numel() != v:
+            raise ValueError(f"{name}: {s.numel()} variable weights for {v} variables")
+        if mask is not None and tuple(mask.shape) != (g, v):
+            raise ValueError(f"{name}: mask must be [G = {g}, V = {v}], got {tuple(mask.shape)}")
+        return g, v
+
+    def per_variable(self, pred: Tensor, target: Tensor, mask: Optional[Tensor] = None, lead_dims: int = 0) -> Tensor:
+        """``[*pred.shape[:lead_dims], V]``: summed over the grid, averaged over the leading axes that are not kept, variable
+        weights applied, no ``1 / V`` -- anemoi-training's ``squash=False`` contract."""
+        g, v = self._check(pred, mask)
+        if not 0 <= lead_dims <= pred.dim() - 2:
+            raise ValueError(f"{type(self).__name__}: lead_dims = {lead_dims} of a pred with {pred.dim() - 2} leading axes")
+        lead = tuple(pred.shape[:lead_dims])
+        n_groups = math.prod(lead)
+        if n_groups == 0:
+            return torch.zeros(lead + (v,), dtype=torch.float32, device=pred.device)
+        n_avg = pred.numel() // max(n_groups * g * v, 1)
+        s = self.variable_weights
+        out = autograd.weighted_error(pred, target, self.node_weights.to(pred.device), self.kind, delta=self.delta,
+                                      col_w=None if s is None else s.to(pred.device), mask=mask, n_groups=n_groups,
+                                      scale=1.0 / max(n_avg, 1))
+        return out.reshape(lead + (v,))
+
+    def forward(self, pred: Tensor, target: Tensor, mask: Optional[Tensor] = None, squash: bool = True,
+                lead_dims: int = 0) -> Tensor:
+        out = self.per_variable(pred, target, mask, lead_dims)
+        return out.mean(-1) if squash else out
+
+
+class WeightedMSELoss(_NodeWeightedLoss):
     """``loss = 1 / (n_lead * V) * sum w^_g * s_v * keep * (pred - target)^2`` over ``pred`` ``[..., G, V]``: ``w^ = w /
     sum(w)`` the normalised node (area) weights, ``s`` the per-variable scaling (``None``: ones), ``n_lead`` the product of
     the leading dimensions (batch, ensemble, and a leading rollout axis where there is one) -- the node-weighted,
@@ -24,26 +82,142 @@ class WeightedMSELoss(nn.Module):
     ``mask`` ``[G, V]`` is an imputer's ``loss_mask_training`` as it is (1 = observed, 0 = imputed): masked values contribute
     exactly 0 to the loss and receive exactly 0 gradient, even where the target is NaN there."""
 
-    def __init__(self, node_weights: Tensor, variable_weights: Optional[Tensor] = None) -> None:
-        super().__init__()
-        w = torch.as_tensor(node_weights).detach().double().reshape(-1)
-        if w.numel() == 0 or not bool((w >= 0).all()) or float(w.sum()) <= 0:
-            raise ValueError("WeightedMSELoss: node_weights must be non-negative with a positive sum")
-        self.register_buffer("node_weights", (w / w.sum()).float(), persistent=False)
-        s = None if variable_weights is None else torch.as_tensor(variable_weights).detach().float().reshape(-1).clone()
-        self.register_buffer("variable_weights", s, persistent=False)
-
-    def forward(self, pred: Tensor, target: Tensor, mask: Optional[Tensor] = None) -> Tensor:
-        g, v = self.node_weights.numel(), pred.shape[-1]
-        if pred.dim() < 2 or pred.shape[-2] != g:
-            raise ValueError(f"WeightedMSELoss: pred {tuple(pred.shape)} does not end in [G = {g}, V]")
+    def forward(self, pred: Tensor, target: Tensor, mask: Optional[Tensor] = None, squash: bool = True,
+                lead_dims: int = 0) -> Tensor:
+        """``squash=False``: the per-variable values ``[V]`` (no ``1 / V``); ``lead_dims = k``: the first ``k`` axes of ``pred``
+        stay unreduced.  With the defaults: the scalar of the class docstring, on ``anemoi_weighted_mse`` as ever."""
+        if not squash or lead_dims != 0:
+            return super().forward(pred, target, mask, squash, lead_dims)
+        g, v = self._check(pred, mask)
         s = self.variable_weights
         if s is None:
             s = torch.ones(v, dtype=torch.float32, device=pred.device)
-        elif s.numel() != v:
-            raise ValueError(f"WeightedMSELoss: {s.numel()} variable weights for {v} variables")
-        if mask is not None and tuple(mask.shape) != (g, v):
-            raise ValueError(f"WeightedMSELoss: mask must be [G = {g}, V = {v}], got {tuple(mask.shape)}")
         n_lead = pred.numel() // max(g * v, 1)
         return autograd.weighted_mse(pred, target, self.node_weights.to(pred.device), s.to(pred.device), mask,
                                      1.0 / (max(n_lead, 1) * v))
+
+
+class WeightedMAELoss(_NodeWeightedLoss):
+    """:class:`WeightedMSELoss` with ``|pred - target|`` for the square; the gradient is ``sign(pred - target)``, 0 where
+    the two are equal (torch's convention)."""
+
+    kind = "mae"
+
+
+class WeightedHuberLoss(_NodeWeightedLoss):
+    """:class:`WeightedMSELoss` with the Huber function: ``0.5 d^2`` for ``|d| <= delta``, ``delta (|d| - 0.5 delta)``
+    beyond."""
+
+    kind = "huber"
+
+    def __init__(self, node_weights: Tensor, variable_weights: Optional[Tensor] = None, delta: float = 1.0) -> None:
+        super().__init__(node_weights, variable_weights)
+        if not float(delta) > 0:
+            raise ValueError(f"WeightedHuberLoss: delta must be positive, got {delta}")
+        self.delta = float(delta)
+
+
+class WeightedLogCoshLoss(_NodeWeightedLoss):
+    """:class:`WeightedMSELoss` with ``log cosh d`` for the square, in the overflow-free form ``|d| + log1p(exp(-2 |d|)) -
+    ln 2``; the gradient is ``tanh d``."""
+
+    kind = "logcosh"
+
+
+class WeightedRMSELoss(_NodeWeightedLoss):
+    """The square root of :class:`WeightedMSELoss`: per variable with ``squash=False``, of the squashed value with
+    ``squash=True``.  The square root is plain torch on the small result; its gradient reaches the kernel as the upstream
+    gradient."""
+
+    kind = "mse"
+
+    def forward(self, pred: Tensor, target: Tensor, mask: Optional[Tensor] = None, squash: bool = True,
+                lead_dims: int = 0) -> Tensor:
+        return super().forward(pred, target, mask, squash, lead_dims).sqrt()
+
+
+METRIC_KINDS = ("mse", "mae", "huber", "logcosh", "rmse")
+
+
+def _output_diff_scale(normalizer, n_vars: Optional[int] = None) -> Optional[Tensor]:
+    """``1 / _norm_mul`` at the model-output variables of an ``InputNormalizer`` (or of a ``Processors`` container that holds
+    nothing else): the scale that takes a difference of normalised values to physical units."""
+    from .preprocessing import Processors
+    from .preprocessing.normalizer import InputNormalizer
+
+    if normalizer is None:
+        return None
+    procs = list(normalizer.processors.values()) if isinstance(normalizer, Processors) else [normalizer]
+    other = [type(p).__name__ for p in procs if not isinstance(p, InputNormalizer)]
+    if other or len(procs) != 1:
+        raise NotImplementedError(
+            f"ValidationMetrics: only one affine InputNormalizer can be folded into the metric kernel (its additive term "
+            f"cancels in pred - target); got {[type(p).__name__ for p in procs]} -- an imputer or remapper is not affine")
+    norm = procs[0]
+    mul = norm._norm_mul.detach().double()
+    if n_vars is None or n_vars == norm._output_idx.numel():
+        mul = mul[norm._output_idx.long()]
+    elif n_vars != mul.numel():
+        raise ValueError(f"ValidationMetrics: {n_vars} variables, the normaliser has {norm._output_idx.numel()} output and "
+                         f"{mul.numel()} data variables")
+    if bool((mul == 0).any()) or not bool(torch.isfinite(mul).all()):
+        raise ValueError("ValidationMetrics: the normaliser has a zero or non-finite _norm_mul: it cannot be inverted")
+    return (1.0 / mul).float()
+
+
+class ValidationMetrics(nn.Module):
+    """Per-variable validation metrics in physical (de-normalised) units for every rollout step.
+
+    ``forward(pred, target, mask=None)`` takes the normalised ``[n_steps, B, Ens, G, V]`` model output and target (or ``[B,
+    Ens, G, V]``: one step) and returns ``{kind: [n_steps, V]}`` -- the node-weighted (``w^ = w / sum(w)``) error of kind
+    ``kind`` summed over the grid and averaged over batch and ensemble, of ``(pred - target) / _norm_mul`` -- and, with
+    ``groups`` (name -> indices of output variables), ``{kind/name: [n_steps]}``, the mean over the group's variables.  One
+    launch pair per kind and no de-normalised copy of either operand: the normaliser is affine, so its additive term cancels in
+    the difference and ``1 / _norm_mul`` enters the kernel as the per-variable scale of the difference.  ``kinds`` from mse,
+    mae, huber (``delta`` in physical units), logcosh, rmse (the square root of mse, per variable).  Runs without autograd."""
+
+    def __init__(self, node_weights: Tensor, normalizer=None, groups: Optional[Mapping[str, Sequence[int]]] = None,
+                 kinds: Sequence[str] = ("mse",), delta: float = 1.0) -> None:
+        super().__init__()
+        w = torch.as_tensor(node_weights).detach().double().reshape(-1)
+        if w.numel() == 0 or not bool((w >= 0).all()) or float(w.sum()) <= 0:
+            raise ValueError("ValidationMetrics: node_weights must be non-negative with a positive sum")
+        self.register_buffer("node_weights", (w / w.sum()).float(), persistent=False)
+        bad = [k for k in kinds if k not in METRIC_KINDS]
+        if bad or not kinds:
+            raise ValueError(f"ValidationMetrics: unknown kinds {bad} (from {METRIC_KINDS})")
+        if not float(delta) > 0:
+            raise ValueError(f"ValidationMetrics: delta must be positive, got {delta}")
+        self.kinds, self.delta = tuple(kinds), float(delta)
+        self.register_buffer("diff_scale", _output_diff_scale(normalizer), persistent=False)
+        self.groups = {str(k): [int(i) for i in idx] for k, idx in (groups or {}).items()}
+        if any(len(idx) == 0 for idx in self.groups.values()):
+            raise ValueError("ValidationMetrics: an empty variable group")
+
+    @torch.no_grad()
+    def forward(self, pred: Tensor, target: Tensor, mask: Optional[Tensor] = None) -> dict:
+        if pred.dim() == 4:
+            pred, target = pred[None], target[None]
+        g = self.node_weights.numel()
+        if pred.dim() != 5 or pred.shape != target.shape or pred.shape[-2] != g:
+            raise ValueError(f"ValidationMetrics: pred {tuple(pred.shape)} / target {tuple(target.shape)} must be "
+                             f"[n_steps, B, Ens, G = {g}, V] (or without the step axis)")
+        n_steps, v = pred.shape[0], pred.shape[-1]
+        c = self.diff_scale
+        if c is not None and c.numel() != v:
+            raise ValueError(f"ValidationMetrics: {v} variables, the normaliser has {c.numel()} output variables")
+        if any(i < 0 or i >= v for idx in self.groups.values() for i in idx):
+            raise ValueError(f"ValidationMetrics: a group index is not one of the {v} output variables")
+        n_avg = max(pred.shape[1] * pred.shape[2], 1)
+        out = {}
+        for kind in self.kinds:
+            per_var = autograd.weighted_error(pred, target, self.node_weights.to(pred.device),
+                                              "mse" if kind == "rmse" else kind, delta=self.delta, mask=mask,
+                                              diff_scale=None if c is None else c.to(pred.device), n_groups=n_steps,
+                                              scale=1.0 / n_avg)
+            if kind == "rmse":
+                per_var = per_var.sqrt()
+            out[kind] = per_var
+            for name, idx in self.groups.items():
+                out[f"{kind}/{name}"] = per_var[:, idx].mean(-1)
+        return out

@@ -1005,6 +1005,69 @@ def weighted_mse_backward(pred: Tensor, target: Tensor, row_w: Tensor, col_w: Te
     return dpred
 
 
+def _werr_args(who: str, pred: Tensor, target: Tensor, row_w: Tensor, kind: str, delta: float, col_w: Optional[Tensor],
+               mask: Optional[Tensor], diff_scale: Optional[Tensor], n_groups: int):
+    _dev(pred, target, row_w, col_w, mask, diff_scale)
+    _rows(pred)
+    if pred.shape != target.shape or not pred.is_contiguous() or not target.is_contiguous():
+        raise ValueError(f"{who}: pred and target must be contiguous [rows, V] of one shape")
+    tensors = [t for t in (pred, target, row_w, col_w, mask, diff_scale) if t is not None]
+    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
+        raise ValueError(f"{who}: every operand must be contiguous float32")
+    if kind not in _lib.LOSS_KINDS:
+        raise ValueError(f"{who}: unknown kind {kind!r} (one of {sorted(_lib.LOSS_KINDS)})")
+    if kind == "huber" and not float(delta) > 0:
+        raise ValueError(f"{who}: the Huber delta must be positive, got {delta}")
+    rows, v = pred.shape
+    g, n_groups = row_w.numel(), int(n_groups)
+    if any(t is not None and t.numel() != v for t in (col_w, diff_scale)) or (mask is not None and tuple(mask.shape) != (g, v)):
+        raise ValueError(f"{who}: col_w [V] / diff_scale [V] / mask [G, V] do not match pred {tuple(pred.shape)} and row_w [{g}]")
+    if n_groups < 1 or g < 1 or rows % (n_groups * g) != 0:
+        raise ValueError(f"{who}: {rows} rows are not {n_groups} groups of a multiple of G = {g} rows")
+    return rows, v, g, n_groups, _lib.LOSS_KINDS[kind]
+
+
+def weighted_error(pred: Tensor, target: Tensor, row_w: Tensor, kind: str, *, delta: float = 1.0,
+                   col_w: Optional[Tensor] = None, mask: Optional[Tensor] = None, diff_scale: Optional[Tensor] = None,
+                   n_groups: int = 1, scale: float = 1.0) -> Tensor:
+    """``out[l, v] = scale * sum_{r in group l} keep * row_w[r % G] * col_w[v] * f(diff_scale[v] * (pred - target))`` as f32
+    ``[n_groups, V]`` (``[rows, V]`` operands in ``n_groups`` equal groups of consecutive rows, each a multiple of ``G =
+    len(row_w)``; ``kind`` one of mse / mae / huber / logcosh): deterministic two-stage reduction, no atomics."""
+    rows, v, g, n_groups, code = _werr_args("weighted_error", pred, target, row_w, kind, delta, col_w, mask, diff_scale, n_groups)
+    lib = _lib.load()
+    out = torch.empty((n_groups, v), dtype=torch.float32, device=pred.device)
+    n_ws = lib.anemoi_weighted_error_workspace_floats(n_groups, rows // n_groups, v)
+    ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=pred.device)
+    with _Timed("weighted_error", bytes=2 * pred.numel() * 4):
+        st = lib.anemoi_weighted_error(code, float(delta), _ptr(pred) or ws.data_ptr(), _ptr(target) or ws.data_ptr(), rows, v,
+                                       g, n_groups, row_w.data_ptr(), _ptr(col_w), _ptr(mask), _ptr(diff_scale), float(scale),
+                                       out.data_ptr(), ws.data_ptr(), n_ws, _stream())
+    _lib.check(st, "anemoi_weighted_error")
+    return out
+
+
+def weighted_error_backward(pred: Tensor, target: Tensor, row_w: Tensor, kind: str, *, delta: float = 1.0,
+                            col_w: Optional[Tensor] = None, mask: Optional[Tensor] = None,
+                            diff_scale: Optional[Tensor] = None, n_groups: int = 1, scale: float = 1.0,
+                            upstream: Tensor) -> Tensor:
+    """``d (sum upstream * out) / d pred`` of :func:`weighted_error`; ``upstream`` is the f32 DEVICE ``[n_groups, V]`` gradient
+    of its result (read by the kernel: no host synchronisation)."""
+    rows, v, g, n_groups, code = _werr_args("weighted_error_backward", pred, target, row_w, kind, delta, col_w, mask,
+                                            diff_scale, n_groups)
+    _dev(upstream)
+    if upstream.dtype != torch.float32 or not upstream.is_contiguous() or tuple(upstream.shape) != (n_groups, v):
+        raise ValueError(f"weighted_error_backward: upstream must be contiguous float32 [{n_groups}, {v}] on the device")
+    dpred = torch.empty_like(pred)
+    if rows == 0:
+        return dpred
+    with _Timed("weighted_error_backward", bytes=3 * pred.numel() * 4):
+        st = _lib.load().anemoi_weighted_error_backward(code, float(delta), pred.data_ptr(), target.data_ptr(), rows, v, g,
+                                                        n_groups, row_w.data_ptr(), _ptr(col_w), _ptr(mask), _ptr(diff_scale),
+                                                        float(scale), upstream.data_ptr(), dpred.data_ptr(), _stream())
+    _lib.check(st, "anemoi_weighted_error_backward")
+    return dpred
+
+
 def prognostic_residual(y: Tensor, x: Tensor, out_idx: Tensor, in_idx: Tensor) -> Tensor:
     """In place: ``y[..., out_idx] += x[:, -1, :, :, in_idx]`` (y f32 ``[B, Ens, G, V_out]`` contiguous)."""
     _dev(y, x, out_idx, in_idx)

@@ -445,6 +445,45 @@ int anemoi_weighted_mse_backward(const float* pred, const float* target, int64_t
                                  const float* row_w, const float* col_w, const float* mask, float scale,
                                  const float* upstream, float* dpred, anemoi_stream_t stream);
 
+/*
+ * The loss family: per-variable node-weighted error over pred / target (f32 [rows, V] contiguous), one value per group of rows
+ * and variable.  rows = n_groups * rows_per_group with rows_per_group a multiple of G; group l is the rows
+ * [l * rows_per_group, (l + 1) * rows_per_group) (a rollout step; n_groups = 1: the whole tensor), row r is grid node r % G:
+ *   out[l, v] = scale * sum_{r in group l} keep(r, v) ? row_w[r % G] * col_w[v] * f(c[v] * (pred[r, v] - target[r, v])) : 0
+ * row_w f32 [G]; col_w f32 [V] or NULL (ones); mask f32 [G, V] or NULL, keep = mask[r % G, v] != 0, a SELECT as in
+ * anemoi_weighted_mse; diff_scale c f32 [V] or NULL (ones): the per-variable scale of the difference (de-normalisation).
+ * `kind` selects f (d = c * (pred - target)):
+ *   ANEMOI_LOSS_MSE      f = d^2                                                   f' = 2 d
+ *   ANEMOI_LOSS_MAE      f = |d|                                                   f' = sign(d), 0 at d = 0
+ *   ANEMOI_LOSS_HUBER    f = 0.5 d^2 if |d| <= delta else delta (|d| - 0.5 delta)  f' = d if |d| <= delta else delta sign(d)
+ *   ANEMOI_LOSS_LOGCOSH  f = |d| + log1p(exp(-2 |d|)) - ln 2                       f' = tanh(d)
+ * (`delta` is read by ANEMOI_LOSS_HUBER only and must be positive there.)  Two deterministic stages without atomics: every
+ * workgroup of stage 1 belongs to one group, reduces a contiguous chunk of its rows and writes one [V] partial to `workspace`
+ * (anemoi_weighted_error_workspace_floats(n_groups, rows_per_group, V) floats: the workgroup count and the chunks are functions
+ * of these three numbers alone); stage 2 adds the partials of a group per variable in ascending workgroup order and applies
+ * `scale`.  out is f32 [n_groups, V].  rows == 0: out = 0 by a memset.  n_groups <= 65535.
+ */
+#define ANEMOI_LOSS_MSE 0
+#define ANEMOI_LOSS_MAE 1
+#define ANEMOI_LOSS_HUBER 2
+#define ANEMOI_LOSS_LOGCOSH 3
+int64_t anemoi_weighted_error_workspace_floats(int64_t n_groups, int64_t rows_per_group, int V);
+int anemoi_weighted_error(int kind, float delta, const float* pred, const float* target, int64_t rows, int V, int64_t G,
+                          int64_t n_groups, const float* row_w, const float* col_w, const float* mask,
+                          const float* diff_scale, float scale, float* out, float* workspace, int64_t workspace_floats,
+                          anemoi_stream_t stream);
+
+/*
+ * Its gradient, one element-wise kernel:
+ *   dpred[r, v] = keep ? (scale * upstream[l, v] * row_w[r % G] * col_w[v] * c[v]) * f'(c[v] * (pred - target)) : 0
+ * `upstream` is a DEVICE pointer to the f32 [n_groups, V] gradient of out: no host synchronisation (graph capture safe).
+ * The gradient of target is -dpred.
+ */
+int anemoi_weighted_error_backward(int kind, float delta, const float* pred, const float* target, int64_t rows, int V,
+                                   int64_t G, int64_t n_groups, const float* row_w, const float* col_w, const float* mask,
+                                   const float* diff_scale, float scale, const float* upstream, float* dpred,
+                                   anemoi_stream_t stream);
+
 /* dtype conversion / K-padding copy: dst[r, 0:cols] = src[r, 0:cols], dst[r, cols:ld_dst] = 0. */
 int anemoi_convert_pad(int src_dtype, const void* src, int64_t ld_src, int dst_dtype, void* dst, int64_t ld_dst,
                        int64_t rows, int cols, anemoi_stream_t stream);
