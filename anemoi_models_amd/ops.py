@@ -1227,6 +1227,8 @@ def act_forward(pre: Tensor, act: str, residual: Optional[Tensor] = None) -> Ten
     _dev(pre, residual)
     rows, cols = _rows(pre).shape
     out = torch.empty((rows, cols), dtype=pre.dtype, device=pre.device)
+    if rows == 0:  # (an empty tensor has no storage: the library would see null pointers)
+        return out
     st = _lib.load().anemoi_act_forward(dtype_code(pre.dtype), _lib.ACT_CODES[act], pre.data_ptr(), _ld(pre),
                                         _ptr(residual), 0 if residual is None else _ld(_rows(residual)), out.data_ptr(),
                                         cols, rows, cols, _stream())
@@ -1241,6 +1243,8 @@ def act_backward(pre: Tensor, dy: Tensor, act: str) -> Tensor:
     if tuple(_rows(dy).shape) != (rows, cols) or dy.dtype != pre.dtype:
         raise ValueError("act_backward: pre and dy must have the same shape and dtype")
     out = torch.empty((rows, cols), dtype=pre.dtype, device=pre.device)
+    if rows == 0:  # (an edge phase without edges: an empty tensor has no storage, the library would see null pointers)
+        return out
     st = _lib.load().anemoi_act_backward(dtype_code(pre.dtype), _lib.ACT_CODES[act], pre.data_ptr(), _ld(pre),
                                          dy.data_ptr(), _ld(dy), out.data_ptr(), cols, rows, cols, _stream())
     _lib.check(st, "anemoi_act_backward")

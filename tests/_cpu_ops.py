@@ -208,6 +208,13 @@ def act_forward(pre, act, residual=None):
     return y if residual is None else y + residual
 
 
+def act_backward(pre, dy, act):
+    with torch.enable_grad():  # f32 torch autograd of the activation
+        p = pre.detach().float().requires_grad_()
+        (g,) = torch.autograd.grad(_ACT[act](p), p, dy.float())
+    return g.to(pre.dtype)
+
+
 def finalize_output(y, x, src, in_affine=None, out_affine=None, rows=None):
     last = x[:, -1]
     if rows is not None:  # y holds the rows of these grid nodes only (batch 1, ensemble 1)
@@ -261,5 +268,5 @@ def install(monkeypatch):
 
     for name in ("layer_norm", "layer_norm_with_stats", "row_stats", "linear", "linear_dual", "edge_attr_csr", "gt_edge_attention", "gt_edge_attention_folded",
                  "gt_conv", "gather_add_act", "segment_sum", "mhsa", "assemble_nodes",
-                 "prognostic_residual", "finalize_output", "bound_output", "advance_input", "convert_pad", "add", "act_forward"):
+                 "prognostic_residual", "finalize_output", "bound_output", "advance_input", "convert_pad", "add", "act_forward", "act_backward"):
         monkeypatch.setattr(ops, name, globals()[name])
