@@ -1,5 +1,5 @@
 _LOSSES = ("WeightedMSELoss", "WeightedMAELoss", "WeightedHuberLoss", "WeightedLogCoshLoss", "WeightedRMSELoss",
-           "ValidationMetrics")
+           "ValidationMetrics", "AlmostFairKernelCRPS", "KernelCRPS", "EnsembleMetrics")
 __all__ = list(_LOSSES)
 
 

@@ -37,7 +37,11 @@ ACT_CODES = {"Identity": ACT_NONE, "GELU": ACT_GELU, "SiLU": ACT_SILU, "ReLU": A
 LOSS_MSE, LOSS_MAE, LOSS_HUBER, LOSS_LOGCOSH = 0, 1, 2, 3
 LOSS_KINDS = {"mse": LOSS_MSE, "mae": LOSS_MAE, "huber": LOSS_HUBER, "logcosh": LOSS_LOGCOSH}
 
-ABI_VERSION = 48
+ENS_AFCRPS, ENS_MEAN_SE, ENS_VARIANCE = 0, 1, 2
+ENS_KINDS = {"afcrps": ENS_AFCRPS, "mean_se": ENS_MEAN_SE, "variance": ENS_VARIANCE}
+ENS_MAX_MEMBERS = 16
+
+ABI_VERSION = 49
 
 
 class GtBlockArgs(ctypes.Structure):
@@ -193,6 +197,11 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
     "anemoi_weighted_error_backward": (c_int, [c_int, c_float, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_void_p,
                                                c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "anemoi_ensemble_score_workspace_floats": (c_int64, [c_int64, c_int64, c_int, c_int]),
+    "anemoi_ensemble_score": (c_int, [c_int, c_float, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_int64, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
+    "anemoi_ensemble_score_backward": (c_int, [c_int, c_float, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_int64,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     "anemoi_transpose": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "anemoi_transpose_colsum_rows": (c_int64, [c_int64, c_int64]),
     "anemoi_transpose_chunked": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p,

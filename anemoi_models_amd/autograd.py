@@ -1400,3 +1400,47 @@ def weighted_error(pred: Tensor, target: Tensor, row_w: Tensor, kind: str = "mse
         t2 = t2.detach()
     return _WeightedError.apply(pred.float().contiguous().view(-1, v), t2, f32(row_w), f32(col_w), f32(mask), f32(diff_scale),
                                 str(kind), float(delta), int(n_groups), float(scale))
+
+
+class _EnsembleScore(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred: Tensor, target: Tensor, row_w: Tensor, col_w: Optional[Tensor], mask: Optional[Tensor],
+                diff_scale: Optional[Tensor], kind: str, n_members: int, alpha: float, n_groups: int, scale: float):
+        ctx.save_for_backward(pred, target, row_w, col_w, mask, diff_scale)
+        ctx.kw = dict(n_members=n_members, alpha=alpha, n_groups=n_groups, scale=scale)
+        ctx.kind = kind
+        return ops.ensemble_score(pred, target, row_w, kind, col_w=col_w, mask=mask, diff_scale=diff_scale, **ctx.kw)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g: Tensor):
+        pred, target, row_w, col_w, mask, diff_scale = ctx.saved_tensors
+        dpred = ops.ensemble_score_backward(pred, target, row_w, ctx.kind, col_w=col_w, mask=mask, diff_scale=diff_scale,
+                                            upstream=g.float().contiguous(), **ctx.kw)
+        return (dpred,) + (None,) * 10
+
+
+def ensemble_score(pred: Tensor, target: Tensor, row_w: Tensor, kind: str = "afcrps", *, alpha: float = 1.0,
+                   col_w: Optional[Tensor] = None, mask: Optional[Tensor] = None, diff_scale: Optional[Tensor] = None,
+                   n_groups: int = 1, scale: float = 1.0) -> Tensor:
+    """``out[l, v] = scale * sum keep * row_w[g] * col_w[v] * S(c_v x_1 .. c_v x_E, c_v y)`` over ``pred`` ``[..., E, G, V]``
+    and ``target`` ``[..., G, V]`` (the same leading axes, no ensemble axis), the points cut into ``n_groups`` equal groups along
+    the flattened leading axes (the leading rollout axis, or 1): f32 ``[n_groups, V]``.  ``kind``: afcrps -- the almost-fair
+    kernel CRPS ``1/E sum_j |x_j - y| - (1 - eps) / (2 E (E - 1)) sum_{j != k} |x_j - x_k|``, ``eps = (1 - alpha) / E`` (``alpha
+    = 1`` fair, ``alpha = 0`` the ensemble CRPS) --, mean_se ``(mean_j x_j - y)^2`` or variance ``1 / (E - 1) sum_j (x_j -
+    mean)^2``; ``2 <= E <= 16``.  Only afcrps has a gradient, for ``pred`` alone (``sgn`` of equal values is 0); the target
+    gets none.  The mask is a select as in :func:`weighted_error`.  Deterministic: no atomics, every sum in an order fixed by
+    the shape."""
+    g = row_w.numel()
+    if pred.dim() < 3 or target.dim() != pred.dim() - 1 or pred.shape[-2] != g \
+            or tuple(pred.shape[:-3]) + tuple(pred.shape[-2:]) != tuple(target.shape):
+        raise ValueError(f"ensemble_score: pred {tuple(pred.shape)} must be [..., E, G = {g}, V] and target "
+                         f"{tuple(target.shape)} the same without the ensemble axis")
+    if target.requires_grad:
+        raise ValueError("ensemble_score: the target requires a gradient, and the ensemble scores have none for it")
+    if pred.requires_grad and torch.is_grad_enabled() and str(kind) != "afcrps":
+        raise ValueError(f"ensemble_score: pred requires a gradient and kind {kind!r} has none (only afcrps has)")
+    v, e = pred.shape[-1], pred.shape[-3]
+    f32 = lambda t: None if t is None else t.detach().float().contiguous()  # noqa: E731
+    return _EnsembleScore.apply(pred.float().contiguous().view(-1, v), f32(target).view(-1, v), f32(row_w), f32(col_w),
+                                f32(mask), f32(diff_scale), str(kind), int(e), float(alpha), int(n_groups), float(scale))

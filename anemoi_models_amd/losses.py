@@ -7,7 +7,11 @@ like the rest of the training path.
 ``WeightedMAELoss``, ``WeightedHuberLoss``, ``WeightedLogCoshLoss`` and ``WeightedRMSELoss`` -- and every loss with
 ``squash=False`` or ``lead_dims > 0`` -- run on the per-variable reduction ``anemoi_weighted_error`` (``[rows, V] -> [groups,
 V]``, as deterministic); ``ValidationMetrics`` reports the same reductions in physical units per variable, variable group and
-rollout step, one launch pair per kind."""
+rollout step, one launch pair per kind.
+
+``AlmostFairKernelCRPS`` / ``KernelCRPS`` are the ensemble objectives (``pred`` carries an ensemble axis, ``target`` none) on
+``anemoi_ensemble_score``; ``EnsembleMetrics`` reports CRPS, ensemble-mean RMSE, spread and the spread/skill ratio from three
+launches of the same kernel."""
 
 from __future__ import annotations
 
@@ -220,4 +224,118 @@ class ValidationMetrics(nn.Module):
             out[kind] = per_var
             for name, idx in self.groups.items():
                 out[f"{kind}/{name}"] = per_var[:, idx].mean(-1)
+        return out
+
+
+class AlmostFairKernelCRPS(_NodeWeightedLoss):
+    """The almost-fair kernel CRPS of AIFS-CRPS over ``pred`` ``[..., E, G, V]`` and ``target`` ``[..., G, V]`` (the same
+    leading axes; the target has no ensemble axis): per point and variable
+
+    ``1/E sum_j |x_j - y| - (1 - eps) / (2 E (E - 1)) sum_{j != k} |x_j - x_k|``, ``eps = (1 - alpha) / E``
+
+    (``alpha = 1``: the fair CRPS, ``alpha = 0``: the ensemble CRPS with ``1 / (2 E^2)``), reduced as the family reduces:
+    summed over the grid with ``w^ = w / sum(w)``, averaged over the leading axes that are not kept, variable weights applied;
+    ``squash=False`` returns the per-variable values without ``1 / V``.  ``2 <= E <= 16``.  ``mask`` ``[G, V]`` is a select: a
+    masked point contributes exactly 0 and its members receive exactly 0 gradient.  The gradient of ``|.|`` at 0 is 0; the
+    target gets no gradient."""
+
+    kind = "afcrps"
+
+    def __init__(self, node_weights: Tensor, variable_weights: Optional[Tensor] = None, alpha: float = 1.0) -> None:
+        super().__init__(node_weights, variable_weights)
+        if not 0.0 <= float(alpha) <= 1.0:
+            raise ValueError(f"{type(self).__name__}: alpha must lie in [0, 1], got {alpha}")
+        self.alpha = float(alpha)
+
+    def per_variable(self, pred: Tensor, target: Tensor, mask: Optional[Tensor] = None, lead_dims: int = 0) -> Tensor:
+        """``[*pred.shape[:lead_dims], V]``; ``lead_dims <= pred.dim() - 3``: the ensemble axis is never a kept axis."""
+        name = type(self).__name__
+        g, v = self._check(pred, mask)
+        if pred.dim() < 3:
+            raise ValueError(f"{name}: pred {tuple(pred.shape)} must be [..., E, G = {g}, V]")
+        if not 0 <= lead_dims <= pred.dim() - 3:
+            raise ValueError(f"{name}: lead_dims = {lead_dims} of a pred with {pred.dim() - 3} leading axes before the "
+                             f"ensemble axis")
+        if tuple(target.shape) != tuple(pred.shape[:-3]) + (g, v):
+            raise ValueError(f"{name}: target {tuple(target.shape)} must be pred {tuple(pred.shape)} without the ensemble axis")
+        if target.requires_grad:
+            raise ValueError(f"{name}: the target requires a gradient, and the ensemble scores have none for it")
+        lead = tuple(pred.shape[:lead_dims])
+        n_groups = math.prod(lead)
+        if n_groups == 0:
+            return torch.zeros(lead + (v,), dtype=torch.float32, device=pred.device)
+        n_avg = target.numel() // max(n_groups * g * v, 1)
+        s = self.variable_weights
+        out = autograd.ensemble_score(pred, target, self.node_weights.to(pred.device), self.kind, alpha=self.alpha,
+                                      col_w=None if s is None else s.to(pred.device), mask=mask, n_groups=n_groups,
+                                      scale=1.0 / max(n_avg, 1))
+        return out.reshape(lead + (v,))
+
+
+class KernelCRPS(AlmostFairKernelCRPS):
+    """:class:`AlmostFairKernelCRPS` at its two ends: ``fair=True`` is ``alpha = 1`` (pair coefficient ``1 / (2 E (E - 1))``),
+    ``fair=False`` is ``alpha = 0`` (``1 / (2 E^2)``)."""
+
+    def __init__(self, node_weights: Tensor, variable_weights: Optional[Tensor] = None, fair: bool = True) -> None:
+        super().__init__(node_weights, variable_weights, alpha=1.0 if fair else 0.0)
+        self.fair = bool(fair)
+
+
+class EnsembleMetrics(nn.Module):
+    """Per-variable ensemble scores in physical (de-normalised) units for every rollout step.
+
+    ``forward(pred, target, mask=None)`` takes the normalised ``[n_steps, B, E, G, V]`` ensemble and its ``[n_steps, B, G, V]``
+    target (or both without the step axis) and returns ``[n_steps, V]`` each of
+
+    * ``crps``: the almost-fair kernel CRPS (``alpha``), node-weighted (``w^ = w / sum(w)``), averaged over the batch;
+    * ``ens_rmse``: the square root of the same reduction of ``(mean_j x_j - y)^2``;
+    * ``spread``: the square root of the same reduction of the ensemble variance ``1 / (E - 1) sum_j (x_j - mean)^2``;
+    * ``spread_skill``: ``sqrt((E + 1) / E) * spread / ens_rmse`` (1 for a statistically consistent ensemble),
+
+    and with ``groups`` (name -> indices of output variables) ``{key/name: [n_steps]}``, the mean of the per-variable values
+    over the group's variables.  Three launches of one kernel and no de-normalised copy: ``1 / _norm_mul`` of the (affine)
+    ``InputNormalizer`` enters as the per-variable scale, as in :class:`ValidationMetrics`.  Runs without autograd."""
+
+    KEYS = ("crps", "ens_rmse", "spread", "spread_skill")
+
+    def __init__(self, node_weights: Tensor, normalizer=None, groups: Optional[Mapping[str, Sequence[int]]] = None,
+                 alpha: float = 1.0) -> None:
+        super().__init__()
+        w = torch.as_tensor(node_weights).detach().double().reshape(-1)
+        if w.numel() == 0 or not bool((w >= 0).all()) or float(w.sum()) <= 0:
+            raise ValueError("EnsembleMetrics: node_weights must be non-negative with a positive sum")
+        self.register_buffer("node_weights", (w / w.sum()).float(), persistent=False)
+        if not 0.0 <= float(alpha) <= 1.0:
+            raise ValueError(f"EnsembleMetrics: alpha must lie in [0, 1], got {alpha}")
+        self.alpha = float(alpha)
+        self.register_buffer("diff_scale", _output_diff_scale(normalizer), persistent=False)
+        self.groups = {str(k): [int(i) for i in idx] for k, idx in (groups or {}).items()}
+        if any(len(idx) == 0 for idx in self.groups.values()):
+            raise ValueError("EnsembleMetrics: an empty variable group")
+
+    @torch.no_grad()
+    def forward(self, pred: Tensor, target: Tensor, mask: Optional[Tensor] = None) -> dict:
+        if pred.dim() == 4:
+            pred, target = pred[None], target[None]
+        g = self.node_weights.numel()
+        if pred.dim() != 5 or target.dim() != 4 or pred.shape[-2] != g \
+                or tuple(target.shape) != tuple(pred.shape[:2]) + tuple(pred.shape[3:]):
+            raise ValueError(f"EnsembleMetrics: pred {tuple(pred.shape)} / target {tuple(target.shape)} must be "
+                             f"[n_steps, B, E, G = {g}, V] / [n_steps, B, G, V] (or both without the step axis)")
+        n_steps, e, v = pred.shape[0], pred.shape[2], pred.shape[-1]
+        c = self.diff_scale
+        if c is not None and c.numel() != v:
+            raise ValueError(f"EnsembleMetrics: {v} variables, the normaliser has {c.numel()} output variables")
+        if any(i < 0 or i >= v for idx in self.groups.values() for i in idx):
+            raise ValueError(f"EnsembleMetrics: a group index is not one of the {v} output variables")
+        kw = dict(alpha=self.alpha, mask=mask, diff_scale=None if c is None else c.to(pred.device), n_groups=n_steps,
+                  scale=1.0 / max(pred.shape[1], 1))
+        w = self.node_weights.to(pred.device)
+        out = {"crps": autograd.ensemble_score(pred, target, w, "afcrps", **kw),
+               "ens_rmse": autograd.ensemble_score(pred, target, w, "mean_se", **kw).sqrt(),
+               "spread": autograd.ensemble_score(pred, target, w, "variance", **kw).sqrt()}
+        out["spread_skill"] = math.sqrt((e + 1) / e) * out["spread"] / out["ens_rmse"]
+        for key in self.KEYS:
+            for name, idx in self.groups.items():
+                out[f"{key}/{name}"] = out[key][:, idx].mean(-1)
         return out

@@ -1068,6 +1068,80 @@ def weighted_error_backward(pred: Tensor, target: Tensor, row_w: Tensor, kind: s
     return dpred
 
 
+def _ens_args(who: str, pred: Tensor, target: Tensor, row_w: Tensor, kind: str, n_members: int, alpha: float,
+              col_w: Optional[Tensor], mask: Optional[Tensor], diff_scale: Optional[Tensor], n_groups: int):
+    _dev(pred, target, row_w, col_w, mask, diff_scale)
+    _rows(pred)
+    _rows(target)
+    tensors = [t for t in (pred, target, row_w, col_w, mask, diff_scale) if t is not None]
+    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
+        raise ValueError(f"{who}: every operand must be contiguous float32")
+    if kind not in _lib.ENS_KINDS:
+        raise ValueError(f"{who}: unknown kind {kind!r} (one of {sorted(_lib.ENS_KINDS)})")
+    e = int(n_members)
+    if e < 2:
+        raise ValueError(f"{who}: an ensemble score needs at least 2 members, got n_members = {e}")
+    if e > _lib.ENS_MAX_MEMBERS:
+        raise NotImplementedError(f"{who}: n_members = {e}, at most {_lib.ENS_MAX_MEMBERS}")
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError(f"{who}: alpha must lie in [0, 1], got {alpha}")
+    rows, v = target.shape
+    if pred.shape[1] != v or pred.shape[0] != rows * e:
+        raise ValueError(f"{who}: pred {tuple(pred.shape)} is not [rows * n_members, V] of target {tuple(target.shape)} with "
+                         f"n_members = {e}")
+    g, n_groups = row_w.numel(), int(n_groups)
+    if any(t is not None and t.numel() != v for t in (col_w, diff_scale)) or (mask is not None and tuple(mask.shape) != (g, v)):
+        raise ValueError(f"{who}: col_w [V] / diff_scale [V] / mask [G, V] do not match target {tuple(target.shape)} and "
+                         f"row_w [{g}]")
+    if n_groups < 1 or g < 1 or rows % (n_groups * g) != 0:
+        raise ValueError(f"{who}: {rows} target rows are not {n_groups} groups of a multiple of G = {g} rows")
+    return rows, v, g, e, n_groups, _lib.ENS_KINDS[kind]
+
+
+def ensemble_score(pred: Tensor, target: Tensor, row_w: Tensor, kind: str, *, n_members: int, alpha: float = 1.0,
+                   col_w: Optional[Tensor] = None, mask: Optional[Tensor] = None, diff_scale: Optional[Tensor] = None,
+                   n_groups: int = 1, scale: float = 1.0) -> Tensor:
+    """``out[l, v] = scale * sum_{b, g} keep * row_w[g] * col_w[v] * S(members, target)`` as f32 ``[n_groups, V]``: ``target``
+    ``[n_groups * B * G, V]``, ``pred`` ``[n_groups * B * n_members * G, V]`` (member ``e`` of point ``(l, b, g)`` in row ``((l B +
+    b) E + e) G + g``), ``kind`` one of afcrps (with ``alpha``) / mean_se / variance, ``2 <= n_members <= 16``: deterministic
+    two-stage reduction, no atomics, every member read once."""
+    rows, v, g, e, n_groups, code = _ens_args("ensemble_score", pred, target, row_w, kind, n_members, alpha, col_w, mask,
+                                              diff_scale, n_groups)
+    lib = _lib.load()
+    out = torch.empty((n_groups, v), dtype=torch.float32, device=target.device)
+    n_ws = lib.anemoi_ensemble_score_workspace_floats(n_groups, rows // n_groups, v, e)
+    ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=target.device)
+    with _Timed("ensemble_score", bytes=(pred.numel() + target.numel()) * 4):
+        st = lib.anemoi_ensemble_score(code, float(alpha), _ptr(pred) or ws.data_ptr(), _ptr(target) or ws.data_ptr(), rows, v,
+                                       g, e, n_groups, row_w.data_ptr(), _ptr(col_w), _ptr(mask), _ptr(diff_scale),
+                                       float(scale), out.data_ptr(), ws.data_ptr(), n_ws, _stream())
+    _lib.check(st, "anemoi_ensemble_score")
+    return out
+
+
+def ensemble_score_backward(pred: Tensor, target: Tensor, row_w: Tensor, kind: str, *, n_members: int, alpha: float = 1.0,
+                            col_w: Optional[Tensor] = None, mask: Optional[Tensor] = None,
+                            diff_scale: Optional[Tensor] = None, n_groups: int = 1, scale: float = 1.0,
+                            upstream: Tensor) -> Tensor:
+    """``d (sum upstream * out) / d pred`` of :func:`ensemble_score` (afcrps only); ``upstream`` is the f32 DEVICE ``[n_groups,
+    V]`` gradient of its result (read by the kernel: no host synchronisation).  The target gets no gradient."""
+    rows, v, g, e, n_groups, code = _ens_args("ensemble_score_backward", pred, target, row_w, kind, n_members, alpha, col_w,
+                                              mask, diff_scale, n_groups)
+    _dev(upstream)
+    if upstream.dtype != torch.float32 or not upstream.is_contiguous() or tuple(upstream.shape) != (n_groups, v):
+        raise ValueError(f"ensemble_score_backward: upstream must be contiguous float32 [{n_groups}, {v}] on the device")
+    dpred = torch.empty_like(pred)
+    if rows == 0 and code == _lib.ENS_AFCRPS:
+        return dpred
+    with _Timed("ensemble_score_backward", bytes=(2 * pred.numel() + target.numel()) * 4):
+        st = _lib.load().anemoi_ensemble_score_backward(code, float(alpha), _ptr(pred) or upstream.data_ptr(),
+                                                        _ptr(target) or upstream.data_ptr(), rows, v, g, e, n_groups,
+                                                        row_w.data_ptr(), _ptr(col_w), _ptr(mask), _ptr(diff_scale),
+                                                        float(scale), upstream.data_ptr(), dpred.data_ptr(), _stream())
+    _lib.check(st, "anemoi_ensemble_score_backward")
+    return dpred
+
+
 def prognostic_residual(y: Tensor, x: Tensor, out_idx: Tensor, in_idx: Tensor) -> Tensor:
     """In place: ``y[..., out_idx] += x[:, -1, :, :, in_idx]`` (y f32 ``[B, Ens, G, V_out]`` contiguous)."""
     _dev(y, x, out_idx, in_idx)

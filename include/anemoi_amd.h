@@ -484,6 +484,52 @@ int anemoi_weighted_error_backward(int kind, float delta, const float* pred, con
                                    const float* diff_scale, float scale, const float* upstream, float* dpred,
                                    anemoi_stream_t stream);
 
+/*
+ * Ensemble scores (ABI v49, csrc/ensemble.hip): per-variable node-weighted scores of an E-member ensemble against one target,
+ * one value per group of points and variable.  target is f32 [rows, V] contiguous with rows = n_groups * B * G (no ensemble
+ * axis; group l is the rows [l * B * G, (l + 1) * B * G), a rollout step; row r is grid node r % G); pred is f32 [rows * E, V]
+ * contiguous, member e of point (l, b, g) in row ((l * B + b) * E + e) * G + g:
+ *   out[l, v] = scale * sum_{b, g} keep(g, v) ? row_w[g] * col_w[v] * S(c[v] x_1 .. c[v] x_E, c[v] y) : 0
+ * row_w f32 [G]; col_w f32 [V] or NULL (ones); mask f32 [G, V] or NULL, keep = mask[g, v] != 0, a SELECT as in
+ * anemoi_weighted_error (a masked point contributes exactly 0 even where the target is NaN or a member Inf); diff_scale c f32
+ * [V] or NULL (ones).  `kind` selects S:
+ *   ANEMOI_ENS_AFCRPS    S = 1/E sum_j |x_j - y| - (1 - eps) / (2 E (E - 1)) sum_{j != k} |x_j - x_k|,  eps = (1 - alpha) / E
+ *                        (the almost-fair kernel CRPS; alpha = 1: the fair CRPS, alpha = 0: the ensemble CRPS with 1 / (2 E^2))
+ *   ANEMOI_ENS_MEAN_SE   S = (mean_j x_j - y)^2
+ *   ANEMOI_ENS_VARIANCE  S = 1 / (E - 1) sum_j (x_j - mean)^2  (the mean first, then the squares)
+ * evaluated on e_j = c (x_j - y), which S takes the same value on; the CRPS as the sum over the pairs j < k of the non-negative
+ * 2 |med3(e_j, e_k, 0)| + eps |e_j - e_k| (= |e_j| + |e_k| - (1 - eps) |e_j - e_k|) over E (E - 1).  2 <= E <= 16 (E < 2:
+ * ANEMOI_ERR_INVALID, E > 16: ANEMOI_ERR_UNSUPPORTED); alpha in [0, 1] for every kind (read by ANEMOI_ENS_AFCRPS only).
+ * Every member is read once and held in registers.  Two deterministic stages without atomics: every workgroup of stage 1
+ * belongs to one group, reduces a contiguous chunk of its points (members ascending, pairs ascending in (j, k)) and writes one
+ * [V] partial to `workspace`
+ * (anemoi_ensemble_score_workspace_floats(n_groups, B * G, V, E) floats: the workgroup count and the chunks are functions of
+ * these four numbers alone); stage 2 adds the partials of a group per variable in ascending workgroup order and applies
+ * `scale`.  out is f32 [n_groups, V].  rows == 0: out = 0 by a memset.  n_groups <= 65535, G * V < 2^31.
+ */
+#define ANEMOI_ENS_AFCRPS 0
+#define ANEMOI_ENS_MEAN_SE 1
+#define ANEMOI_ENS_VARIANCE 2
+int64_t anemoi_ensemble_score_workspace_floats(int64_t n_groups, int64_t points_per_group, int V, int E);
+int anemoi_ensemble_score(int kind, float alpha, const float* pred, const float* target, int64_t rows, int V, int64_t G, int E,
+                          int64_t n_groups, const float* row_w, const float* col_w, const float* mask,
+                          const float* diff_scale, float scale, float* out, float* workspace, int64_t workspace_floats,
+                          anemoi_stream_t stream);
+
+/*
+ * The gradient of ANEMOI_ENS_AFCRPS for the members (the other kinds: ANEMOI_ERR_UNSUPPORTED; the target gets none), one
+ * thread per point and variable writing its E values:
+ *   dpred[e] = keep ? scale * upstream[l, v] * row_w[g] * col_w[v] * |c[v]|
+ *                     * (sgn(x_e - y) / E - (1 - eps) / (E (E - 1)) sum_k sgn(x_e - x_k)) : 0
+ * sgn is taken by comparing the raw members, so equal values give exactly 0 (torch's convention for |.|).  `upstream` is a
+ * DEVICE pointer to the f32 [n_groups, V] gradient of out: no host synchronisation (graph capture safe).  dpred is f32
+ * [rows * E, V].
+ */
+int anemoi_ensemble_score_backward(int kind, float alpha, const float* pred, const float* target, int64_t rows, int V,
+                                   int64_t G, int E, int64_t n_groups, const float* row_w, const float* col_w,
+                                   const float* mask, const float* diff_scale, float scale, const float* upstream,
+                                   float* dpred, anemoi_stream_t stream);
+
 /* dtype conversion / K-padding copy: dst[r, 0:cols] = src[r, 0:cols], dst[r, cols:ld_dst] = 0. */
 int anemoi_convert_pad(int src_dtype, const void* src, int64_t ld_src, int dst_dtype, void* dst, int64_t ld_dst,
                        int64_t rows, int cols, anemoi_stream_t stream);
