@@ -41,7 +41,15 @@ ENS_AFCRPS, ENS_MEAN_SE, ENS_VARIANCE = 0, 1, 2
 ENS_KINDS = {"afcrps": ENS_AFCRPS, "mean_se": ENS_MEAN_SE, "variance": ENS_VARIANCE}
 ENS_MAX_MEMBERS = 16
 
-ABI_VERSION = 49
+COND_LN_MAX_K = 32  # the fused conditional LayerNorm's widest condition (CLN_MAX_K of csrc/cond_layer_norm.hip)
+
+
+def cond_ln_padded_k(k: int) -> int:
+    """The column count (4, 8, 16 or 32) the fused conditional LayerNorm takes a condition of ``k <= 32`` columns padded to."""
+    return 4 if k <= 4 else (8 if k <= 8 else (16 if k <= 16 else 32))
+
+
+ABI_VERSION = 51
 
 
 class GtBlockArgs(ctypes.Structure):
@@ -202,6 +210,13 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
     "anemoi_ensemble_score_backward": (c_int, [c_int, c_float, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_int64,
                                                c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "anemoi_cond_layer_norm": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_float, c_void_p]),
+    "anemoi_cond_layer_norm_backward_workspace_floats": (c_int64, [c_int64, c_int, c_int]),
+    "anemoi_cond_layer_norm_backward": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int,
+                                                c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "anemoi_gaussian_noise": (c_int, [c_void_p, c_int64, c_int, c_float, c_uint32, c_void_p, c_void_p]),
     "anemoi_transpose": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "anemoi_transpose_colsum_rows": (c_int64, [c_int64, c_int64]),
     "anemoi_transpose_chunked": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p,

@@ -28,6 +28,7 @@ from typing import Optional
 import torch
 from torch import Tensor
 
+from . import _lib
 from . import ops
 from . import runtime
 
@@ -425,6 +426,53 @@ def linear(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, act: str = 
 def layer_norm(x: Tensor, gamma: Tensor, beta: Tensor, eps: float = 1e-5) -> Tensor:
     """``LayerNorm(x) * gamma + beta`` over the last dimension with gradients for ``x``, ``gamma``, ``beta``."""
     return _LayerNorm.apply(x, gamma, beta, eps)
+
+
+class _CondLayerNorm(torch.autograd.Function):
+    """The fused conditional LayerNorm (``anemoi_cond_layer_norm`` / ``_backward``): neither ``[rows, C]`` product of the
+    condition exists in the forward or in the backward."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, cond: Tensor, w_scale: Tensor, b_scale: Tensor, w_bias: Tensor, b_bias: Tensor, eps: float):
+        y, stats = ops.cond_layer_norm(x, cond, w_scale, b_scale, w_bias, b_bias, eps, with_stats=True)
+        ctx.save_for_backward(x, stats, cond, w_scale, b_scale, w_bias)
+        ctx.dtypes = (cond.dtype, w_scale.dtype, b_scale.dtype, w_bias.dtype, b_bias.dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        x, stats, cond, w_scale, b_scale, w_bias = ctx.saved_tensors
+        grads = ops.cond_layer_norm_backward(dy.contiguous(), x, stats, cond, w_scale, b_scale, w_bias)
+        return (grads[0], *(g.to(dt) for g, dt in zip(grads[1:], ctx.dtypes)), None)
+
+
+def cond_layer_norm_composed(x: Tensor, cond: Tensor, w_scale: Tensor, b_scale: Tensor, w_bias: Tensor, b_bias: Tensor,
+                             eps: float = 1e-5) -> Tensor:
+    """:func:`cond_layer_norm` from existing operations: two fused Linears of the condition, a LayerNorm with ``gamma = 1,
+    beta = 0`` and two element-wise passes.  The route of a condition wider than the fused kernel takes, the cross-check of
+    the tests and the baseline of ``tools/cond_ln_bench.py``."""
+    c_in = cond.to(x.dtype)
+    scale = linear(c_in, w_scale, b_scale)
+    shift = linear(c_in, w_bias, b_bias)
+    ones = torch.ones(x.shape[1], dtype=torch.float32, device=x.device)
+    xh = layer_norm(x, ones, torch.zeros_like(ones), eps)
+    return xh * (1.0 + scale) + shift
+
+
+def cond_layer_norm(x: Tensor, cond: Tensor, w_scale: Tensor, b_scale: Tensor, w_bias: Tensor, b_bias: Tensor,
+                    eps: float = 1e-5) -> Tensor:
+    """``xhat(x) * (1 + cond @ w_scale.T + b_scale) + (cond @ w_bias.T + b_bias)`` with gradients for all six tensors: ``x``
+    ``[rows, C]`` in the compute dtype, ``cond [rows, K]``, the weights ``[C, K]`` and biases ``[C]`` of the two Linears of
+    ``layers.normalization.ConditionalLayerNorm``.  ``K <= 32``: one fused row kernel each way; wider: composed."""
+    if not cond_layer_norm_fused(cond.shape[1]):
+        return cond_layer_norm_composed(x, cond, w_scale, b_scale, w_bias, b_bias, eps)
+    return _CondLayerNorm.apply(x, cond, w_scale, b_scale, w_bias, b_bias, eps)
+
+
+def cond_layer_norm_fused(k: int) -> bool:
+    """Does a condition of ``k`` columns take the fused kernels?  Up to 32 columns, unless ``ANEMOI_AMD_COND_LN=composed`` (the
+    A/B switch of ``tools/cond_ln_bench.py``)."""
+    return k <= _lib.COND_LN_MAX_K and os.environ.get("ANEMOI_AMD_COND_LN", "fused") != "composed"
 
 
 class _ScaledLinear(torch.autograd.Function):

@@ -32,6 +32,7 @@ from .mlp import NativeSequential
 from .mlp import activation_class
 from .mlp import fused_activation_name
 from .mlp import linear_native
+from .normalization import ConditionalLayerNorm
 
 
 def inference_num_chunks() -> int:
@@ -1017,27 +1018,50 @@ class GraphConvMapperBlock(GraphConvBaseBlock):
 # =============================================================================================
 class TransformerProcessorBlock(BaseBlock):
     def __init__(self, num_channels: int, hidden_dim: int, num_heads: int, activation: str, window_size: int,
-                 dropout_p: float = 0.0):
+                 dropout_p: float = 0.0, cond_dim: Optional[int] = None):
         super().__init__()
         from .attention import MultiHeadSelfAttention
 
         act = activation_class(activation)
-        self.layer_norm1 = nn.LayerNorm(num_channels)
+        self.cond_dim = cond_dim
+        # cond_dim: both LayerNorms are conditional on a per-row embedding of width cond_dim (the ensemble model's noise)
+        norm = (lambda: nn.LayerNorm(num_channels)) if cond_dim is None else (
+            lambda: ConditionalLayerNorm(num_channels, cond_dim))
+        self.layer_norm1 = norm()
         self.attention = MultiHeadSelfAttention(num_heads=num_heads, embed_dim=num_channels, window_size=window_size,
                                                 bias=False, is_causal=False, dropout_p=dropout_p)
         self.mlp = nn.Sequential(nn.Linear(num_channels, hidden_dim), act(), nn.Linear(hidden_dim, num_channels))
-        self.layer_norm2 = nn.LayerNorm(num_channels)
+        self.layer_norm2 = norm()
 
         self._mlp: Optional[NativeSequential] = None
 
-    def native(self, x: Tensor, batch_size: int, head_exchange=None) -> Tensor:
+    def _check_cond(self, cond: Optional[Tensor], sharded: bool) -> None:
+        if (cond is None) != (self.cond_dim is None):
+            raise ValueError("TransformerProcessorBlock: `cond` goes with cond_dim (a block built with cond_dim needs it, "
+                             "a block built without takes none)")
+        if cond is not None and sharded:
+            raise NotImplementedError("TransformerProcessorBlock: conditional LayerNorms are not implemented across a model "
+                                      "communication group")
+
+    def native(self, x: Tensor, batch_size: int, head_exchange=None, cond: Optional[Tensor] = None) -> Tensor:
         """Pre-LN attention residual + pre-LN MLP residual (reference layers/block.py:99-105).
 
         ``head_exchange`` (node-partitioned run): q|k|v of the own rows go through an all-to-all so that this rank holds
         ALL rows of its share of the heads, attention runs on those heads, and a second all-to-all brings the own rows
-        of all heads back."""
+        of all heads back.  ``cond`` ``[rows, cond_dim]`` f32: the condition of the two conditional LayerNorms."""
+        self._check_cond(cond, head_exchange is not None)
         ln1, ln2 = self.layer_norm1, self.layer_norm2
         att = self.attention
+        if cond is not None:  # op by op: the block-level entry point knows the plain LayerNorm only
+            h = ln1.native(x, cond)
+            qkv = linear_native(att._packed, "lin_qkv", att.lin_qkv, h)
+            drop_p, drop_seed, drop_dev = att.dropout()
+            a = ops.mhsa(qkv, batch_size, att.num_heads, att.attention_window(), dropout_p=drop_p, dropout_seed=drop_seed,
+                         seed_dev=drop_dev)
+            x = linear_native(att._packed, "projection", att.projection, a, residual=x)
+            if self._mlp is None:
+                self._mlp = NativeSequential(self.mlp)
+            return self._mlp(ln2.native(x, cond), residual=x)
         if head_exchange is None:
             done = self._block_abi(x, batch_size)
             if done is not None:
@@ -1078,6 +1102,8 @@ class TransformerProcessorBlock(BaseBlock):
 
         from .. import _lib
 
+        if self.cond_dim is not None:
+            return None
         dtype, att = x.dtype, self.attention
         c, rows = x.shape[1], x.shape[0]
         mult = ops.k_multiple(dtype)
@@ -1151,10 +1177,11 @@ class TransformerProcessorBlock(BaseBlock):
         h = ops.layer_norm(x, runtime.f32c(ln2.weight), runtime.f32c(ln2.bias), ln2.eps)
         return self._mlp(h, residual=x)
 
-    def forward(self, x: Tensor, shapes: list, batch_size: int, model_comm_group=None) -> Tensor:
+    def forward(self, x: Tensor, shapes: list, batch_size: int, model_comm_group=None, cond: Optional[Tensor] = None) -> Tensor:
+        self._check_cond(cond, _group_size(model_comm_group) > 1)
         if _group_size(model_comm_group) > 1:
             return self._sharded(x, shapes, batch_size, model_comm_group)
-        if training.wants_grad(self, x):
-            return training.transformer_block(self, x, batch_size)
+        if training.wants_grad(self, x, cond):
+            return training.transformer_block(self, x, batch_size, cond)
         dtype = runtime.compute_dtype(x)
-        return self.native(_as_compute(x, dtype), batch_size)
+        return self.native(_as_compute(x, dtype), batch_size, cond=cond)

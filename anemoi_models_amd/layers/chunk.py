@@ -35,21 +35,26 @@ class BaseProcessorChunk(nn.Module, ABC):
 
 class TransformerProcessorChunk(BaseProcessorChunk):
     def __init__(self, num_channels: int, num_layers: int, window_size: int, num_heads: int = 16,
-                 mlp_hidden_ratio: int = 4, activation: str = "GELU", dropout_p: float = 0.0) -> None:
+                 mlp_hidden_ratio: int = 4, activation: str = "GELU", dropout_p: float = 0.0,
+                 cond_dim: Optional[int] = None) -> None:
         super().__init__(num_channels=num_channels, num_layers=num_layers)
+        kw = {} if cond_dim is None else {"cond_dim": cond_dim}
         self.build_blocks(
             TransformerProcessorBlock, num_channels=num_channels, hidden_dim=mlp_hidden_ratio * num_channels,
-            num_heads=num_heads, activation=activation, window_size=window_size, dropout_p=dropout_p,
+            num_heads=num_heads, activation=activation, window_size=window_size, dropout_p=dropout_p, **kw,
         )
 
-    def native(self, x: Tensor, batch_size: int) -> Tensor:
+    def native(self, x: Tensor, batch_size: int, cond: Optional[Tensor] = None) -> Tensor:
         for blk in self.blocks:
-            x = blk.native(x, batch_size)
+            x = blk.native(x, batch_size) if cond is None else blk.native(x, batch_size, cond=cond)
         return x
 
-    def forward(self, x: Tensor, shapes: list, batch_size: int, model_comm_group=None):
+    def forward(self, x: Tensor, shapes: list, batch_size: int, model_comm_group=None, cond: Optional[Tensor] = None):
         for blk in self.blocks:
-            x = blk(x, shapes, batch_size, model_comm_group=model_comm_group)
+            if cond is None:
+                x = blk(x, shapes, batch_size, model_comm_group=model_comm_group)
+            else:
+                x = blk(x, shapes, batch_size, model_comm_group=model_comm_group, cond=cond)
         return (x,)
 
 

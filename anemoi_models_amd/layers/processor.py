@@ -66,26 +66,31 @@ class BaseProcessor(nn.Module, ABC):
 class TransformerProcessor(BaseProcessor):
     def __init__(self, num_layers: int, *args, window_size: Optional[int] = None, num_channels: int = 128,
                  num_chunks: int = 2, activation: str = "GELU", cpu_offload: bool = False, num_heads: int = 16,
-                 mlp_hidden_ratio: int = 4, dropout_p: float = 0.1, **kwargs) -> None:
+                 mlp_hidden_ratio: int = 4, dropout_p: float = 0.1, cond_dim: Optional[int] = None, **kwargs) -> None:
         super().__init__(num_channels=num_channels, num_layers=num_layers, num_chunks=num_chunks,
                          activation=activation, cpu_offload=cpu_offload)
+        self.cond_dim = cond_dim
+        kw = {} if cond_dim is None else {"cond_dim": cond_dim}
         self.build_layers(
             TransformerProcessorChunk, num_channels=num_channels, mlp_hidden_ratio=mlp_hidden_ratio,
             num_heads=num_heads, num_layers=self.chunk_size, window_size=window_size, activation=activation,
-            dropout_p=dropout_p,
+            dropout_p=dropout_p, **kw,
         )
         self.offload_layers(cpu_offload)
 
-    def native(self, x: Tensor, batch_size: int, node_map: Optional[Tensor] = None) -> Tensor:
+    def native(self, x: Tensor, batch_size: int, node_map: Optional[Tensor] = None, cond: Optional[Tensor] = None) -> Tensor:
         """x ``[B * N, C]`` in the compute dtype.  Global attention is permutation-equivariant, so an internal node
-        order needs no special handling; a sliding window acts on the EXTERNAL order, hence the un/re-permutation."""
+        order needs no special handling; a sliding window acts on the EXTERNAL order, hence the un/re-permutation.
+        ``cond`` ``[B * N, cond_dim]`` (a processor built with ``cond_dim``): row ``i`` of it conditions row ``i`` of ``x``
+        as handed in."""
         windowed = self.proc[0].blocks[0].attention.attention_window() >= 0
         if node_map is not None and windowed:
             n = node_map.shape[0]
             ext = torch.cat([node_map + b * n for b in range(batch_size)])  # external row -> internal row
             x = x.index_select(0, ext)
+            cond = None if cond is None else cond.index_select(0, ext)
         for chunk in self.proc:
-            x = chunk.native(x, batch_size)
+            x = chunk.native(x, batch_size) if cond is None else chunk.native(x, batch_size, cond)
         if node_map is not None and windowed:
             back = torch.empty_like(x)
             back[ext] = x
@@ -100,24 +105,30 @@ class TransformerProcessor(BaseProcessor):
                 x_own = blk.native(x_own, 1, head_exchange=local_graph.heads)
         return x_own
 
-    def forward(self, x: Tensor, batch_size: int, shard_shapes, model_comm_group=None, *args, **kwargs) -> Tensor:
+    def forward(self, x: Tensor, batch_size: int, shard_shapes, model_comm_group=None, *args,
+                cond: Optional[Tensor] = None, **kwargs) -> Tensor:
+        if (cond is None) != (self.cond_dim is None):
+            raise ValueError("TransformerProcessor: `cond` goes with cond_dim")
         if model_comm_group is not None:
             assert (
                 model_comm_group.size() == 1 or batch_size == 1
             ), "Only batch size of 1 is supported when model is sharded accross GPUs"
             if model_comm_group.size() > 1:
+                if cond is not None:
+                    raise NotImplementedError("TransformerProcessor: conditional LayerNorms are not implemented across a model "
+                                              "communication group")
                 # the reference's protocol (layers/processor.py:103-137): x is this rank's row shard, shard_shapes the row
                 # counts of all ranks; every block reshards rows <-> heads around its attention
                 for chunk in self.proc:
                     for blk in chunk.blocks:
                         x = blk(x, shard_shapes, batch_size, model_comm_group)
                 return x
-        if training.wants_grad(self, x):
+        if training.wants_grad(self, x, cond):
             with self._offloaded():
-                return training.transformer_processor(self, x, batch_size)
+                return training.transformer_processor(self, x, batch_size, cond)
         dtype = runtime.compute_dtype(x)
         xin = x if x.dtype == dtype else x.to(dtype)
-        return self.native(xin if xin.stride(-1) == 1 else xin.contiguous(), batch_size)
+        return self.native(xin if xin.stride(-1) == 1 else xin.contiguous(), batch_size, cond=cond)
 
 
 class GNNProcessor(GraphEdgeMixin, BaseProcessor):

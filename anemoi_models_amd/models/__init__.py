@@ -1,4 +1,5 @@
 from .encoder_processor_decoder import AnemoiModelEncProcDec
+from .ensemble import AnemoiEnsModelEncProcDec
 from .hierarchical import AnemoiModelEncProcDecHierarchical
 
-__all__ = ["AnemoiModelEncProcDec", "AnemoiModelEncProcDecHierarchical"]
+__all__ = ["AnemoiModelEncProcDec", "AnemoiEnsModelEncProcDec", "AnemoiModelEncProcDecHierarchical"]

@@ -75,6 +75,7 @@ class AnemoiModelEncProcDec(nn.Module):
             sub_graph=self._graph_data[(hidden, "to", hidden)],
             src_grid_size=self.node_attributes.num_nodes[hidden],
             dst_grid_size=self.node_attributes.num_nodes[hidden],
+            **self._processor_kwargs(model_config),
         )
         self.decoder = instantiate(
             model_config.model.decoder,
@@ -123,6 +124,14 @@ class AnemoiModelEncProcDec(nn.Module):
         from torch.utils.checkpoint import checkpoint
 
         return checkpoint(mapper, data, **kwargs, use_reentrant=use_reentrant)
+
+    def _processor_kwargs(self, model_config) -> dict:
+        """Further constructor arguments of the processor; none here (``models.ensemble``: the width of the condition)."""
+        return {}
+
+    def _processor_condition(self, batch_size: int, x_latent: Tensor) -> Optional[Tensor]:
+        """The per-row condition of the processor's LayerNorms for this call; none here (``models.ensemble`` draws noise)."""
+        return None
 
     def _prognostic_indices(self, device):
         key = str(device)
@@ -287,7 +296,9 @@ class AnemoiModelEncProcDec(nn.Module):
         # GraphTransformer forward mapper hands the RAW data input on to the decoder (reference layers/mapper.py:345);
         # the GNN forward mapper hands on its UPDATED source embedding (reference layers/mapper.py:522)
         x_data_latent, x_latent = (x_data, enc) if not isinstance(enc, tuple) else enc
-        x_proc = self.processor.native(x_latent, batch_size, node_map=inv)
+        cond = self._processor_condition(batch_size, x_latent)
+        x_proc = (self.processor.native(x_latent, batch_size, node_map=inv) if cond is None
+                  else self.processor.native(x_latent, batch_size, node_map=inv, cond=cond))
         x_latent_proc = ops.add(x_proc, x_latent)
         y = self.decoder.native(x_latent_proc, x_data_latent, batch_size, out_dtype=torch.float32, src_map=inv,
                                 **self._one_cols(self.decoder, None, one_data if x_data_latent is x_data else None))

@@ -1349,6 +1349,102 @@ def layer_norm_backward(x: Tensor, stats: Tensor, gamma: Tensor, dy: Tensor, dre
     return dx, dgamma, dbeta
 
 
+def _pad_k(t: Tensor, kp: int) -> Tensor:
+    """f32, contiguous, the last axis zero-padded to ``kp`` columns (the layout the conditional LayerNorm kernels read)."""
+    t = t.detach().float()
+    if t.shape[1] == kp:
+        return t.contiguous()
+    out = torch.zeros((t.shape[0], kp), dtype=torch.float32, device=t.device)
+    out[:, :t.shape[1]] = t
+    return out
+
+
+def _cond_ln_args(who: str, x: Tensor, cond: Tensor, w_scale: Tensor, w_bias: Tensor):
+    rows, c = _rows(x).shape
+    k = w_scale.shape[1]
+    if tuple(w_scale.shape) != (c, k) or tuple(w_bias.shape) != (c, k) or tuple(cond.shape) != (rows, k):
+        raise ValueError(f"{who}: x {tuple(x.shape)}, cond {tuple(cond.shape)} and the weights {tuple(w_scale.shape)} / "
+                         f"{tuple(w_bias.shape)} do not fit ([rows, C], [rows, K], [C, K])")
+    return rows, c, k
+
+
+def cond_layer_norm(x: Tensor, cond: Tensor, w_scale: Tensor, b_scale: Tensor, w_bias: Tensor, b_bias: Tensor,
+                    eps: float = 1e-5, with_stats: bool = False):
+    """``xhat * (1 + cond @ w_scale.T + b_scale) + (cond @ w_bias.T + b_bias)`` in one pass over ``x [rows, C]`` (f32 or bf16;
+    ``cond [rows, K]``, the weights ``[C, K]`` and the biases ``[C]`` are taken in f32), ``K <= 32`` -- a wider condition raises
+    ``NotImplementedError`` (``autograd.cond_layer_norm`` then composes the operation).  ``with_stats``: also the row
+    statistics ``[rows, 2]`` of :func:`row_stats`, for :func:`cond_layer_norm_backward`."""
+    _dev(x, cond, w_scale, b_scale, w_bias, b_bias)
+    rows, c, k = _cond_ln_args("cond_layer_norm", x, cond, w_scale, w_bias)
+    if k > _lib.COND_LN_MAX_K:
+        raise NotImplementedError(f"cond_layer_norm: K = {k} condition columns, at most {_lib.COND_LN_MAX_K} on the fused kernel")
+    kp = _lib.cond_ln_padded_k(k)
+    cond, w_scale, w_bias = (_pad_k(t, kp) for t in (cond, w_scale, w_bias))
+    b_scale, b_bias = (t.detach().float().contiguous() for t in (b_scale, b_bias))
+    y = torch.empty((rows, c), dtype=x.dtype, device=x.device)
+    stats = torch.empty((rows, 2), dtype=torch.float32, device=x.device) if with_stats else None
+    with _Timed("cond_layer_norm", bytes=2 * rows * c * x.element_size() + rows * k * 4, flops=4 * rows * c * k):
+        st = _lib.load().anemoi_cond_layer_norm(dtype_code(x.dtype), x.data_ptr(), _ld(x), cond.data_ptr(), kp, k,
+                                                w_scale.data_ptr(), kp, b_scale.data_ptr(), w_bias.data_ptr(), b_bias.data_ptr(),
+                                                y.data_ptr(), c, _ptr(stats), rows, c, eps, _stream())
+    _lib.check(st, "anemoi_cond_layer_norm")
+    return (y, stats) if with_stats else y
+
+
+def cond_layer_norm_backward(dy: Tensor, x: Tensor, stats: Tensor, cond: Tensor, w_scale: Tensor, b_scale: Tensor,
+                             w_bias: Tensor):
+    """``(dx, dcond, dw_scale, db_scale, dw_bias, db_bias)`` of :func:`cond_layer_norm` from the forward's statistics; everything
+    but ``dx`` in f32.  Deterministic (fixed row chunks, partials added in ascending order)."""
+    _dev(dy, x, stats, cond, w_scale, b_scale, w_bias)
+    rows, c, k = _cond_ln_args("cond_layer_norm_backward", x, cond, w_scale, w_bias)
+    if tuple(_rows(dy).shape) != (rows, c) or dy.dtype != x.dtype or tuple(stats.shape) != (rows, 2):
+        raise ValueError("cond_layer_norm_backward: shapes of x, dy, stats do not match")
+    if k > _lib.COND_LN_MAX_K:
+        raise NotImplementedError(f"cond_layer_norm_backward: K = {k} condition columns, at most {_lib.COND_LN_MAX_K}")
+    kp = _lib.cond_ln_padded_k(k)
+    cond, w_scale, w_bias = (_pad_k(t, kp) for t in (cond, w_scale, w_bias))
+    b_scale = b_scale.detach().float().contiguous()
+    dev = x.device
+    dx = torch.empty((rows, c), dtype=x.dtype, device=dev)
+    dcond = torch.empty((rows, k), dtype=torch.float32, device=dev)
+    dws, dwb = (torch.empty((c, k), dtype=torch.float32, device=dev) for _ in range(2))
+    dbs, dbb = (torch.empty(c, dtype=torch.float32, device=dev) for _ in range(2))
+    lib = _lib.load()
+    if rows == 0:
+        return dx, dcond, dws.zero_(), dbs.zero_(), dwb.zero_(), dbb.zero_()
+    n_ws = lib.anemoi_cond_layer_norm_backward_workspace_floats(rows, c, k)
+    ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=dev)
+    with _Timed("cond_layer_norm_backward", bytes=5 * rows * c * x.element_size() + 2 * rows * k * 4, flops=10 * rows * c * k):
+        st = lib.anemoi_cond_layer_norm_backward(dtype_code(x.dtype), dy.data_ptr(), _ld(dy), x.data_ptr(), _ld(x),
+                                                 stats.data_ptr(), cond.data_ptr(), kp, k, w_scale.data_ptr(), kp, b_scale.data_ptr(),
+                                                 w_bias.data_ptr(), dx.data_ptr(), c, dcond.data_ptr(), dws.data_ptr(),
+                                                 dbs.data_ptr(), dwb.data_ptr(), dbb.data_ptr(), rows, c, ws.data_ptr(), n_ws,
+                                                 _stream())
+    _lib.check(st, "anemoi_cond_layer_norm_backward")
+    return dx, dcond, dws, dbs, dwb, dbb
+
+
+def gaussian_noise(rows: int, k: int, std: float = 1.0, *, seed: int, seed_dev: Optional[Tensor] = None, device=None,
+                   out: Optional[Tensor] = None) -> Tensor:
+    """f32 ``[rows, k]`` of ``std * z``, ``z ~ N(0, 1)``: element ``i = row * k + col`` is a function of ``(seed + seed_dev[0], i)``
+    alone (Philox4x32-10 and Box-Muller, ``anemoi_gaussian_noise``), so the first ``n`` rows of a longer draw are the ``n``-row
+    draw.  ``seed_dev``: a device integer word the kernel adds to the seed (``runtime.DeviceDropout``: a captured step draws new
+    noise on every replay)."""
+    if out is None:
+        out = torch.empty((int(rows), int(k)), dtype=torch.float32,
+                          device=device if device is not None else (seed_dev.device if seed_dev is not None else "cuda"))
+    _dev(out)
+    if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (int(rows), int(k)):
+        raise ValueError("gaussian_noise: out must be contiguous float32 [rows, k]")
+    if out.numel() == 0:  # (torch hands out a null pointer for an empty tensor)
+        return out
+    with _Timed("gaussian_noise", bytes=out.numel() * 4):
+        st = _lib.load().anemoi_gaussian_noise(out.data_ptr(), int(rows), int(k), float(std), int(seed) & 0xFFFFFFFF,
+                                               _seed_dev_ptr(seed_dev, out), _stream())
+    _lib.check(st, "anemoi_gaussian_noise")
+    return out
+
+
 def weight_grad(dpre: Tensor, x: Tensor, k: int, want_bias: bool = False, transposed_route: bool = False,
                 out: Optional[Tensor] = None):
     """``dW [N, k] = dpre^T @ x[:, :k]`` in f32 (``dpre [M, N]``, ``x [M, >= k]`` in the compute dtype): the reduction

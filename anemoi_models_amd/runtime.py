@@ -977,6 +977,9 @@ class GraphedTrainStep:
     default is 0.1, ``layers/processor.py:99``): the captured step runs inside a :class:`DeviceDropout` context
     (``self.dropout``) whose ``advance()`` is the first captured operation, so every replay draws new masks from the step
     counter in device memory; ``self.dropout.counter`` may be read or set between replays (reproducibility, resume).
+    The same context is opened -- dropout or not, training mode or not -- for a model that holds a
+    ``layers.ensemble.NoiseConditioning`` with ``inject_noise`` (the ensemble model): its Gaussian noise takes the step's device
+    word the same way, so every replay draws new noise.  A model with neither has ``self.dropout = None``, as before.
 
     Side effects worth knowing: the ``warmup`` eager steps are REAL steps on ``example_x`` -- with an ``optimizer`` they
     update the parameters and the optimizer state (torch's capture recipe needs the optimizer's state initialised; pass
@@ -992,7 +995,12 @@ class GraphedTrainStep:
         self.model, self.loss_fn, self.optimizer = model, loss_fn, optimizer
         self.static_x, self.static_target = example_x.clone(), example_target.clone()
         self._config = self._dropout_config()
-        self.dropout = DeviceDropout(example_x.device) if model.training and any(p > 0.0 for p in self._config[1]) else None
+        # device-side seeds: attention dropout in training mode, and the noise of an ensemble model (training mode or not)
+        from .layers.ensemble import NoiseConditioning
+
+        noisy = any(isinstance(m, NoiseConditioning) and m.inject_noise for m in model.modules())
+        self.dropout = DeviceDropout(example_x.device) if (model.training and any(p > 0.0 for p in self._config[1])) or noisy \
+            else None
         params = [p for p in model.parameters() if p.requires_grad]
 
         def zero():

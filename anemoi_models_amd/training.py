@@ -393,31 +393,41 @@ def gnn_mapper(mapper, x_src: Tensor, x_dst: Tensor, batch_size: int, src_map: O
 
 
 # ------------------------------------------------------------------------------------------------ Transformer
-def transformer_block(block, x: Tensor, batch_size: int) -> Tensor:
+def _block_norm(norm, x: Tensor, cond: Optional[Tensor]) -> Tensor:
+    """``nn.LayerNorm`` or, with ``cond``, ``layers.normalization.ConditionalLayerNorm`` (its autograd route)."""
+    if cond is None:
+        return autograd.layer_norm(x, norm.weight, norm.bias, norm.eps)
+    return autograd.cond_layer_norm(x, cond, norm.scale.weight, norm.scale.bias, norm.bias.weight, norm.bias.bias, norm.eps)
+
+
+def transformer_block(block, x: Tensor, batch_size: int, cond: Optional[Tensor] = None) -> Tensor:
     """``TransformerProcessorBlock.forward`` (reference layers/block.py:99-105): ``x + proj(attn(qkv(LN x)))``, then
-    ``x + MLP(LN x)``."""
+    ``x + MLP(LN x)``.  ``cond``: the condition of a block built with ``cond_dim`` (both LayerNorms conditional)."""
+    if (cond is None) != (getattr(block, "cond_dim", None) is None):
+        raise ValueError("transformer_block: `cond` goes with the block's cond_dim")
     dtype = runtime.compute_dtype(x)
     att = block.attention
     x = _cast(x, dtype)
-    h = autograd.layer_norm(x, block.layer_norm1.weight, block.layer_norm1.bias, block.layer_norm1.eps)
+    h = _block_norm(block.layer_norm1, x, cond)
     qkv = autograd.linear(h, att.lin_qkv.weight, att.lin_qkv.bias)
     p, seed, seed_dev = att.dropout()  # attention dropout in training mode (reference layers/attention.py:90)
     a = autograd.mhsa(qkv, batch_size, att.num_heads, att.attention_window(), p, seed, seed_dev=seed_dev)
     x = autograd.linear(a, att.projection.weight, att.projection.bias, "Identity", x)
-    h = autograd.layer_norm(x, block.layer_norm2.weight, block.layer_norm2.bias, block.layer_norm2.eps)
+    h = _block_norm(block.layer_norm2, x, cond)
     return sequential(block.mlp, h, residual=x)
 
 
-def transformer_processor(proc, x: Tensor, batch_size: int) -> Tensor:
-    """``TransformerProcessor.forward`` (reference layers/processor.py:103-137): checkpointed chunks of blocks."""
-    def run_chunk(chunk, h):
+def transformer_processor(proc, x: Tensor, batch_size: int, cond: Optional[Tensor] = None) -> Tensor:
+    """``TransformerProcessor.forward`` (reference layers/processor.py:103-137): checkpointed chunks of blocks.  ``cond`` is an
+    argument of the checkpointed region: the recomputation sees the tensor the forward saw."""
+    def run_chunk(chunk, h, c):
         for blk in chunk.blocks:
-            h = transformer_block(blk, h, batch_size)
+            h = transformer_block(blk, h, batch_size, c)
         return h
 
     h = _cast(x, runtime.compute_dtype(x))
     for chunk in proc.proc:
-        h = _checkpoint(run_chunk, chunk, h)
+        h = _checkpoint(run_chunk, chunk, h, cond)
     return h
 
 
@@ -574,7 +584,9 @@ def model_forward(model, x: Tensor) -> Tensor:
 
         x_data_latent, x_latent = _checkpoint(lambda a, c: run_mapper(model.encoder, a, c, None, inv), x_data, x_hidden)
         if inv is None:
-            x_proc = model.processor(x_latent, rows, shapes)
+            cond = model._processor_condition(rows, x_latent)  # (None but for the ensemble model: its noise embedding)
+            x_proc = model.processor(x_latent, rows, shapes) if cond is None else model.processor(x_latent, rows, shapes,
+                                                                                                   cond=cond)
         elif isinstance(model.processor, GraphTransformerProcessor):
             x_proc = gt_processor(model.processor, x_latent, rows, inv)
         else:

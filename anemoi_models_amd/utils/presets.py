@@ -20,7 +20,9 @@ BASELINE_CONFIGS = {
 
 def model_config(processor: str = "GraphTransformer", channels: int = 64, layers: int = 4, heads: int = 16,
                  multistep: int = 2, trainable: int = 8, proc_chunks: int = 2, window_size: int = 512,
-                 mappers: str = "GraphTransformer") -> DotDict:
+                 mappers: str = "GraphTransformer", noise_injector=None) -> DotDict:
+    """``noise_injector`` (a dict ``noise_std`` / ``noise_channels_dim`` / ``noise_mlp_hidden_dim`` [/ ``inject_noise``]): the
+    ``model.noise_injector`` entry ``models.AnemoiEnsModelEncProcDec`` is built from."""
     common = {"sub_graph_edge_attributes": EDGE_ATTRS, "trainable_size": trainable}
     mapper = {"activation": "GELU", "num_chunks": 1, "mlp_hidden_ratio": 4, "num_heads": heads, **common}
     procs = {
@@ -44,19 +46,16 @@ def model_config(processor: str = "GraphTransformer", channels: int = 64, layers
         gm = {"activation": "SiLU", "num_chunks": 1, "mlp_extra_layers": 0, **common}
         enc = {"_target_": "anemoi.models.layers.mapper.GNNForwardMapper", **gm}
         dec = {"_target_": "anemoi.models.layers.mapper.GNNBackwardMapper", **gm}
-    return DotDict(
-        {
-            "graph": {"data": "data", "hidden": "hidden"},
-            "training": {"multistep_input": multistep},
-            "model": {
-                "num_channels": channels,
-                "trainable_parameters": {"data": trainable, "hidden": trainable},
-                "encoder": enc,
-                "processor": procs[processor],
-                "decoder": dec,
-            },
-        }
-    )
+    model = {
+        "num_channels": channels,
+        "trainable_parameters": {"data": trainable, "hidden": trainable},
+        "encoder": enc,
+        "processor": procs[processor],
+        "decoder": dec,
+    }
+    if noise_injector is not None:
+        model["noise_injector"] = dict(noise_injector)
+    return DotDict({"graph": {"data": "data", "hidden": "hidden"}, "training": {"multistep_input": multistep}, "model": model})
 
 
 def hierarchical_model_config(channels: int = 64, heads: int = 16, hidden=("hidden_1", "hidden_2"),

@@ -530,6 +530,50 @@ int anemoi_ensemble_score_backward(int kind, float alpha, const float* pred, con
                                    const float* mask, const float* diff_scale, float scale, const float* upstream,
                                    float* dpred, anemoi_stream_t stream);
 
+/*
+ * Conditional LayerNorm (the processor LayerNorm of an ensemble model: scale and shift are linear in a per-row condition):
+ *   y[r, c] = xhat[r, c] * (1 + cond[r, :] . Ws[c, :] + bs[c]) + (cond[r, :] . Wb[c, :] + bb[c])
+ * x, y: [rows, C] in `dtype` (f32 or bf16); cond: f32 [rows, K] with leading dimension ldc; Ws, Wb: f32 [C, K] (an
+ * nn.Linear(K, C).weight) with leading dimension ldw; bs, bb: f32 [C].  The caller pads K to KP = 4, 8, 16 or 32 columns
+ * (the next of these): ldc, ldw >= KP and multiples of 4, cond / Ws / Wb 16-byte aligned (ANEMOI_ERR_INVALID otherwise),
+ * columns K .. KP - 1 zero (the contents are the caller's) -- the kernels read KP columns with 16-byte loads and have one
+ * code path per KP.  xhat = (x - mean) * rstd with the statistics of anemoi_layer_norm -- the same order of every sum: with
+ * zero weights y is bit for bit anemoi_layer_norm(gamma = 1, beta = 0) -- and stats[r] = { rstd_r, -mean_r * rstd_r } as
+ * anemoi_row_stats leaves them (stats may be NULL).  Neither [rows, C] product exists in memory.  1 <= K <= 32 (K < 1:
+ * ANEMOI_ERR_INVALID; K > 32: ANEMOI_ERR_UNSUPPORTED, the caller composes the operation from a Linear and a LayerNorm); every
+ * C of anemoi_layer_norm.
+ */
+int anemoi_cond_layer_norm(int dtype, const void* x, int64_t ldx, const float* cond, int64_t ldc, int K, const float* Ws,
+                           int64_t ldw, const float* bs, const float* Wb, const float* bb, void* y, int64_t ldy, float* stats,
+                           int64_t rows, int C, float eps, anemoi_stream_t stream);
+
+/*
+ * Its backward.  With ds = dy * xhat and g = dy * (1 + s):
+ *   dx = rstd * (g - mean_c(g) - xhat * mean_c(g * xhat))       dcond[r, k] = sum_c ds * Ws[c, k] + dy * Wb[c, k]
+ *   dWs[c, k] = sum_r ds * cond[r, k]    dbs[c] = sum_r ds      dWb[c, k] = sum_r dy * cond[r, k]    dbb[c] = sum_r dy
+ * (dx in `dtype`, everything else f32; cond, Ws, Wb padded as in the forward; dcond [rows, K], dWs and dWb [C, K] contiguous).
+ * Deterministic, no atomics: the column sums are taken over fixed chunks of rows, one [2 K + 2, C] partial per chunk in
+ * `workspace` (anemoi_cond_layer_norm_backward_workspace_floats(rows, C, K) floats; the chunks are a function of `rows`
+ * alone), and added in ascending chunk order.
+ */
+int64_t anemoi_cond_layer_norm_backward_workspace_floats(int64_t rows, int C, int K);
+int anemoi_cond_layer_norm_backward(int dtype, const void* dy, int64_t ldd, const void* x, int64_t ldx, const float* stats,
+                                    const float* cond, int64_t ldc, int K, const float* Ws, int64_t ldw, const float* bs,
+                                    const float* Wb, void* dx, int64_t ldo, float* dcond, float* dWs, float* dbs, float* dWb,
+                                    float* dbb, int64_t rows, int C, float* workspace, int64_t workspace_floats,
+                                    anemoi_stream_t stream);
+
+/*
+ * out[rows, K] (f32, contiguous) = std * z, z ~ N(0, 1), counter-based: element i = row * K + k is a function of
+ * (seed + *seed_dev, i) alone, whatever `rows` and the launch.  Philox4x32-10 with counter (i / 4, (i / 4) >> 32, 0, 0) and
+ * key (seed + *seed_dev, 0x6E6F6973) yields the words w0..w3 of the elements 4 q .. 4 q + 3; a pair (wa, wb) gives
+ *   u1 = ((wa >> 8) + 1) / 2^24,  u2 = (wb >> 8) / 2^24,  (z, z') = sqrt(-2 ln u1) * (cos 2 pi u2, sin 2 pi u2)
+ * -- (w0, w1) the elements 4 q and 4 q + 1, (w2, w3) the next two -- so |z| <= sqrt(48 ln 2) ~ 5.77.  `seed_dev`: NULL or a
+ * device word added to the seed by the kernel (what a captured training step advances, as for the dropout kernels).
+ */
+int anemoi_gaussian_noise(float* out, int64_t rows, int K, float std, uint32_t seed, const void* seed_dev,
+                          anemoi_stream_t stream);
+
 /* dtype conversion / K-padding copy: dst[r, 0:cols] = src[r, 0:cols], dst[r, cols:ld_dst] = 0. */
 int anemoi_convert_pad(int src_dtype, const void* src, int64_t ld_src, int dst_dtype, void* dst, int64_t ld_dst,
                        int64_t rows, int cols, anemoi_stream_t stream);
