@@ -49,7 +49,7 @@ def cond_ln_padded_k(k: int) -> int:
     return 4 if k <= 4 else (8 if k <= 8 else (16 if k <= 16 else 32))
 
 
-ABI_VERSION = 51
+ABI_VERSION = 52
 
 
 class GtBlockArgs(ctypes.Structure):
@@ -195,6 +195,9 @@ SIGNATURES = {
                                                c_void_p]),
     "anemoi_prognostic_residual_backward": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int,
                                                     c_void_p, c_void_p]),
+    "anemoi_csr_project": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int,
+                                   c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                   c_void_p, c_int, c_void_p]),
     "anemoi_weighted_mse_workspace_floats": (c_int64, [c_int64, c_int]),
     "anemoi_weighted_mse": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_float,
                                     c_void_p, c_void_p, c_int64, c_void_p]),

@@ -1382,6 +1382,48 @@ def advance_input(x: Tensor, y: Tensor, colmap: Tensor, forcing: Optional[Tensor
     return _AdvanceInput.apply(x.float().contiguous(), y.float().contiguous(), colmap, f)
 
 
+class _TruncatedResidual(torch.autograd.Function):
+    """``y = float(out)`` with ``y[..., out_idx] += A_up (A_down x[:, -1, ..., in_idx])`` on ``anemoi_csr_project`` (two launches,
+    one per matrix, straight out of ``x`` and into ``y``); backward on the same kernel with the transposed matrices.  Where
+    torch composes this from an index_select, two sparse products per batch entry and an index-add -- a coalesce and atomic
+    accumulation in the backward, allocations inside the products -- every element here is owned by one thread."""
+
+    @staticmethod
+    def forward(ctx, out: Tensor, x: Tensor, dev, out_idx: Tensor, in_idx: Tensor, shape):
+        from .layers.truncation import project_add
+
+        y = torch.empty(shape, dtype=torch.float32, device=out.device)  # (a tensor of its own: boundings write in place)
+        y.view(out.shape).copy_(out)
+        project_add(y, x[:, -1], dev, out_idx, in_idx)
+        ctx.out_shape, ctx.out_dtype, ctx.x_shape = out.shape, out.dtype, tuple(x.shape)
+        ctx.dev, ctx.out_idx, ctx.in_idx = dev, out_idx, in_idx
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g: Tensor):
+        from .layers.truncation import project_add_backward
+
+        dx = None
+        if ctx.needs_input_grad[1]:
+            dx = project_add_backward(g.float().contiguous(), ctx.dev, ctx.out_idx, ctx.in_idx, ctx.x_shape)
+        return g.reshape(ctx.out_shape).to(ctx.out_dtype), dx, None, None, None, None
+
+
+def truncated_residual(out: Tensor, x: Tensor, plan, out_idx: Tensor, in_idx: Tensor, shape, cache: Optional[dict] = None) -> Tensor:
+    """The truncated skip connection, differentiable: ``y = float(out).view(shape)``, then ``y[..., out_idx] += A_up (A_down
+    x[:, -1, ..., in_idx])`` with the matrices of ``plan`` (``layers.truncation.TruncationPlan``); ``x`` f32 ``[B, T, Ens, G, V_in]``,
+    ``shape = (B, Ens, G, V_out)``, ``out_idx`` / ``in_idx`` int32 on the device (the prognostic columns; only they are
+    projected).  The gradient of ``out`` is the incoming one; ``x`` receives ``dx[:, -1, ..., in_idx] = A_down^T (A_up^T dy[...,
+    out_idx])``, zeros elsewhere, when it requires one.  ``cache``: where the plan keeps its device copies (a model's ``_idx_cache``)."""
+    if x.dtype != torch.float32 or x.dim() != 5:
+        raise ValueError(f"truncated_residual: x must be float32 [B, T, Ens, G, V_in], got {tuple(x.shape)} {x.dtype}")
+    if tuple(shape[:3]) != (x.shape[0], x.shape[2], x.shape[3]) or x.shape[3] != plan.grid_size:
+        raise ValueError(f"truncated_residual: output shape {tuple(shape)} / plan grid {plan.grid_size} do not belong to x "
+                         f"{tuple(x.shape)}")
+    return _TruncatedResidual.apply(out, x, plan.on(x.device, cache), out_idx, in_idx, tuple(shape))
+
+
 class _WeightedMSE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred: Tensor, target: Tensor, row_w: Tensor, col_w: Tensor, mask: Optional[Tensor], scale: float):

@@ -366,12 +366,21 @@ def gather_output_rows(sp: "ShardPlan", y_local: Tensor, group, grid: int) -> Te
     return gathered.index_select(0, _gather_positions(sp, grid, y_local.device))
 
 
+def _refuse_truncation(model) -> None:
+    """A model with a truncated skip connection is refused before any plan is built: the projection is not row-local."""
+    if getattr(model, "_truncation", None) is not None:
+        from ..layers.truncation import REFUSAL
+
+        raise NotImplementedError(REFUSAL)
+
+
 def sharded_forward(model, x: Tensor, group, input_affine=None, output_affine=None, local_output: bool = False):
     """Full-input / full-output forward with the mesh partitioned over ``group`` (batch size 1, as in the reference).
 
     ``local_output=True`` (rollout with the state kept sharded, :func:`advance_sharded_state`): the final all-gather is
     skipped and ``(y_local [rows, V_out] f32 WITHOUT the prognostic residual, shard plan)`` is returned; of ``x`` only
     the grid rows this rank's encoder and decoder read (``enc_src_ids``, ``dec_dst_ids``) need to be valid."""
+    _refuse_truncation(model)
     if torch.is_grad_enabled() and any(p.requires_grad for p in model.parameters()):
         if input_affine is not None or output_affine is not None:
             raise NotImplementedError("input_affine / output_affine belong to the inference interface (predict_step)")
@@ -530,6 +539,7 @@ def sharded_training_forward(model, x: Tensor, group) -> Tensor:
     from ..layers.processor import GNNProcessor
     from ..layers.processor import GraphTransformerProcessor
 
+    _refuse_truncation(model)
     gt_maps = isinstance(model.encoder, GraphTransformerBaseMapper) and isinstance(model.decoder, GraphTransformerBaseMapper)
     gnn_maps = isinstance(model.encoder, GNNBaseMapper) and isinstance(model.decoder, GNNBaseMapper)
     from ..layers.processor import TransformerProcessor

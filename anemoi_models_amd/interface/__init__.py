@@ -15,7 +15,9 @@ from ..preprocessing import Processors
 
 class AnemoiModelInterface(torch.nn.Module):
     def __init__(self, *, config, graph_data, statistics: dict, data_indices, metadata: dict,
-                 supporting_arrays: dict = None) -> None:
+                 supporting_arrays: dict = None, truncation_data: dict = None) -> None:
+        """``truncation_data``: ``{"down": A_down, "up": A_up}`` of the truncated skip connection, handed to the model as current
+        anemoi-models does (``layers.truncation``); ``None``: the model is built without the argument, as before."""
         super().__init__()
         self.config = config
         self.id = str(uuid.uuid4())
@@ -25,6 +27,7 @@ class AnemoiModelInterface(torch.nn.Module):
         self.metadata = metadata
         self.supporting_arrays = supporting_arrays if supporting_arrays is not None else {}
         self.data_indices = data_indices
+        self.truncation_data = truncation_data
         self._build_model()
 
     def _build_model(self) -> None:
@@ -34,8 +37,9 @@ class AnemoiModelInterface(torch.nn.Module):
         ]
         self.pre_processors = Processors(processors)
         self.post_processors = Processors(processors, inverse=True)
+        extra = {} if not self.truncation_data else {"truncation_data": self.truncation_data}
         self.model = instantiate(self.config.model.model, model_config=self.config, data_indices=self.data_indices,
-                                 graph_data=self.graph_data, _recursive_=False)
+                                 graph_data=self.graph_data, _recursive_=False, **extra)
         self.forward = self.model.forward
 
     def predict_step(self, batch: torch.Tensor) -> torch.Tensor:

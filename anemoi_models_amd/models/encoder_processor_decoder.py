@@ -21,6 +21,7 @@ from torch import nn
 from .. import ops
 from .. import runtime
 from ..layers.graph import NamedNodesAttributes
+from ..layers.truncation import project_add
 
 try:  # real hydra when available, otherwise the local minimal implementation
     from hydra.utils import instantiate as _hydra_instantiate  # type: ignore
@@ -43,7 +44,10 @@ def instantiate(cfg, **kwargs):
 class AnemoiModelEncProcDec(nn.Module):
     """Encoder - processor - decoder graph network on MI355X kernels."""
 
-    def __init__(self, *, model_config, data_indices, graph_data) -> None:
+    def __init__(self, *, model_config, data_indices, graph_data, truncation_data=None) -> None:
+        """``truncation_data`` (keyword-only, as in current anemoi-models): ``{"down": A_down, "up": A_up}``, the sparse matrices
+        of the truncated skip connection ``x_skip = A_up (A_down x[:, -1])`` in any form ``layers.truncation.canonical_csr``
+        takes; ``None`` / ``{}``: the untruncated residual, exactly as without the argument."""
         super().__init__()
         self._graph_data = graph_data
         self._graph_name_data = model_config.graph.data
@@ -94,6 +98,17 @@ class AnemoiModelEncProcDec(nn.Module):
             ]
         )
         self._idx_cache: dict = {}
+        self._set_truncation(truncation_data)
+
+    def _set_truncation(self, truncation_data) -> None:
+        """The plan of the truncated skip connection: a plain attribute (no parameters, no buffers -- the ``state_dict`` is
+        that of the model without it); ``None`` without matrices."""
+        from ..layers.truncation import TruncationPlan
+
+        plan = TruncationPlan(truncation_data, grid_size=self.node_attributes.num_nodes[self._graph_name_data])
+        if plan and len(set(torch.as_tensor(self._internal_input_idx).tolist())) != len(self._internal_input_idx):
+            raise ValueError("truncation_data: the prognostic input columns repeat (the input gradient stores each column once)")
+        self._truncation = plan if plan else None
 
     def _calculate_shapes_and_indices(self, data_indices) -> None:
         self.num_input_channels = len(data_indices.internal_model.input)
@@ -192,18 +207,36 @@ class AnemoiModelEncProcDec(nn.Module):
         only those nodes' rows ``[1, 1, len(rows), V_out]`` -- every step here is row-local, so a rank of a node-partitioned
         run finishes the rows it decoded before they are all-gathered."""
         key = ("residual_src", str(y.device))
-        if key not in self._idx_cache:
+        out_dtype = x.dtype
+        truncation = getattr(self, "_truncation", None)
+        if truncation is not None:
+            # truncated skip connection: y += A_up (A_down x') on the raw x (input affine on load), two launches straight out
+            # of x and into y; the rest of this function then runs with a column map that adds nothing
+            if rows is not None:
+                from ..layers.truncation import REFUSAL
+
+                raise NotImplementedError(REFUSAL)
+            o_idx, i_idx = self._prognostic_indices(y.device)
+            x_last = x[:, -1] if x.dtype == torch.float32 else x[:, -1].float()
+            project_add(y, x_last, truncation.on(y.device, self._idx_cache), o_idx, i_idx, input_affine)
+            key = ("no_residual_src", str(y.device))
+            if key not in self._idx_cache:
+                self._idx_cache[key] = torch.full((self.num_output_channels,), -1, dtype=torch.int32, device=y.device)
+            # finalize_output reads no element of its x under this map, only its shape: y itself stands in (contiguous f32,
+            # so nothing is copied or cast -- a slice of the state would be, once per step, for B > 1 or a non-f32 state)
+            x, input_affine = y.view(y.shape[0], 1, y.shape[1], y.shape[2], y.shape[3]), None
+        elif key not in self._idx_cache:
             src = torch.full((self.num_output_channels,), -1, dtype=torch.int32)
             src[torch.as_tensor(self._internal_output_idx).long()] = torch.as_tensor(self._internal_input_idx).to(torch.int32)
             self._idx_cache[key] = src.to(y.device)
         if len(self.boundings) == 0:
             ops.finalize_output(y, x, self._idx_cache[key], input_affine, output_affine, rows=rows)
-            return y if y.dtype == x.dtype else y.to(x.dtype)
+            return y if y.dtype == out_dtype else y.to(out_dtype)
         plan = self._bounding_plan(y.device, output_affine)
         if plan is None:  # a bounding class this package does not know: call the modules, as the reference does
             ops.finalize_output(y, x, self._idx_cache[key], input_affine, None, rows=rows)
-            if y.dtype != x.dtype:
-                y = y.to(x.dtype)
+            if y.dtype != out_dtype:
+                y = y.to(out_dtype)
             for bounding in self.boundings:
                 y = bounding(y)
             if output_affine is not None:  # boundings act on the normalised output: de-normalise after them
@@ -214,7 +247,7 @@ class AnemoiModelEncProcDec(nn.Module):
         op_lists, masked_affine, fin = plan
         ops.finalize_output(y, x, self._idx_cache[key], input_affine, masked_affine, rows=rows)
         ops.bound_output(y, *op_lists, fin=fin)
-        return y if y.dtype == x.dtype else y.to(x.dtype)
+        return y if y.dtype == out_dtype else y.to(out_dtype)
 
     def _bounding_plan(self, device, output_affine):
         """Device-side op list of ``self.boundings`` (cached per device and output affine), ``None`` for unknown classes."""
@@ -263,6 +296,10 @@ class AnemoiModelEncProcDec(nn.Module):
         if model_comm_group is not None and model_comm_group.size() > 1:
             from ..distributed.partition import sharded_forward
 
+            if getattr(self, "_truncation", None) is not None:
+                from ..layers.truncation import REFUSAL
+
+                raise NotImplementedError(REFUSAL)
             return sharded_forward(self, x, model_comm_group, input_affine=input_affine, output_affine=output_affine)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             return self._training_forward(x, input_affine, output_affine)

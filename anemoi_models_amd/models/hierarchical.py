@@ -24,7 +24,7 @@ from .encoder_processor_decoder import instantiate
 class AnemoiModelEncProcDecHierarchical(AnemoiModelEncProcDec):
     """Message passing hierarchical graph network on MI355X kernels."""
 
-    def __init__(self, *, model_config, data_indices, graph_data) -> None:
+    def __init__(self, *, model_config, data_indices, graph_data, truncation_data=None) -> None:
         nn.Module.__init__(self)
         self._graph_data = graph_data
         self._graph_name_data = model_config.graph.data
@@ -113,6 +113,7 @@ class AnemoiModelEncProcDecHierarchical(AnemoiModelEncProcDec):
             ]
         )
         self._idx_cache: dict = {}
+        self._set_truncation(truncation_data)  # (the truncated skip connection of the shared ``_finish``)
 
     def forward(self, x: Tensor, model_comm_group=None) -> Tensor:
         if model_comm_group is not None and model_comm_group.size() > 1:

@@ -956,6 +956,114 @@ def prognostic_residual_backward(dy: Tensor, src: Tensor, shape) -> Tensor:
     return dx
 
 
+def csr_transpose(indptr, idx, val, n_cols: int):
+    """``(indptr, idx, val)`` of the transpose of a CSR matrix with ``n_cols`` columns, built on the HOST (CPU tensors in and
+    out; int64 / int32 / the dtype of ``val``) by a stable counting sort over the column index: every transposed row lists its
+    entries in ascending source-row order -- the order in which :func:`csr_project` adds them.  Runs once per matrix."""
+    indptr = torch.as_tensor(indptr).to(device="cpu", dtype=torch.int64)
+    idx = torch.as_tensor(idx).to(device="cpu", dtype=torch.int64)
+    val = torch.as_tensor(val).to(device="cpu")
+    n_rows, n_cols = indptr.numel() - 1, int(n_cols)
+    if n_rows < 0 or n_cols < 0 or idx.numel() != val.numel() or (n_rows >= 0 and int(indptr[-1]) != idx.numel()):
+        raise ValueError("csr_transpose: indptr / idx / val do not describe one CSR matrix")
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n_cols):
+        raise ValueError(f"csr_transpose: column index out of range [0, {n_cols})")
+    rows = torch.repeat_interleave(torch.arange(n_rows, dtype=torch.int64), indptr[1:] - indptr[:-1])
+    order = torch.argsort(idx, stable=True)  # (rows ascend along the CSR: a stable sort by column keeps them ascending)
+    t_indptr = torch.zeros(n_cols + 1, dtype=torch.int64)
+    t_indptr[1:] = torch.cumsum(torch.bincount(idx, minlength=n_cols), 0)
+    return t_indptr, rows[order].to(torch.int32), val[order].contiguous()
+
+
+_CHECKED_COLUMNS: set = set()
+
+
+def _check_columns(name: str, cols: Optional[Tensor], width: int, unique: bool) -> None:
+    """Values of a column list inside ``[0, width)`` (and, for the output side, without repeats: two lanes on one element would
+    end the one-owner property).  Reading a device list back synchronises, so a list is checked once -- remembered by its
+    storage, version and the width -- and never while its stream is capturing (warm-up calls come first)."""
+    if cols is None:
+        return
+    key = (cols.data_ptr(), cols._version, cols.numel(), int(width), unique, str(cols.device))
+    if key in _CHECKED_COLUMNS or (cols.is_cuda and torch.cuda.is_current_stream_capturing()):
+        return
+    host = cols.detach().cpu()
+    if host.numel() and (int(host.min()) < 0 or int(host.max()) >= width):
+        raise ValueError(f"csr_project: {name} holds a column outside [0, {width})")
+    if unique and torch.unique(host).numel() != host.numel():
+        raise ValueError(f"csr_project: {name} repeats a column (every output element is owned by one thread)")
+    if len(_CHECKED_COLUMNS) > 4096:
+        _CHECKED_COLUMNS.clear()
+    _CHECKED_COLUMNS.add(key)
+
+
+def _byte_span(t: Tensor):
+    """[first, last + 1) byte addresses that the elements of a (strided) tensor lie in."""
+    if t.numel() == 0:
+        return 0, 0
+    reach = sum((n - 1) * abs(st) for n, st in zip(t.shape, t.stride()))
+    return t.data_ptr(), t.data_ptr() + (reach + 1) * t.element_size()
+
+
+def csr_project(x: Tensor, out: Tensor, indptr: Tensor, idx: Tensor, val: Tensor, cols_in: Optional[Tensor] = None,
+                cols_out: Optional[Tensor] = None, in_affine=None, accumulate: bool = False, p: Optional[int] = None) -> Tensor:
+    """``out[a, b, i, cols_out[q]] (= or +=) sum_k val[k] * x'[a, b, idx[k], cols_in[q]]`` over the entries ``k`` of CSR row ``i``
+    (``anemoi_csr_project``), for ``q < P``.  ``x`` ``[A, B, n_in, W_in]`` and ``out`` ``[A, B, n_out, W_out]`` are f32 with
+    unit-stride columns; the other dimensions may be strided views (a time slice of the state, a transposed ensemble view).
+    ``indptr`` int64 ``[n_out + 1]``, ``idx`` int32, ``val`` f32; ``cols_in`` / ``cols_out`` int32 ``[P]`` or ``None`` (the
+    identity ``0..P-1``; ``P`` then comes from the other list, from ``p``, or is the width of ``x``).  ``in_affine = (mul, add)``
+    per INPUT column: ``x' = x * mul + add``.  Checked here: shapes, dtypes, strides, the values of ``cols_in`` / ``cols_out``
+    (inside the widths; ``cols_out`` without repeats; each list once, see :func:`_check_columns`) and that ``x`` and ``out`` do not
+    overlap.  NOT checked here: the values of ``idx`` (``< n_in``) and ``indptr`` -- ``layers.truncation`` checks them once on the
+    host when it builds a plan, and a caller with matrices of its own must do the same.  Returns ``out``."""
+    _dev(x, out, indptr, idx, val, cols_in, cols_out)
+    if x.dim() != 4 or out.dim() != 4 or x.dtype != torch.float32 or out.dtype != torch.float32:
+        raise ValueError(f"csr_project: x and out must be float32 [A, B, rows, columns], got {tuple(x.shape)} {x.dtype} and "
+                         f"{tuple(out.shape)} {out.dtype}")
+    if tuple(x.shape[:2]) != tuple(out.shape[:2]):
+        raise ValueError(f"csr_project: slab dimensions differ, {tuple(x.shape[:2])} and {tuple(out.shape[:2])}")
+    if (x.shape[3] > 1 and x.stride(3) != 1) or (out.shape[3] > 1 and out.stride(3) != 1):
+        raise ValueError("csr_project: the columns of x and out must have unit stride")
+    n_in, n_out = x.shape[2], out.shape[2]
+    if (indptr.dtype != torch.int64 or idx.dtype != torch.int32 or val.dtype != torch.float32 or indptr.numel() != n_out + 1
+            or idx.numel() != val.numel() or not (indptr.is_contiguous() and idx.is_contiguous() and val.is_contiguous())):
+        raise ValueError("csr_project: indptr int64 [n_out + 1], idx int32 and val float32 of one length, all contiguous")
+    for name, c in (("cols_in", cols_in), ("cols_out", cols_out)):
+        if c is not None and (c.dtype != torch.int32 or c.dim() != 1 or not c.is_contiguous()):
+            raise ValueError(f"csr_project: {name} must be a contiguous 1-d int32 tensor")
+    counts = {int(c.numel()) for c in (cols_in, cols_out) if c is not None} | ({int(p)} if p is not None else set())
+    if len(counts) > 1:
+        raise ValueError(f"csr_project: column counts differ: {sorted(counts)}")
+    n_p = counts.pop() if counts else int(x.shape[3])
+    if n_p <= 0 or (cols_in is None and n_p > x.shape[3]) or (cols_out is None and n_p > out.shape[3]):
+        raise ValueError(f"csr_project: P = {n_p} columns do not fit x / out of widths {x.shape[3]} / {out.shape[3]}")
+    _check_columns("cols_in", cols_in, x.shape[3], unique=False)
+    _check_columns("cols_out", cols_out, out.shape[3], unique=True)
+    (x0, x1), (o0, o1) = _byte_span(x), _byte_span(out)
+    if x0 < o1 and o0 < x1:
+        raise ValueError("csr_project: x and out overlap in memory")
+    mul = add = None
+    if in_affine is not None:
+        mul, add = (t_.contiguous().float() for t_ in in_affine)
+        _dev(mul, add)
+        if mul.numel() != x.shape[3] or add.numel() != x.shape[3]:
+            raise ValueError("csr_project: in_affine needs one (mul, add) pair per column of x")
+    if out.numel() == 0:
+        return out
+    if idx.numel() == 0:  # no entries at all: nothing to add; the store writes its zeros (two words the kernel never reads
+        if accumulate:    # stand in for the empty arrays, whose pointers are null)
+            return out
+        idx, val = torch.zeros(1, dtype=torch.int32, device=out.device), torch.zeros(1, dtype=torch.float32, device=out.device)
+    ldx = max(x.stride(2), x.shape[3]) if n_in <= 1 else x.stride(2)
+    ldo = max(out.stride(2), out.shape[3]) if n_out <= 1 else out.stride(2)
+    st = _lib.load().anemoi_csr_project(x.data_ptr(), ldx, x.stride(0), x.stride(1), out.data_ptr(), ldo, out.stride(0),
+                                        out.stride(1), out.shape[0], out.shape[1], n_in, n_out, indptr.data_ptr(),
+                                        idx.data_ptr(), val.data_ptr(), _ptr(cols_in), _ptr(cols_out), n_p, _ptr(mul), _ptr(add),
+                                        int(bool(accumulate)), _stream())
+    _lib.check(st, "anemoi_csr_project")
+    return out
+
+
 def _wmse_args(who: str, pred: Tensor, target: Tensor, row_w: Tensor, col_w: Tensor, mask: Optional[Tensor]):
     _dev(pred, target, row_w, col_w, mask)
     _rows(pred)

@@ -52,9 +52,10 @@ _ROLLOUT_INPUT_GRAD = False
 @contextlib.contextmanager
 def rollout_input_grad():
     """Inside this context ``model_forward`` / ``_finish`` keep the one-pass I/O kernels (:class:`_AssembleNodes`,
-    :class:`_PrognosticResidual`) for an input that requires a gradient -- steps 2.. of :class:`RolloutModel`, whose input is
-    the previous step's :func:`autograd.advance_input` -- and return ``dx`` from ``anemoi_assemble_nodes_backward`` /
-    ``anemoi_prognostic_residual_backward``.  Outside it (a direct ``model(x)`` with ``x.requires_grad``) the generic torch
+    :class:`_PrognosticResidual` or, with ``truncation_data``, ``autograd.truncated_residual``) for an input that requires a
+    gradient -- steps 2.. of :class:`RolloutModel`, whose input is the previous step's :func:`autograd.advance_input` -- and
+    return ``dx`` from ``anemoi_assemble_nodes_backward`` / ``anemoi_prognostic_residual_backward`` / ``anemoi_csr_project`` on the
+    transposed matrices.  Outside it (a direct ``model(x)`` with ``x.requires_grad``) the generic torch
     route is kept as it was.  ``ANEMOI_AMD_ROLLOUT_FUSED=0`` switches the context off (A/B against the generic route)."""
     global _ROLLOUT_INPUT_GRAD
     outer, _ROLLOUT_INPUT_GRAD = _ROLLOUT_INPUT_GRAD, os.environ.get("ANEMOI_AMD_ROLLOUT_FUSED", "1") != "0"
@@ -496,8 +497,15 @@ class _PrognosticResidual(torch.autograd.Function):
 
 
 def _finish(model, out: Tensor, x: Tensor, b: int, ens: int, g: int) -> Tensor:
+    truncation = getattr(model, "_truncation", None)  # (layers.truncation.TruncationPlan: x_skip = A_up (A_down x[:, -1]))
     if (out.is_cuda and _fused_io(x) and x.dtype == torch.float32 and x.dim() == 5
             and os.environ.get("ANEMOI_AMD_TRAIN_FUSED_FINISH", "1") != "0"):
+        if truncation is not None:
+            o_idx, i_idx = model._prognostic_indices(x.device)
+            y = autograd.truncated_residual(out, x, truncation, o_idx, i_idx, (b, ens, g, out.shape[-1]), model._idx_cache)
+            for bounding in model.boundings:
+                y = bounding(y)
+            return y
         key = ("residual_src", str(x.device))  # (the inference route's column map, models/encoder_processor_decoder.py::_finish)
         if key not in model._idx_cache:
             src = torch.full((model.num_output_channels,), -1, dtype=torch.int32)
@@ -516,7 +524,15 @@ def _finish(model, out: Tensor, x: Tensor, b: int, ens: int, g: int) -> Tensor:
     # the prognostic residual as ONE full-width addend (zeros outside the prognostic columns): a plain add in the graph --
     # reading y[..., o_idx] instead costs torch's sort-based index accumulation in the backward (1.8 ms per step)
     res = torch.zeros_like(y)
-    res[..., o_idx] = x[:, -1].index_select(-1, i_idx).to(y.dtype)
+    skip = x[:, -1].index_select(-1, i_idx).to(y.dtype)
+    if truncation is not None:
+        # the composition of current anemoi-models: two sparse products per (batch entry, member) over the prognostic columns
+        mats = truncation.sparse(x.device, y.dtype, model._idx_cache)
+        flat = skip.reshape(b * ens, g, -1)
+        for m in mats:
+            flat = torch.stack([torch.sparse.mm(m, flat[i]) for i in range(flat.shape[0])])
+        skip = flat.reshape(skip.shape)
+    res[..., o_idx] = skip
     y = y + res
     for bounding in model.boundings:  # in-place clamps on the cloned output: plain differentiable torch ops
         y = bounding(y)

@@ -423,6 +423,28 @@ int anemoi_prognostic_residual_backward(const float* dy, int V_out, float* dx, i
                                         const int32_t* src, anemoi_stream_t stream);
 
 /*
+ * Truncated residual connection (ABI v52, csrc/truncation.hip): current anemoi-models adds A_up (A_down x[:, -1]) -- the last
+ * input state projected to a coarser grid and back by two sparse interpolation matrices -- to the decoder output instead of
+ * the state itself.  One CSR projection serves both products and, on the transposed matrices, their backward:
+ *   out[s, i, cols_out[p]]  (= or +=)  sum_{k = indptr[i] .. indptr[i+1]-1} val[k] * x'[s, idx[k], cols_in[p]]     p < P
+ *   x' = x * in_mul[cols_in[p]] + in_add[cols_in[p]]        (both NULL: x' = x)
+ * x and out are f32 with unit-stride columns and rows ldx / ldo elements apart; indptr int64 [n_out + 1], idx int32 (< n_in),
+ * val f32; cols_in / cols_out int32 [P], NULL = 0..P-1.  Slab s = so * n_inner + si (so < n_outer, si < n_inner) of x starts
+ * at x + so * xs_outer + si * xs_inner and of out at out + so * os_outer + si * os_inner (element strides; the caller adds
+ * the base, e.g. time slice T-1): the down-projection reads x [B, T, Ens, G, V_in] -- or a transposed view of it -- in place
+ * for every (b, ens), the up-projection accumulates straight into y [B, Ens, G, V_out].  accumulate = 0 stores (an empty row
+ * writes 0), 1 adds to out (an empty row leaves it untouched).  Each output element is owned by one thread that adds the
+ * terms of its row in ascending CSR position with one f32 FMA each: no atomics, no workspace, the same bits on every run.
+ * Negative sizes or strides, P <= 0, a row pitch below P under NULL columns and overlapping output slabs are
+ * ANEMOI_ERR_INVALID before any launch; more than 65535 slabs is ANEMOI_ERR_UNSUPPORTED.  x must not overlap out.
+ */
+int anemoi_csr_project(const float* x, int64_t ldx, int64_t xs_outer, int64_t xs_inner, float* out, int64_t ldo,
+                       int64_t os_outer, int64_t os_inner, int n_outer, int n_inner, int64_t n_in, int64_t n_out,
+                       const int64_t* indptr, const int32_t* idx, const float* val, const int32_t* cols_in,
+                       const int32_t* cols_out, int P, const float* in_mul, const float* in_add, int accumulate,
+                       anemoi_stream_t stream);
+
+/*
  * Node-weighted, variable-scaled, masked squared error over pred / target (f32 [rows, V] contiguous; rows is a multiple of G
  * and row r belongs to grid node r % G, so a stack of rollout steps, batch and ensemble members is one call):
  *   loss = scale * sum_{r, v} keep(r, v) ? row_w[r % G] * col_w[v] * (pred - target)^2 : 0
