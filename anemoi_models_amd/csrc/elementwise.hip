@@ -793,7 +793,8 @@ int anemoi_row_dot(int dtype, const void* a, int64_t lda, const void* b, int64_t
 
 int anemoi_add(int dtype, const void* a, int64_t lda, const void* b, int64_t ldb, void* y, int64_t ldy, int64_t rows,
                int cols, anemoi_stream_t stream) {
-  ANEMOI_REQUIRE(a && b && y && rows >= 0 && cols >= 0, ANEMOI_ERR_INVALID, "anemoi_add: bad argument");
+  ANEMOI_REQUIRE(a && b && y && rows >= 0 && cols >= 0 && lda >= cols && ldb >= cols && ldy >= cols, ANEMOI_ERR_INVALID,
+                 "anemoi_add: bad argument");
   if (rows * cols == 0) return ANEMOI_OK;
   hipStream_t st = as_stream(stream);
   dim3 grid(flat_grid(rows * cols)), block(256);

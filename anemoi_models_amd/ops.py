@@ -101,9 +101,11 @@ def layer_norm(x: Tensor, weight: Tensor, bias: Tensor, eps: float = 1e-5, out: 
     _rows(x)
     if out is None:
         out = torch.empty((x.shape[0], x.shape[1]), dtype=x.dtype, device=x.device)
+    if residual is not None and (residual.dtype != x.dtype or residual.shape != x.shape):
+        raise ValueError("layer_norm: the residual must have the shape and dtype of x")
+    if x.shape[0] == 0:  # (an empty tensor has no storage: the library would see null pointers)
+        return out
     if residual is not None:
-        if residual.dtype != x.dtype or residual.shape != x.shape:
-            raise ValueError("layer_norm: the residual must have the shape and dtype of x")
         with _Timed("layer_norm", bytes=3 * x.shape[0] * x.shape[1] * x.element_size()):
             st = _lib.load().anemoi_layer_norm_residual(dtype_code(x.dtype), x.data_ptr(), _ld(x), weight.data_ptr(),
                                                         bias.data_ptr(), residual.data_ptr(), _ld(_rows(residual)),
@@ -125,6 +127,8 @@ def layer_norm_with_stats(x: Tensor, weight: Tensor, bias: Tensor, eps: float = 
     _rows(x)
     out = torch.empty((x.shape[0], x.shape[1]), dtype=x.dtype, device=x.device)
     stats = torch.empty((x.shape[0], 2), dtype=torch.float32, device=x.device)
+    if x.shape[0] == 0:
+        return out, stats
     st = _lib.load().anemoi_layer_norm_stats(dtype_code(x.dtype), x.data_ptr(), _ld(x), weight.data_ptr(), bias.data_ptr(),
                                              out.data_ptr(), _ld(out), stats.data_ptr(), x.shape[0], x.shape[1], eps,
                                              _stream())
@@ -157,6 +161,8 @@ def row_stats(x: Tensor, eps: float = 1e-5) -> Tensor:
     if carried is not None:
         return carried
     out = torch.empty((x.shape[0], 2), dtype=torch.float32, device=x.device)
+    if x.shape[0] == 0:
+        return out
     with _Timed("row_stats", bytes=x.shape[0] * x.shape[1] * x.element_size()):
         st = _lib.load().anemoi_row_stats(dtype_code(x.dtype), x.data_ptr(), _ld(x), out.data_ptr(), x.shape[0],
                                           x.shape[1], eps, _stream())
@@ -1312,6 +1318,8 @@ def col_sum(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
         out = torch.empty(cols, dtype=torch.float32, device=x.device)
     elif out.dtype != torch.float32 or out.numel() != cols or not out.is_contiguous():
         raise ValueError("col_sum: out must be a contiguous f32 vector of the column count")
+    if rows == 0:  # (an empty tensor has no storage: the library would see a null pointer)
+        return out.zero_()
     n_ws = lib.anemoi_col_sum_workspace_floats(rows, cols)
     ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=x.device)
     st = lib.anemoi_col_sum(dtype_code(x.dtype), x.data_ptr(), _ld(x), rows, cols, out.data_ptr(), ws.data_ptr(), n_ws,
@@ -1444,11 +1452,13 @@ def layer_norm_backward(x: Tensor, stats: Tensor, gamma: Tensor, dy: Tensor, dre
     dx = torch.empty((rows, c), dtype=x.dtype, device=x.device)
     dgamma = torch.empty(c, dtype=torch.float32, device=x.device)
     dbeta = torch.empty(c, dtype=torch.float32, device=x.device)
+    if dres is not None and (tuple(_rows(dres).shape) != (rows, c) or dres.dtype != x.dtype):
+        raise ValueError("layer_norm_backward: dres must have x's shape and dtype")
+    if rows == 0:  # (no rows: nothing to launch, and an empty tensor has no storage to point the library at)
+        return dx, dgamma.zero_(), dbeta.zero_()
     n_ws = lib.anemoi_layer_norm_backward_workspace_floats(rows, c)
     ws = torch.empty(n_ws, dtype=torch.float32, device=x.device)
     gamma = gamma.detach().float().contiguous()
-    if dres is not None and (tuple(_rows(dres).shape) != (rows, c) or dres.dtype != x.dtype):
-        raise ValueError("layer_norm_backward: dres must have x's shape and dtype")
     st = lib.anemoi_layer_norm_backward(dtype_code(x.dtype), x.data_ptr(), _ld(x), stats.data_ptr(), gamma.data_ptr(),
                                         dy.data_ptr(), _ld(dy), _ptr(dres), 0 if dres is None else _ld(_rows(dres)),
                                         dx.data_ptr(), c, rows, c, dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(),
