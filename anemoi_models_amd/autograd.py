@@ -1424,6 +1424,11 @@ def truncated_residual(out: Tensor, x: Tensor, plan, out_idx: Tensor, in_idx: Te
     return _TruncatedResidual.apply(out, x, plan.on(x.device, cache), out_idx, in_idx, tuple(shape))
 
 
+def _f32c(t: Optional[Tensor]) -> Optional[Tensor]:
+    """A constant operand of a loss (no gradient) as contiguous float32."""
+    return None if t is None else t.detach().float().contiguous()
+
+
 class _WeightedMSE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred: Tensor, target: Tensor, row_w: Tensor, col_w: Tensor, mask: Optional[Tensor], scale: float):
@@ -1448,9 +1453,8 @@ def weighted_mse(pred: Tensor, target: Tensor, row_w: Tensor, col_w: Tensor, mas
     g, v = row_w.numel(), pred.shape[-1]
     if pred.shape != target.shape or pred.dim() < 2 or pred.shape[-2] != g:
         raise ValueError(f"weighted_mse: pred {tuple(pred.shape)} / target {tuple(target.shape)} do not end in [G = {g}, V]")
-    f32 = lambda t: None if t is None else t.detach().float().contiguous()  # noqa: E731
     p2 = pred.float().contiguous().view(-1, v)
-    return _WeightedMSE.apply(p2, f32(target).view(-1, v), f32(row_w), f32(col_w), f32(mask), float(scale))
+    return _WeightedMSE.apply(p2, _f32c(target).view(-1, v), _f32c(row_w), _f32c(col_w), _f32c(mask), float(scale))
 
 
 class _WeightedError(torch.autograd.Function):
@@ -1484,12 +1488,11 @@ def weighted_error(pred: Tensor, target: Tensor, row_w: Tensor, kind: str = "mse
     g, v = row_w.numel(), pred.shape[-1]
     if pred.shape != target.shape or pred.dim() < 2 or pred.shape[-2] != g:
         raise ValueError(f"weighted_error: pred {tuple(pred.shape)} / target {tuple(target.shape)} do not end in [G = {g}, V]")
-    f32 = lambda t: None if t is None else t.detach().float().contiguous()  # noqa: E731
     t2 = target.float().contiguous().view(-1, v)
     if not target.requires_grad:
         t2 = t2.detach()
-    return _WeightedError.apply(pred.float().contiguous().view(-1, v), t2, f32(row_w), f32(col_w), f32(mask), f32(diff_scale),
-                                str(kind), float(delta), int(n_groups), float(scale))
+    return _WeightedError.apply(pred.float().contiguous().view(-1, v), t2, _f32c(row_w), _f32c(col_w), _f32c(mask),
+                                _f32c(diff_scale), str(kind), float(delta), int(n_groups), float(scale))
 
 
 class _EnsembleScore(torch.autograd.Function):
@@ -1531,6 +1534,5 @@ def ensemble_score(pred: Tensor, target: Tensor, row_w: Tensor, kind: str = "afc
     if pred.requires_grad and torch.is_grad_enabled() and str(kind) != "afcrps":
         raise ValueError(f"ensemble_score: pred requires a gradient and kind {kind!r} has none (only afcrps has)")
     v, e = pred.shape[-1], pred.shape[-3]
-    f32 = lambda t: None if t is None else t.detach().float().contiguous()  # noqa: E731
-    return _EnsembleScore.apply(pred.float().contiguous().view(-1, v), f32(target).view(-1, v), f32(row_w), f32(col_w),
-                                f32(mask), f32(diff_scale), str(kind), int(e), float(alpha), int(n_groups), float(scale))
+    return _EnsembleScore.apply(pred.float().contiguous().view(-1, v), _f32c(target).view(-1, v), _f32c(row_w), _f32c(col_w),
+                                _f32c(mask), _f32c(diff_scale), str(kind), int(e), float(alpha), int(n_groups), float(scale))

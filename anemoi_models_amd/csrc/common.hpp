@@ -37,6 +37,8 @@ inline int check_launch(const char* what) {
     if (!(cond)) return ::anemoi::fail(code, __VA_ARGS__); \
   } while (0)
 
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 // "Has this call site prepared its kernels on the CURRENT device yet?" -- for hipFuncSetAttribute(MaxDynamicShared
 // MemorySize), which is a per-device property of a kernel: one bit per device ordinal, atomics only (two threads racing
 // through the first call both set the (idempotent) attribute; neither launches before it is set).

@@ -6,45 +6,20 @@
 // backward of the CRPS with a per-variable upstream gradient.  pred is [n_groups * B * E * G, V] (member e of point (l, b, g) is
 // row ((l B + b) E + e) G + g), target [n_groups * B * G, V].
 //
-// Deterministic like anemoi_weighted_error (csrc/losses.hip), whose column layout this keeps: no atomics; the workgroup count,
-// the group and the contiguous chunk of points of every workgroup are functions of (n_groups, B * G, V, E) alone; every sum has
-// a fixed order.  Stage 1, V <= 256: thread t < L * V (L = 256 / V row lanes) owns column t % V and row lane t / V, so that one
-// pass of the workgroup over L points reads, member by member, the contiguous floats point0 * V + t of that member's plane.  V >
-// 256: column tiles of 256, one point per pass.  E is a template argument: the E members of a point are loaded once, held in
-// registers, and all E (E - 1) / 2 pair terms are formed there.  S is evaluated on e_j = c (x_j - y) (the same value: S takes
-// differences only), so an additive offset common to members and target -- a normaliser's -- never meets the rounding.  Sums
-// over members ascend in j; a pair sum is sum_j (sum_{k > j} term(j, k)), both ascending.  A thread adds the terms of its
-// column in ascending point order (for E <= 4 with 4 or 2 independent points of loads in flight), the L lanes of a column are
-// summed through LDS in lane order.  Workgroup k of group l writes its [V] partial to workspace[(l * W + k) * V].
-// Stage 2: one thread per (l, v) adds the W partials in ascending workgroup order and applies `scale`.
-#include "common.hpp"
-#include "trail.hpp"
+// It is a column reduction of csrc/column_reduce.hpp (geometry, layout, sum order and determinism contract there) over points:
+// one pass of the workgroup over L points reads, member by member, the contiguous floats point0 * V + t of that member's plane.
+// E is a template argument: the E members of a point are loaded once, held in registers, and all E (E - 1) / 2 pair terms are
+// formed there.  S is evaluated on e_j = c (x_j - y) (the same value: S takes differences only), so an additive offset common to
+// members and target -- a normaliser's -- never meets the rounding.  Sums over members ascend in j; a pair sum is sum_j (sum_{k >
+// j} term(j, k)), both ascending.  A thread adds the terms of its column in ascending point order (for E <= 4 with 4 or 2
+// independent points of loads in flight).
+#include "column_reduce.hpp"
 
 namespace anemoi {
 
 constexpr int ENS_AFCRPS = 0, ENS_MEAN_SE = 1, ENS_VARIANCE = 2;  // ANEMOI_ENS_* of include/anemoi_amd.h
 constexpr int ENS_MAX_MEMBERS = 16;
-constexpr int64_t ENS_PER_BLOCK = 4096;  // (point, column) pairs per workgroup before the workgroup count of a group saturates
-constexpr int64_t ENS_MAX_BLOCKS = 2048;  // workgroups per group
-
-static inline int ens_lanes(int V) { return V <= 256 ? 256 / V : 1; }
-
-// points of one workgroup's chunk: a multiple of the row lanes (only the last chunk of a group has a ragged pass)
-static inline int64_t ens_chunk_points(int64_t points_per_group, int V, int E) {
-  (void)E;  // part of the contract's key; the chunking does not use it
-  int64_t blocks = (points_per_group * (int64_t)V + ENS_PER_BLOCK - 1) / ENS_PER_BLOCK;
-  if (blocks > ENS_MAX_BLOCKS) blocks = ENS_MAX_BLOCKS;
-  if (blocks < 1) blocks = 1;
-  const int64_t lanes = ens_lanes(V);
-  const int64_t chunk = ((points_per_group + blocks - 1) / blocks + lanes - 1) / lanes * lanes;
-  return chunk < lanes ? lanes : chunk;
-}
-
-static inline int64_t ens_blocks(int64_t points_per_group, int V, int E) {  // per group
-  const int64_t chunk = ens_chunk_points(points_per_group, V, E);
-  const int64_t blocks = (points_per_group + chunk - 1) / chunk;
-  return blocks < 1 ? 1 : blocks;
-}
+constexpr int64_t ENS_MAX_BLOCKS = 2048;  // workgroups per group (the chunking does not depend on E)
 
 // S of one point.  a1, a2 by kind: AFCRPS 2 / (E (E - 1)), eps / (E (E - 1)); MEAN_SE 1 / E, -; VARIANCE 1 / E, 1 / (E - 1).
 //
@@ -172,19 +147,6 @@ __global__ __launch_bounds__(256) void ensemble_score_kernel(const float* __rest
   }
 }
 
-__global__ __launch_bounds__(256) void ensemble_score_finish_kernel(const float* __restrict__ partial, int64_t blocks,
-                                                                    int64_t n_out, int V, float scale,
-                                                                    float* __restrict__ out) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;  // (l, v)
-  if (idx >= n_out) return;
-  const int64_t l = idx / V, v = idx - l * V;
-  const float* p = partial + l * blocks * V + v;
-  float s = 0.f;
-#pragma unroll 8
-  for (int64_t k = 0; k < blocks; ++k) s += p[k * V];
-  out[idx] = s * scale;
-}
-
 // d AFCRPS / d members: one thread per (point, column) reads the E members and the target once and writes the E gradients.
 // The signs come from comparing the raw members: equal values give exactly 0 whatever the scale and the flush mode.
 template <int E>
@@ -227,20 +189,11 @@ __global__ __launch_bounds__(256) void ensemble_crps_backward_kernel(const float
 
 static int check_ens(const char* who, int kind, float alpha, const float* pred, const float* target, int64_t rows, int V,
                      int64_t G, int E, int64_t n_groups, const float* row_w) {
-  ANEMOI_REQUIRE(pred && target && row_w, ANEMOI_ERR_INVALID, "%s: null pointer", who);
-  ANEMOI_REQUIRE(kind == ENS_AFCRPS || kind == ENS_MEAN_SE || kind == ENS_VARIANCE, ANEMOI_ERR_INVALID, "%s: unknown kind %d",
-                 who, kind);
+  if (int rc = column_reduce::check_operands(who, kind, 3, pred, target, row_w)) return rc;
   ANEMOI_REQUIRE(E >= 2, ANEMOI_ERR_INVALID, "%s: an ensemble score needs at least 2 members, got E = %d", who, E);
   ANEMOI_REQUIRE(E <= ENS_MAX_MEMBERS, ANEMOI_ERR_UNSUPPORTED, "%s: E = %d members, at most %d", who, E, ENS_MAX_MEMBERS);
   ANEMOI_REQUIRE(alpha >= 0.f && alpha <= 1.f, ANEMOI_ERR_INVALID, "%s: alpha must lie in [0, 1], got %g", who, (double)alpha);
-  ANEMOI_REQUIRE(rows >= 0 && V > 0 && G > 0 && n_groups > 0, ANEMOI_ERR_INVALID,
-                 "%s: bad shape rows=%lld V=%d G=%lld n_groups=%lld", who, (long long)rows, V, (long long)G,
-                 (long long)n_groups);
-  ANEMOI_REQUIRE(G * (int64_t)V < ((int64_t)1 << 31), ANEMOI_ERR_UNSUPPORTED, "%s: G * V does not fit 31 bits", who);
-  ANEMOI_REQUIRE(n_groups <= 65535, ANEMOI_ERR_UNSUPPORTED, "%s: %lld groups, at most 65535", who, (long long)n_groups);
-  ANEMOI_REQUIRE(rows % (n_groups * G) == 0, ANEMOI_ERR_INVALID,
-                 "%s: rows %lld is not a multiple of n_groups * G = %lld * %lld", who, (long long)rows, (long long)n_groups,
-                 (long long)G);
+  if (int rc = column_reduce::check_shape(who, rows, V, G, n_groups)) return rc;
   ANEMOI_REQUIRE(rows / (n_groups * G) < ((int64_t)1 << 31), ANEMOI_ERR_UNSUPPORTED, "%s: the batch does not fit 31 bits", who);
   return ANEMOI_OK;
 }
@@ -285,7 +238,7 @@ extern "C" {
 
 int64_t anemoi_ensemble_score_workspace_floats(int64_t n_groups, int64_t points_per_group, int V, int E) {
   if (n_groups <= 0 || points_per_group <= 0 || V <= 0 || E < 2 || E > ENS_MAX_MEMBERS) return 0;
-  return n_groups * ens_blocks(points_per_group, V, E) * V;
+  return n_groups * column_reduce::blocks(points_per_group, V, ENS_MAX_BLOCKS) * V;
 }
 
 int anemoi_ensemble_score(int kind, float alpha, const float* pred, const float* target, int64_t rows, int V, int64_t G, int E,
@@ -293,32 +246,22 @@ int anemoi_ensemble_score(int kind, float alpha, const float* pred, const float*
                           const float* diff_scale, float scale, float* out, float* workspace, int64_t workspace_floats,
                           anemoi_stream_t stream) {
   if (int rc = check_ens("anemoi_ensemble_score", kind, alpha, pred, target, rows, V, G, E, n_groups, row_w)) return rc;
-  ANEMOI_REQUIRE(out != nullptr, ANEMOI_ERR_INVALID, "anemoi_ensemble_score: null pointer (out)");
   hipStream_t st = as_stream(stream);
-  const int64_t n_out = n_groups * V;
-  if (rows == 0) {
-    hipError_t e = hipMemsetAsync(out, 0, n_out * sizeof(float), st);
-    if (e != hipSuccess) return fail(ANEMOI_ERR_LAUNCH, "anemoi_ensemble_score: %s", hipGetErrorString(e));
-    return ANEMOI_OK;
-  }
-  const int64_t ppg = rows / n_groups;
-  const int64_t blocks = ens_blocks(ppg, V, E), need = n_groups * blocks * V;
-  ANEMOI_REQUIRE(workspace != nullptr && workspace_floats >= need, ANEMOI_ERR_INVALID,
-                 "anemoi_ensemble_score: workspace of %lld floats, %lld needed", (long long)workspace_floats, (long long)need);
-  const dim3 grid((unsigned)blocks, (unsigned)n_groups);
-  const int64_t chunk = ens_chunk_points(ppg, V, E);
   float a1, a2;
   ens_coefficients(kind, alpha, E, false, a1, a2);
-  if (kind == ENS_AFCRPS)
-    launch_ens_score<ENS_AFCRPS>(E, grid, st, pred, target, ppg, chunk, G, V, row_w, col_w, mask, diff_scale, a1, a2, workspace);
-  else if (kind == ENS_MEAN_SE)
-    launch_ens_score<ENS_MEAN_SE>(E, grid, st, pred, target, ppg, chunk, G, V, row_w, col_w, mask, diff_scale, a1, a2, workspace);
-  else
-    launch_ens_score<ENS_VARIANCE>(E, grid, st, pred, target, ppg, chunk, G, V, row_w, col_w, mask, diff_scale, a1, a2, workspace);
-  hipLaunchKernelGGL(ensemble_score_finish_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, workspace, blocks,
-                     n_out, V, scale, out);
-  int rc = trail::note(check_launch("anemoi_ensemble_score"), "anemoi_ensemble_score", "partials", ANEMOI_F32, workspace, V,
-                       n_groups * blocks, V, st);
+  int64_t blocks;
+  int rc = column_reduce::run(
+      "anemoi_ensemble_score", rows, V, n_groups, ENS_MAX_BLOCKS, scale, out, workspace, workspace_floats, st, blocks,
+      [&](dim3 grid, int64_t ppg, int64_t chunk) {
+#define ANEMOI_ENS_SCORE(KIND)                                                                                            \
+  launch_ens_score<KIND>(E, grid, st, pred, target, ppg, chunk, G, V, row_w, col_w, mask, diff_scale, a1, a2, workspace)
+        if (kind == ENS_AFCRPS) ANEMOI_ENS_SCORE(ENS_AFCRPS);
+        else if (kind == ENS_MEAN_SE) ANEMOI_ENS_SCORE(ENS_MEAN_SE);
+        else ANEMOI_ENS_SCORE(ENS_VARIANCE);
+#undef ANEMOI_ENS_SCORE
+      });
+  if (blocks == 0) return rc;  // refused, or no rows: nothing was launched
+  rc = trail::note(rc, "anemoi_ensemble_score", "partials", ANEMOI_F32, workspace, V, n_groups * blocks, V, st);
   return trail::note(rc, "anemoi_ensemble_score", "out", ANEMOI_F32, out, V, n_groups, V, st);
 }
 

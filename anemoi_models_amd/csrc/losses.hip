@@ -1,43 +1,22 @@
-// The loss family ("8f-6"): one reduction [rows, V] -> [groups, V] for the node-weighted, variable-scaled,
-// masked MSE / MAE / Huber / log-cosh error per variable, and its element-wise backward with a per-variable upstream gradient.
+// The loss family ("rollout" and "8f-6").
+//
+// anemoi_weighted_error: one reduction [rows, V] -> [groups, V] for the node-weighted, variable-scaled, masked MSE / MAE /
+// Huber / log-cosh error per variable, and its element-wise backward with a per-variable upstream gradient.
 //
 //   out[l, v] = scale * sum_{r in group l} keep(g, v) ? row_w[g] * col_w[v] * f(c[v] * (pred[r, v] - target[r, v])) : 0,  g = r % G
 //
-// Deterministic like anemoi_weighted_mse (csrc/rollout.hip): no atomics, the workgroup count, the group and the contiguous row
-// chunk of every workgroup are functions of (n_groups, rows_per_group, V) alone, every sum has a fixed order.
+// It is a column reduction of csrc/column_reduce.hpp (geometry, layout, sum order and determinism contract there) over rows: a
+// thread adds the terms of its column in ascending row order, WERR_UNROLL independent passes of loads in flight.
 //
-// Stage 1, V <= 256: thread t < L * V (L = 256 / V row lanes) owns column t % V and row lane t / V, so that one pass of the
-// workgroup over L rows reads the contiguous floats row0 * V + t.  A thread adds the terms of its column in ascending row order
-// (WERR_UNROLL independent passes of loads in flight), then the L lanes of a column are summed through LDS in lane order.
-// V > 256: column tiles of 256, one row per pass.  Workgroup k of group l writes its [V] partial to workspace[(l * W + k) * V].
-// Stage 2: one thread per (l, v) adds the W partials in ascending workgroup order and applies `scale`.
-#include "common.hpp"
-#include "trail.hpp"
+// anemoi_weighted_mse: the scalar node-weighted, variable-scaled, masked MSE of a rollout step with its gradient, on a flat-index
+// reduction of its own (below) -- as deterministic, another sum order.
+#include "column_reduce.hpp"
 
 namespace anemoi {
 
 constexpr int WERR_MSE = 0, WERR_MAE = 1, WERR_HUBER = 2, WERR_LOGCOSH = 3;  // ANEMOI_LOSS_* of include/anemoi_amd.h
-constexpr int64_t WERR_PER_BLOCK = 4096;  // elements per workgroup before the workgroup count of a group saturates
 constexpr int64_t WERR_MAX_BLOCKS = 1024;  // workgroups per group
 constexpr int WERR_UNROLL = 4;
-
-static inline int werr_lanes(int V) { return V <= 256 ? 256 / V : 1; }
-
-// rows of one workgroup's chunk: a multiple of the row lanes (only the last chunk of a group has a ragged pass)
-static inline int64_t werr_chunk_rows(int64_t rows_per_group, int V) {
-  int64_t blocks = (rows_per_group * (int64_t)V + WERR_PER_BLOCK - 1) / WERR_PER_BLOCK;
-  if (blocks > WERR_MAX_BLOCKS) blocks = WERR_MAX_BLOCKS;
-  if (blocks < 1) blocks = 1;
-  const int64_t lanes = werr_lanes(V);
-  const int64_t chunk = ((rows_per_group + blocks - 1) / blocks + lanes - 1) / lanes * lanes;
-  return chunk < lanes ? lanes : chunk;
-}
-
-static inline int64_t werr_blocks(int64_t rows_per_group, int V) {  // per group
-  const int64_t chunk = werr_chunk_rows(rows_per_group, V);
-  const int64_t blocks = (rows_per_group + chunk - 1) / chunk;
-  return blocks < 1 ? 1 : blocks;
-}
 
 template <int KIND>
 __device__ __forceinline__ float werr_f(float e, float delta) {
@@ -140,9 +119,10 @@ __global__ __launch_bounds__(256) void weighted_error_kernel(const float* __rest
   }
 }
 
-__global__ __launch_bounds__(256) void weighted_error_finish_kernel(const float* __restrict__ partial, int64_t blocks,
-                                                                    int64_t n_out, int V, float scale,
-                                                                    float* __restrict__ out) {
+// Stage 2 of every column reduction (column_reduce::launch_finish, used by csrc/ensemble.hip as well).
+__global__ __launch_bounds__(256) void column_reduce_finish_kernel(const float* __restrict__ partial, int64_t blocks,
+                                                                   int64_t n_out, int V, float scale,
+                                                                   float* __restrict__ out) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;  // (l, v)
   if (idx >= n_out) return;
   const int64_t l = idx / V, v = idx - l * V;
@@ -151,6 +131,12 @@ __global__ __launch_bounds__(256) void weighted_error_finish_kernel(const float*
 #pragma unroll 8
   for (int64_t k = 0; k < blocks; ++k) s += p[k * V];
   out[idx] = s * scale;
+}
+
+void column_reduce::launch_finish(const float* partial, int64_t blocks, int64_t n_out, int V, float scale, float* out,
+                                  hipStream_t st) {
+  hipLaunchKernelGGL(column_reduce_finish_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, partial, blocks,
+                     n_out, V, scale, out);
 }
 
 // dpred, four consecutive elements per thread (one 16-byte access per operand where the pointers allow), (l, g, v) kept by
@@ -211,19 +197,121 @@ __global__ __launch_bounds__(256) void weighted_error_backward_kernel(const floa
 
 static int check_werr(const char* who, int kind, float delta, const float* pred, const float* target, int64_t rows, int V,
                       int64_t G, int64_t n_groups, const float* row_w) {
-  ANEMOI_REQUIRE(pred && target && row_w, ANEMOI_ERR_INVALID, "%s: null pointer", who);
-  ANEMOI_REQUIRE(kind == WERR_MSE || kind == WERR_MAE || kind == WERR_HUBER || kind == WERR_LOGCOSH, ANEMOI_ERR_INVALID,
-                 "%s: unknown kind %d", who, kind);
+  if (int rc = column_reduce::check_operands(who, kind, 4, pred, target, row_w)) return rc;
   ANEMOI_REQUIRE(kind != WERR_HUBER || delta > 0.f, ANEMOI_ERR_INVALID, "%s: the Huber delta must be positive, got %g", who,
                  (double)delta);
-  ANEMOI_REQUIRE(rows >= 0 && V > 0 && G > 0 && n_groups > 0, ANEMOI_ERR_INVALID,
-                 "%s: bad shape rows=%lld V=%d G=%lld n_groups=%lld", who, (long long)rows, V, (long long)G,
-                 (long long)n_groups);
+  return column_reduce::check_shape(who, rows, V, G, n_groups);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Weighted MSE.  Flat element i of pred / target [rows, V]: position i % (G * V) of the [G, V] weight / mask plane.
+// One thread walks four consecutive elements (one 16-byte load per operand) and keeps (g, v) by increments.
+// Stage 1: workgroup k reduces the contiguous chunk [k * chunk, (k + 1) * chunk) -- chunk and the workgroup count are functions
+// of rows * V alone (wmse_blocks / wmse_chunk) -- each thread in ascending index order, the wave by the fixed butterfly of
+// wave_sum, the four waves in wave order.  Stage 2: one workgroup sums the partials the same way and applies `scale`.
+// ---------------------------------------------------------------------------------------------
+constexpr int64_t WMSE_PER_BLOCK = 4096;  // elements per workgroup before the workgroup count saturates
+constexpr int64_t WMSE_MAX_BLOCKS = 2048;
+
+static inline int64_t wmse_blocks(int64_t n) {
+  int64_t blocks = (n + WMSE_PER_BLOCK - 1) / WMSE_PER_BLOCK;
+  if (blocks > WMSE_MAX_BLOCKS) blocks = WMSE_MAX_BLOCKS;
+  return blocks < 1 ? 1 : blocks;
+}
+
+static inline int64_t wmse_chunk(int64_t n) {  // a multiple of the 1024 elements one workgroup takes per trip
+  const int64_t blocks = wmse_blocks(n);
+  return ((n + blocks - 1) / blocks + 1023) / 1024 * 1024;
+}
+
+__device__ __forceinline__ float block_sum_256(float v, float* sh4) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((sh4[0] + sh4[1]) + sh4[2]) + sh4[3];
+}
+
+// BACKWARD = false: partial[blockIdx.x] = sum of the chunk's terms.  BACKWARD = true: dpred over the same chunks.
+template <bool BACKWARD>
+__global__ __launch_bounds__(256) void weighted_mse_kernel(const float* __restrict__ pred,
+                                                           const float* __restrict__ target, int64_t n, int64_t chunk,
+                                                           int64_t G, int V, const float* __restrict__ row_w,
+                                                           const float* __restrict__ col_w,
+                                                           const float* __restrict__ mask, float scale,
+                                                           const float* __restrict__ upstream,
+                                                           float* __restrict__ out, int vec_ok) {
+  __shared__ float sh4[4];
+  const int64_t begin = (int64_t)blockIdx.x * chunk;
+  const int64_t end = begin + chunk < n ? begin + chunk : n;
+  const int64_t plane = G * (int64_t)V;  // < 2^31 (checked by the entry point)
+  const bool fits32 = n < ((int64_t)1 << 31);
+  float coef = 0.f;
+  if constexpr (BACKWARD) coef = (*upstream * scale) * 2.0f;
+  float acc = 0.f;
+  for (int64_t i0 = begin + (int64_t)threadIdx.x * 4; i0 < end; i0 += 1024) {
+    int64_t rep, m0;
+    fast_divmod(i0, plane, fits32, rep, m0);
+    unsigned g = (unsigned)m0 / (unsigned)V, v = (unsigned)m0 - g * (unsigned)V;
+    const int cnt = end - i0 < 4 ? (int)(end - i0) : 4;
+    float p[4] = {0.f, 0.f, 0.f, 0.f}, t[4] = {0.f, 0.f, 0.f, 0.f}, r[4];
+    if (cnt == 4 && vec_ok) {
+      VecIO<float, 4>::load(pred + i0, p);
+      VecIO<float, 4>::load(target + i0, t);
+    } else {
+      for (int k = 0; k < cnt; ++k) {
+        p[k] = pred[i0 + k];
+        t[k] = target[i0 + k];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      r[k] = 0.f;
+      if (k < cnt) {
+        const bool keep = mask == nullptr || mask[(int64_t)g * V + v] != 0.f;  // a select: a masked NaN contributes exactly 0
+        const float w = row_w[g] * col_w[v];
+        const float d = p[k] - t[k];
+        if constexpr (BACKWARD) {
+          r[k] = keep ? (coef * w) * d : 0.f;
+        } else {
+          acc += keep ? (w * d) * d : 0.f;
+        }
+        if (++v == (unsigned)V) {
+          v = 0;
+          if (++g == (unsigned)G) g = 0;
+        }
+      }
+    }
+    if constexpr (BACKWARD) {
+      if (cnt == 4 && vec_ok) {
+        VecIO<float, 4>::store(out + i0, r);
+      } else {
+        for (int k = 0; k < cnt; ++k) out[i0 + k] = r[k];
+      }
+    }
+  }
+  if constexpr (!BACKWARD) {
+    const float s = block_sum_256(acc, sh4);
+    if (threadIdx.x == 0) out[blockIdx.x] = s;
+  }
+}
+
+__global__ __launch_bounds__(256) void weighted_mse_finish_kernel(const float* __restrict__ partial, int n_partial,
+                                                                  float scale, float* __restrict__ loss) {
+  __shared__ float sh4[4];
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < n_partial; i += 256) acc += partial[i];
+  const float s = block_sum_256(acc, sh4);
+  if (threadIdx.x == 0) *loss = s * scale;
+}
+
+static int check_wmse(const char* who, const float* pred, const float* target, int64_t rows, int V, int64_t G,
+                      const float* row_w, const float* col_w) {
+  ANEMOI_REQUIRE(pred && target && row_w && col_w, ANEMOI_ERR_INVALID, "%s: null pointer", who);
+  ANEMOI_REQUIRE(rows >= 0 && V > 0 && G > 0, ANEMOI_ERR_INVALID, "%s: bad shape rows=%lld V=%d G=%lld", who,
+                 (long long)rows, V, (long long)G);
+  ANEMOI_REQUIRE(rows % G == 0, ANEMOI_ERR_INVALID, "%s: rows %lld is not a multiple of the grid size G = %lld", who,
+                 (long long)rows, (long long)G);
   ANEMOI_REQUIRE(G * (int64_t)V < ((int64_t)1 << 31), ANEMOI_ERR_UNSUPPORTED, "%s: G * V does not fit 31 bits", who);
-  ANEMOI_REQUIRE(n_groups <= 65535, ANEMOI_ERR_UNSUPPORTED, "%s: %lld groups, at most 65535", who, (long long)n_groups);
-  ANEMOI_REQUIRE(rows % (n_groups * G) == 0, ANEMOI_ERR_INVALID,
-                 "%s: rows %lld is not a multiple of n_groups * G = %lld * %lld", who, (long long)rows, (long long)n_groups,
-                 (long long)G);
   return ANEMOI_OK;
 }
 
@@ -235,7 +323,7 @@ extern "C" {
 
 int64_t anemoi_weighted_error_workspace_floats(int64_t n_groups, int64_t rows_per_group, int V) {
   if (n_groups <= 0 || rows_per_group <= 0 || V <= 0) return 0;
-  return n_groups * werr_blocks(rows_per_group, V) * V;
+  return n_groups * column_reduce::blocks(rows_per_group, V, WERR_MAX_BLOCKS) * V;
 }
 
 int anemoi_weighted_error(int kind, float delta, const float* pred, const float* target, int64_t rows, int V, int64_t G,
@@ -243,33 +331,22 @@ int anemoi_weighted_error(int kind, float delta, const float* pred, const float*
                           const float* diff_scale, float scale, float* out, float* workspace, int64_t workspace_floats,
                           anemoi_stream_t stream) {
   if (int rc = check_werr("anemoi_weighted_error", kind, delta, pred, target, rows, V, G, n_groups, row_w)) return rc;
-  ANEMOI_REQUIRE(out != nullptr, ANEMOI_ERR_INVALID, "anemoi_weighted_error: null pointer (out)");
   hipStream_t st = as_stream(stream);
-  const int64_t n_out = n_groups * V;
-  if (rows == 0) {
-    hipError_t e = hipMemsetAsync(out, 0, n_out * sizeof(float), st);
-    if (e != hipSuccess) return fail(ANEMOI_ERR_LAUNCH, "anemoi_weighted_error: %s", hipGetErrorString(e));
-    return ANEMOI_OK;
-  }
-  const int64_t rows_per_group = rows / n_groups;
-  const int64_t blocks = werr_blocks(rows_per_group, V), need = n_groups * blocks * V;
-  ANEMOI_REQUIRE(workspace != nullptr && workspace_floats >= need, ANEMOI_ERR_INVALID,
-                 "anemoi_weighted_error: workspace of %lld floats, %lld needed", (long long)workspace_floats,
-                 (long long)need);
-  const dim3 grid((unsigned)blocks, (unsigned)n_groups);
-  const int64_t chunk = werr_chunk_rows(rows_per_group, V);
+  int64_t blocks;
+  int rc = column_reduce::run(
+      "anemoi_weighted_error", rows, V, n_groups, WERR_MAX_BLOCKS, scale, out, workspace, workspace_floats, st, blocks,
+      [&](dim3 grid, int64_t rows_per_group, int64_t chunk) {
 #define ANEMOI_WERR(KIND)                                                                                                  \
   hipLaunchKernelGGL(weighted_error_kernel<KIND>, grid, dim3(256), 0, st, pred, target, rows_per_group, chunk, G, V, row_w,   \
                      col_w, mask, diff_scale, delta, workspace)
-  if (kind == WERR_MSE) ANEMOI_WERR(WERR_MSE);
-  else if (kind == WERR_MAE) ANEMOI_WERR(WERR_MAE);
-  else if (kind == WERR_HUBER) ANEMOI_WERR(WERR_HUBER);
-  else ANEMOI_WERR(WERR_LOGCOSH);
+        if (kind == WERR_MSE) ANEMOI_WERR(WERR_MSE);
+        else if (kind == WERR_MAE) ANEMOI_WERR(WERR_MAE);
+        else if (kind == WERR_HUBER) ANEMOI_WERR(WERR_HUBER);
+        else ANEMOI_WERR(WERR_LOGCOSH);
 #undef ANEMOI_WERR
-  hipLaunchKernelGGL(weighted_error_finish_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, workspace, blocks,
-                     n_out, V, scale, out);
-  int rc = trail::note(check_launch("anemoi_weighted_error"), "anemoi_weighted_error", "partials", ANEMOI_F32, workspace, V,
-                       n_groups * blocks, V, st);
+      });
+  if (blocks == 0) return rc;  // refused, or no rows: nothing was launched
+  rc = trail::note(rc, "anemoi_weighted_error", "partials", ANEMOI_F32, workspace, V, n_groups * blocks, V, st);
   return trail::note(rc, "anemoi_weighted_error", "out", ANEMOI_F32, out, V, n_groups, V, st);
 }
 
@@ -295,6 +372,51 @@ int anemoi_weighted_error_backward(int kind, float delta, const float* pred, con
 #undef ANEMOI_WERR
   return trail::note(check_launch("anemoi_weighted_error_backward"), "anemoi_weighted_error_backward", "dpred", ANEMOI_F32,
                      dpred, V, rows, V, st);
+}
+
+int64_t anemoi_weighted_mse_workspace_floats(int64_t rows, int V) {
+  if (rows <= 0 || V <= 0) return 0;
+  return wmse_blocks(rows * (int64_t)V);
+}
+
+int anemoi_weighted_mse(const float* pred, const float* target, int64_t rows, int V, int64_t G, const float* row_w,
+                        const float* col_w, const float* mask, float scale, float* loss, float* workspace,
+                        int64_t workspace_floats, anemoi_stream_t stream) {
+  if (int rc = check_wmse("anemoi_weighted_mse", pred, target, rows, V, G, row_w, col_w)) return rc;
+  ANEMOI_REQUIRE(loss != nullptr, ANEMOI_ERR_INVALID, "anemoi_weighted_mse: null pointer (loss)");
+  hipStream_t st = as_stream(stream);
+  const int64_t n = rows * (int64_t)V;
+  if (n == 0) {
+    hipError_t e = hipMemsetAsync(loss, 0, sizeof(float), st);
+    if (e != hipSuccess) return fail(ANEMOI_ERR_LAUNCH, "anemoi_weighted_mse: %s", hipGetErrorString(e));
+    return ANEMOI_OK;
+  }
+  const int64_t blocks = wmse_blocks(n);
+  ANEMOI_REQUIRE(workspace != nullptr && workspace_floats >= blocks, ANEMOI_ERR_INVALID,
+                 "anemoi_weighted_mse: workspace of %lld floats, %lld needed", (long long)workspace_floats,
+                 (long long)blocks);
+  const int vec_ok = aligned16(pred) && aligned16(target);
+  hipLaunchKernelGGL(weighted_mse_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, pred, target, n, wmse_chunk(n), G,
+                     V, row_w, col_w, mask, scale, (const float*)nullptr, workspace, vec_ok);
+  hipLaunchKernelGGL(weighted_mse_finish_kernel, dim3(1), dim3(256), 0, st, workspace, (int)blocks, scale, loss);
+  int rc = trail::note(check_launch("anemoi_weighted_mse"), "anemoi_weighted_mse", "partials", ANEMOI_F32, workspace, blocks,
+                       1, blocks, st);
+  return trail::note(rc, "anemoi_weighted_mse", "loss", ANEMOI_F32, loss, 1, 1, 1, st);
+}
+
+int anemoi_weighted_mse_backward(const float* pred, const float* target, int64_t rows, int V, int64_t G,
+                                 const float* row_w, const float* col_w, const float* mask, float scale,
+                                 const float* upstream, float* dpred, anemoi_stream_t stream) {
+  if (int rc = check_wmse("anemoi_weighted_mse_backward", pred, target, rows, V, G, row_w, col_w)) return rc;
+  ANEMOI_REQUIRE(upstream && dpred, ANEMOI_ERR_INVALID, "anemoi_weighted_mse_backward: null pointer (upstream / dpred)");
+  const int64_t n = rows * (int64_t)V;
+  if (n == 0) return ANEMOI_OK;
+  hipStream_t st = as_stream(stream);
+  const int vec_ok = aligned16(pred) && aligned16(target) && aligned16(dpred);
+  hipLaunchKernelGGL(weighted_mse_kernel<true>, dim3((unsigned)wmse_blocks(n)), dim3(256), 0, st, pred, target, n,
+                     wmse_chunk(n), G, V, row_w, col_w, mask, scale, upstream, dpred, vec_ok);
+  return trail::note(check_launch("anemoi_weighted_mse_backward"), "anemoi_weighted_mse_backward", "dpred", ANEMOI_F32, dpred,
+                     V, rows, V, st);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // Rollout training ("rollout"): the differentiable state advance between two steps of an autoregressive
-// rollout, the input gradients of the one-pass I/O kernels (anemoi_assemble_nodes / anemoi_finalize_output) and the
-// node-weighted, variable-scaled, masked MSE with its gradient.
+// rollout and the input gradients of the one-pass I/O kernels (anemoi_assemble_nodes / anemoi_finalize_output).  (The loss of
+// a rollout step is in csrc/losses.hip.)
 //
 // All of them are streaming kernels in the style of csrc/elementwise.hip: a flat grid-stride mapping, 16-byte accesses where
 // the rows allow, 32-bit index divisions when the flat index space fits 31 bits.  Every output element is owned by exactly one
@@ -16,8 +16,6 @@ static inline unsigned flat_grid(int64_t total) {
   if (blocks < 1) blocks = 1;
   return (unsigned)blocks;
 }
-
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // ---------------------------------------------------------------------------------------------
 // State advance, out of place.  `slab` = Ens * G * V_in floats of one (b, t); the flat index space is
@@ -198,107 +196,6 @@ __global__ __launch_bounds__(256) void prognostic_residual_backward_kernel(const
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// Weighted MSE.  Flat element i of pred / target [rows, V]: position i % (G * V) of the [G, V] weight / mask plane.
-// One thread walks four consecutive elements (one 16-byte load per operand) and keeps (g, v) by increments.
-// Stage 1: workgroup k reduces the contiguous chunk [k * chunk, (k + 1) * chunk) -- chunk and the workgroup count are functions
-// of rows * V alone (wmse_blocks / wmse_chunk) -- each thread in ascending index order, the wave by the fixed butterfly of
-// wave_sum, the four waves in wave order.  Stage 2: one workgroup sums the partials the same way and applies `scale`.
-// ---------------------------------------------------------------------------------------------
-constexpr int64_t WMSE_PER_BLOCK = 4096;  // elements per workgroup before the workgroup count saturates
-constexpr int64_t WMSE_MAX_BLOCKS = 2048;
-
-static inline int64_t wmse_blocks(int64_t n) {
-  int64_t blocks = (n + WMSE_PER_BLOCK - 1) / WMSE_PER_BLOCK;
-  if (blocks > WMSE_MAX_BLOCKS) blocks = WMSE_MAX_BLOCKS;
-  return blocks < 1 ? 1 : blocks;
-}
-
-static inline int64_t wmse_chunk(int64_t n) {  // a multiple of the 1024 elements one workgroup takes per trip
-  const int64_t blocks = wmse_blocks(n);
-  return ((n + blocks - 1) / blocks + 1023) / 1024 * 1024;
-}
-
-__device__ __forceinline__ float block_sum_256(float v, float* sh4) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((sh4[0] + sh4[1]) + sh4[2]) + sh4[3];
-}
-
-// BACKWARD = false: partial[blockIdx.x] = sum of the chunk's terms.  BACKWARD = true: dpred over the same chunks.
-template <bool BACKWARD>
-__global__ __launch_bounds__(256) void weighted_mse_kernel(const float* __restrict__ pred,
-                                                           const float* __restrict__ target, int64_t n, int64_t chunk,
-                                                           int64_t G, int V, const float* __restrict__ row_w,
-                                                           const float* __restrict__ col_w,
-                                                           const float* __restrict__ mask, float scale,
-                                                           const float* __restrict__ upstream,
-                                                           float* __restrict__ out, int vec_ok) {
-  __shared__ float sh4[4];
-  const int64_t begin = (int64_t)blockIdx.x * chunk;
-  const int64_t end = begin + chunk < n ? begin + chunk : n;
-  const int64_t plane = G * (int64_t)V;  // < 2^31 (checked by the entry point)
-  const bool fits32 = n < ((int64_t)1 << 31);
-  float coef = 0.f;
-  if constexpr (BACKWARD) coef = (*upstream * scale) * 2.0f;
-  float acc = 0.f;
-  for (int64_t i0 = begin + (int64_t)threadIdx.x * 4; i0 < end; i0 += 1024) {
-    int64_t rep, m0;
-    fast_divmod(i0, plane, fits32, rep, m0);
-    unsigned g = (unsigned)m0 / (unsigned)V, v = (unsigned)m0 - g * (unsigned)V;
-    const int cnt = end - i0 < 4 ? (int)(end - i0) : 4;
-    float p[4] = {0.f, 0.f, 0.f, 0.f}, t[4] = {0.f, 0.f, 0.f, 0.f}, r[4];
-    if (cnt == 4 && vec_ok) {
-      VecIO<float, 4>::load(pred + i0, p);
-      VecIO<float, 4>::load(target + i0, t);
-    } else {
-      for (int k = 0; k < cnt; ++k) {
-        p[k] = pred[i0 + k];
-        t[k] = target[i0 + k];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      r[k] = 0.f;
-      if (k < cnt) {
-        const bool keep = mask == nullptr || mask[(int64_t)g * V + v] != 0.f;  // a select: a masked NaN contributes exactly 0
-        const float w = row_w[g] * col_w[v];
-        const float d = p[k] - t[k];
-        if constexpr (BACKWARD) {
-          r[k] = keep ? (coef * w) * d : 0.f;
-        } else {
-          acc += keep ? (w * d) * d : 0.f;
-        }
-        if (++v == (unsigned)V) {
-          v = 0;
-          if (++g == (unsigned)G) g = 0;
-        }
-      }
-    }
-    if constexpr (BACKWARD) {
-      if (cnt == 4 && vec_ok) {
-        VecIO<float, 4>::store(out + i0, r);
-      } else {
-        for (int k = 0; k < cnt; ++k) out[i0 + k] = r[k];
-      }
-    }
-  }
-  if constexpr (!BACKWARD) {
-    const float s = block_sum_256(acc, sh4);
-    if (threadIdx.x == 0) out[blockIdx.x] = s;
-  }
-}
-
-__global__ __launch_bounds__(256) void weighted_mse_finish_kernel(const float* __restrict__ partial, int n_partial,
-                                                                  float scale, float* __restrict__ loss) {
-  __shared__ float sh4[4];
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < n_partial; i += 256) acc += partial[i];
-  const float s = block_sum_256(acc, sh4);
-  if (threadIdx.x == 0) *loss = s * scale;
-}
-
 static int check_state_shape(const char* who, int B, int T, int Ens, int64_t G, int V_in, int V_out) {
   ANEMOI_REQUIRE(B > 0 && T > 0 && Ens > 0 && G >= 0 && V_in > 0 && V_out > 0, ANEMOI_ERR_INVALID,
                  "%s: bad shape B=%d T=%d Ens=%d G=%lld V_in=%d V_out=%d", who, B, T, Ens, (long long)G, V_in, V_out);
@@ -406,62 +303,6 @@ int anemoi_prognostic_residual_backward(const float* dy, int V_out, float* dx, i
                        slab, V_in, src);
   return trail::note(check_launch("anemoi_prognostic_residual_backward"), "anemoi_prognostic_residual_backward", "dx",
                      ANEMOI_F32, dx, V_in, (int64_t)B * T * Ens * G, V_in, st);
-}
-
-int64_t anemoi_weighted_mse_workspace_floats(int64_t rows, int V) {
-  if (rows <= 0 || V <= 0) return 0;
-  return wmse_blocks(rows * (int64_t)V);
-}
-
-static int check_wmse(const char* who, const float* pred, const float* target, int64_t rows, int V, int64_t G,
-                      const float* row_w, const float* col_w) {
-  ANEMOI_REQUIRE(pred && target && row_w && col_w, ANEMOI_ERR_INVALID, "%s: null pointer", who);
-  ANEMOI_REQUIRE(rows >= 0 && V > 0 && G > 0, ANEMOI_ERR_INVALID, "%s: bad shape rows=%lld V=%d G=%lld", who,
-                 (long long)rows, V, (long long)G);
-  ANEMOI_REQUIRE(rows % G == 0, ANEMOI_ERR_INVALID, "%s: rows %lld is not a multiple of the grid size G = %lld", who,
-                 (long long)rows, (long long)G);
-  ANEMOI_REQUIRE(G * (int64_t)V < ((int64_t)1 << 31), ANEMOI_ERR_UNSUPPORTED, "%s: G * V does not fit 31 bits", who);
-  return ANEMOI_OK;
-}
-
-int anemoi_weighted_mse(const float* pred, const float* target, int64_t rows, int V, int64_t G, const float* row_w,
-                        const float* col_w, const float* mask, float scale, float* loss, float* workspace,
-                        int64_t workspace_floats, anemoi_stream_t stream) {
-  if (int rc = check_wmse("anemoi_weighted_mse", pred, target, rows, V, G, row_w, col_w)) return rc;
-  ANEMOI_REQUIRE(loss != nullptr, ANEMOI_ERR_INVALID, "anemoi_weighted_mse: null pointer (loss)");
-  hipStream_t st = as_stream(stream);
-  const int64_t n = rows * (int64_t)V;
-  if (n == 0) {
-    hipError_t e = hipMemsetAsync(loss, 0, sizeof(float), st);
-    if (e != hipSuccess) return fail(ANEMOI_ERR_LAUNCH, "anemoi_weighted_mse: %s", hipGetErrorString(e));
-    return ANEMOI_OK;
-  }
-  const int64_t blocks = wmse_blocks(n);
-  ANEMOI_REQUIRE(workspace != nullptr && workspace_floats >= blocks, ANEMOI_ERR_INVALID,
-                 "anemoi_weighted_mse: workspace of %lld floats, %lld needed", (long long)workspace_floats,
-                 (long long)blocks);
-  const int vec_ok = aligned16(pred) && aligned16(target);
-  hipLaunchKernelGGL(weighted_mse_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, pred, target, n, wmse_chunk(n), G,
-                     V, row_w, col_w, mask, scale, (const float*)nullptr, workspace, vec_ok);
-  hipLaunchKernelGGL(weighted_mse_finish_kernel, dim3(1), dim3(256), 0, st, workspace, (int)blocks, scale, loss);
-  int rc = trail::note(check_launch("anemoi_weighted_mse"), "anemoi_weighted_mse", "partials", ANEMOI_F32, workspace, blocks,
-                       1, blocks, st);
-  return trail::note(rc, "anemoi_weighted_mse", "loss", ANEMOI_F32, loss, 1, 1, 1, st);
-}
-
-int anemoi_weighted_mse_backward(const float* pred, const float* target, int64_t rows, int V, int64_t G,
-                                 const float* row_w, const float* col_w, const float* mask, float scale,
-                                 const float* upstream, float* dpred, anemoi_stream_t stream) {
-  if (int rc = check_wmse("anemoi_weighted_mse_backward", pred, target, rows, V, G, row_w, col_w)) return rc;
-  ANEMOI_REQUIRE(upstream && dpred, ANEMOI_ERR_INVALID, "anemoi_weighted_mse_backward: null pointer (upstream / dpred)");
-  const int64_t n = rows * (int64_t)V;
-  if (n == 0) return ANEMOI_OK;
-  hipStream_t st = as_stream(stream);
-  const int vec_ok = aligned16(pred) && aligned16(target) && aligned16(dpred);
-  hipLaunchKernelGGL(weighted_mse_kernel<true>, dim3((unsigned)wmse_blocks(n)), dim3(256), 0, st, pred, target, n,
-                     wmse_chunk(n), G, V, row_w, col_w, mask, scale, upstream, dpred, vec_ok);
-  return trail::note(check_launch("anemoi_weighted_mse_backward"), "anemoi_weighted_mse_backward", "dpred", ANEMOI_F32, dpred,
-                     V, rows, V, st);
 }
 
 }  // extern "C"

@@ -27,6 +27,14 @@ from torch import nn
 from . import autograd
 
 
+def _normalised_node_weights(name: str, node_weights) -> Tensor:
+    """``w / sum(w)`` as float32, for the class ``name``."""
+    w = torch.as_tensor(node_weights).detach().double().reshape(-1)
+    if w.numel() == 0 or not bool((w >= 0).all()) or float(w.sum()) <= 0:
+        raise ValueError(f"{name}: node_weights must be non-negative with a positive sum")
+    return (w / w.sum()).float()
+
+
 class _NodeWeightedLoss(nn.Module):
     """Node weights ``w^ = w / sum(w)``, optional per-variable weights, and the per-variable form shared by the family."""
 
@@ -35,10 +43,7 @@ class _NodeWeightedLoss(nn.Module):
 
     def __init__(self, node_weights: Tensor, variable_weights: Optional[Tensor] = None) -> None:
         super().__init__()
-        w = torch.as_tensor(node_weights).detach().double().reshape(-1)
-        if w.numel() == 0 or not bool((w >= 0).all()) or float(w.sum()) <= 0:
-            raise ValueError(f"{type(self).__name__}: node_weights must be non-negative with a positive sum")
-        self.register_buffer("node_weights", (w / w.sum()).float(), persistent=False)
+        self.register_buffer("node_weights", _normalised_node_weights(type(self).__name__, node_weights), persistent=False)
         s = None if variable_weights is None else torch.as_tensor(variable_weights).detach().float().reshape(-1).clone()
         self.register_buffer("variable_weights", s, persistent=False)
 
@@ -143,9 +148,9 @@ class WeightedRMSELoss(_NodeWeightedLoss):
 METRIC_KINDS = ("mse", "mae", "huber", "logcosh", "rmse")
 
 
-def _output_diff_scale(normalizer, n_vars: Optional[int] = None) -> Optional[Tensor]:
+def _output_diff_scale(name: str, normalizer, n_vars: Optional[int] = None) -> Optional[Tensor]:
     """``1 / _norm_mul`` at the model-output variables of an ``InputNormalizer`` (or of a ``Processors`` container that holds
-    nothing else): the scale that takes a difference of normalised values to physical units."""
+    nothing else): the scale that takes a difference of normalised values to physical units.  ``name``: the calling class."""
     from .preprocessing import Processors
     from .preprocessing.normalizer import InputNormalizer
 
@@ -155,21 +160,48 @@ def _output_diff_scale(normalizer, n_vars: Optional[int] = None) -> Optional[Ten
     other = [type(p).__name__ for p in procs if not isinstance(p, InputNormalizer)]
     if other or len(procs) != 1:
         raise NotImplementedError(
-            f"ValidationMetrics: only one affine InputNormalizer can be folded into the metric kernel (its additive term "
+            f"{name}: only one affine InputNormalizer can be folded into the metric kernel (its additive term "
             f"cancels in pred - target); got {[type(p).__name__ for p in procs]} -- an imputer or remapper is not affine")
     norm = procs[0]
     mul = norm._norm_mul.detach().double()
     if n_vars is None or n_vars == norm._output_idx.numel():
         mul = mul[norm._output_idx.long()]
     elif n_vars != mul.numel():
-        raise ValueError(f"ValidationMetrics: {n_vars} variables, the normaliser has {norm._output_idx.numel()} output and "
+        raise ValueError(f"{name}: {n_vars} variables, the normaliser has {norm._output_idx.numel()} output and "
                          f"{mul.numel()} data variables")
     if bool((mul == 0).any()) or not bool(torch.isfinite(mul).all()):
-        raise ValueError("ValidationMetrics: the normaliser has a zero or non-finite _norm_mul: it cannot be inverted")
+        raise ValueError(f"{name}: the normaliser has a zero or non-finite _norm_mul: it cannot be inverted")
     return (1.0 / mul).float()
 
 
-class ValidationMetrics(nn.Module):
+class _PhysicalMetrics(nn.Module):
+    """What the metrics classes share: normalised node weights, ``1 / _norm_mul`` of the normaliser as the kernel's per-variable
+    scale of the difference, and the variable groups with their means."""
+
+    def __init__(self, node_weights: Tensor, normalizer, groups: Optional[Mapping[str, Sequence[int]]]) -> None:
+        super().__init__()
+        name = type(self).__name__
+        self.register_buffer("node_weights", _normalised_node_weights(name, node_weights), persistent=False)
+        self.register_buffer("diff_scale", _output_diff_scale(name, normalizer), persistent=False)
+        self.groups = {str(k): [int(i) for i in idx] for k, idx in (groups or {}).items()}
+        if any(len(idx) == 0 for idx in self.groups.values()):
+            raise ValueError(f"{name}: an empty variable group")
+
+    def _diff_scale_for(self, v: int, device) -> Optional[Tensor]:
+        """``diff_scale`` on ``device``, after the per-call checks against the ``v`` variables of a ``pred``."""
+        name, c = type(self).__name__, self.diff_scale
+        if c is not None and c.numel() != v:
+            raise ValueError(f"{name}: {v} variables, the normaliser has {c.numel()} output variables")
+        if any(i < 0 or i >= v for idx in self.groups.values() for i in idx):
+            raise ValueError(f"{name}: a group index is not one of the {v} output variables")
+        return None if c is None else c.to(device)
+
+    def _add_group_means(self, out: dict, key: str) -> None:
+        for name, idx in self.groups.items():
+            out[f"{key}/{name}"] = out[key][:, idx].mean(-1)
+
+
+class ValidationMetrics(_PhysicalMetrics):
     """Per-variable validation metrics in physical (de-normalised) units for every rollout step.
 
     ``forward(pred, target, mask=None)`` takes the normalised ``[n_steps, B, Ens, G, V]`` model output and target (or ``[B,
@@ -182,21 +214,13 @@ class ValidationMetrics(nn.Module):
 
     def __init__(self, node_weights: Tensor, normalizer=None, groups: Optional[Mapping[str, Sequence[int]]] = None,
                  kinds: Sequence[str] = ("mse",), delta: float = 1.0) -> None:
-        super().__init__()
-        w = torch.as_tensor(node_weights).detach().double().reshape(-1)
-        if w.numel() == 0 or not bool((w >= 0).all()) or float(w.sum()) <= 0:
-            raise ValueError("ValidationMetrics: node_weights must be non-negative with a positive sum")
-        self.register_buffer("node_weights", (w / w.sum()).float(), persistent=False)
+        super().__init__(node_weights, normalizer, groups)
         bad = [k for k in kinds if k not in METRIC_KINDS]
         if bad or not kinds:
             raise ValueError(f"ValidationMetrics: unknown kinds {bad} (from {METRIC_KINDS})")
         if not float(delta) > 0:
             raise ValueError(f"ValidationMetrics: delta must be positive, got {delta}")
         self.kinds, self.delta = tuple(kinds), float(delta)
-        self.register_buffer("diff_scale", _output_diff_scale(normalizer), persistent=False)
-        self.groups = {str(k): [int(i) for i in idx] for k, idx in (groups or {}).items()}
-        if any(len(idx) == 0 for idx in self.groups.values()):
-            raise ValueError("ValidationMetrics: an empty variable group")
 
     @torch.no_grad()
     def forward(self, pred: Tensor, target: Tensor, mask: Optional[Tensor] = None) -> dict:
@@ -207,23 +231,17 @@ class ValidationMetrics(nn.Module):
             raise ValueError(f"ValidationMetrics: pred {tuple(pred.shape)} / target {tuple(target.shape)} must be "
                              f"[n_steps, B, Ens, G = {g}, V] (or without the step axis)")
         n_steps, v = pred.shape[0], pred.shape[-1]
-        c = self.diff_scale
-        if c is not None and c.numel() != v:
-            raise ValueError(f"ValidationMetrics: {v} variables, the normaliser has {c.numel()} output variables")
-        if any(i < 0 or i >= v for idx in self.groups.values() for i in idx):
-            raise ValueError(f"ValidationMetrics: a group index is not one of the {v} output variables")
+        c = self._diff_scale_for(v, pred.device)
         n_avg = max(pred.shape[1] * pred.shape[2], 1)
         out = {}
         for kind in self.kinds:
             per_var = autograd.weighted_error(pred, target, self.node_weights.to(pred.device),
                                               "mse" if kind == "rmse" else kind, delta=self.delta, mask=mask,
-                                              diff_scale=None if c is None else c.to(pred.device), n_groups=n_steps,
-                                              scale=1.0 / n_avg)
+                                              diff_scale=c, n_groups=n_steps, scale=1.0 / n_avg)
             if kind == "rmse":
                 per_var = per_var.sqrt()
             out[kind] = per_var
-            for name, idx in self.groups.items():
-                out[f"{kind}/{name}"] = per_var[:, idx].mean(-1)
+            self._add_group_means(out, kind)
         return out
 
 
@@ -281,7 +299,7 @@ class KernelCRPS(AlmostFairKernelCRPS):
         self.fair = bool(fair)
 
 
-class EnsembleMetrics(nn.Module):
+class EnsembleMetrics(_PhysicalMetrics):
     """Per-variable ensemble scores in physical (de-normalised) units for every rollout step.
 
     ``forward(pred, target, mask=None)`` takes the normalised ``[n_steps, B, E, G, V]`` ensemble and its ``[n_steps, B, G, V]``
@@ -300,18 +318,10 @@ class EnsembleMetrics(nn.Module):
 
     def __init__(self, node_weights: Tensor, normalizer=None, groups: Optional[Mapping[str, Sequence[int]]] = None,
                  alpha: float = 1.0) -> None:
-        super().__init__()
-        w = torch.as_tensor(node_weights).detach().double().reshape(-1)
-        if w.numel() == 0 or not bool((w >= 0).all()) or float(w.sum()) <= 0:
-            raise ValueError("EnsembleMetrics: node_weights must be non-negative with a positive sum")
-        self.register_buffer("node_weights", (w / w.sum()).float(), persistent=False)
+        super().__init__(node_weights, normalizer, groups)
         if not 0.0 <= float(alpha) <= 1.0:
             raise ValueError(f"EnsembleMetrics: alpha must lie in [0, 1], got {alpha}")
         self.alpha = float(alpha)
-        self.register_buffer("diff_scale", _output_diff_scale(normalizer), persistent=False)
-        self.groups = {str(k): [int(i) for i in idx] for k, idx in (groups or {}).items()}
-        if any(len(idx) == 0 for idx in self.groups.values()):
-            raise ValueError("EnsembleMetrics: an empty variable group")
 
     @torch.no_grad()
     def forward(self, pred: Tensor, target: Tensor, mask: Optional[Tensor] = None) -> dict:
@@ -323,12 +333,7 @@ class EnsembleMetrics(nn.Module):
             raise ValueError(f"EnsembleMetrics: pred {tuple(pred.shape)} / target {tuple(target.shape)} must be "
                              f"[n_steps, B, E, G = {g}, V] / [n_steps, B, G, V] (or both without the step axis)")
         n_steps, e, v = pred.shape[0], pred.shape[2], pred.shape[-1]
-        c = self.diff_scale
-        if c is not None and c.numel() != v:
-            raise ValueError(f"EnsembleMetrics: {v} variables, the normaliser has {c.numel()} output variables")
-        if any(i < 0 or i >= v for idx in self.groups.values() for i in idx):
-            raise ValueError(f"EnsembleMetrics: a group index is not one of the {v} output variables")
-        kw = dict(alpha=self.alpha, mask=mask, diff_scale=None if c is None else c.to(pred.device), n_groups=n_steps,
+        kw = dict(alpha=self.alpha, mask=mask, diff_scale=self._diff_scale_for(v, pred.device), n_groups=n_steps,
                   scale=1.0 / max(pred.shape[1], 1))
         w = self.node_weights.to(pred.device)
         out = {"crps": autograd.ensemble_score(pred, target, w, "afcrps", **kw),
@@ -336,6 +341,5 @@ class EnsembleMetrics(nn.Module):
                "spread": autograd.ensemble_score(pred, target, w, "variance", **kw).sqrt()}
         out["spread_skill"] = math.sqrt((e + 1) / e) * out["spread"] / out["ens_rmse"]
         for key in self.KEYS:
-            for name, idx in self.groups.items():
-                out[f"{key}/{name}"] = out[key][:, idx].mean(-1)
+            self._add_group_means(out, key)
         return out

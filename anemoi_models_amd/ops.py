@@ -1070,45 +1070,71 @@ def csr_project(x: Tensor, out: Tensor, indptr: Tensor, idx: Tensor, val: Tensor
     return out
 
 
-def _wmse_args(who: str, pred: Tensor, target: Tensor, row_w: Tensor, col_w: Tensor, mask: Optional[Tensor]):
-    _dev(pred, target, row_w, col_w, mask)
+def _loss_operands(who: str, pred: Tensor, target: Tensor, row_w: Tensor, col_w: Optional[Tensor], mask: Optional[Tensor],
+                   diff_scale: Optional[Tensor] = None, n_groups: Optional[int] = None, *, ensemble: bool = False,
+                   upstream: Optional[Tensor] = None):
+    """The operand check of the loss entry points: every operand on the device, float32 and contiguous, ``pred`` / ``target``
+    ``[rows, V]`` (``ensemble``: only ``target``; its caller relates ``pred`` to it), ``col_w`` / ``diff_scale`` ``[V]``, ``mask``
+    ``[G, V]``, ``rows`` in ``n_groups >= 1`` groups of a multiple of ``G = len(row_w) >= 1`` and ``upstream`` ``[n_groups, V]``.
+    ``n_groups = None`` is the scalar ``weighted_mse``: no groups, ``upstream`` one value.  Returns ``rows, V, G, n_groups``."""
+    _dev(pred, target, row_w, col_w, mask, diff_scale)
     _rows(pred)
-    if pred.shape != target.shape or not pred.is_contiguous() or not target.is_contiguous():
+    if ensemble:
+        _rows(target)
+    elif pred.shape != target.shape or not pred.is_contiguous() or not target.is_contiguous():
         raise ValueError(f"{who}: pred and target must be contiguous [rows, V] of one shape")
-    tensors = [pred, target, row_w, col_w] + ([] if mask is None else [mask])
+    tensors = [t for t in (pred, target, row_w, col_w, mask, diff_scale) if t is not None]
     if any(t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
         raise ValueError(f"{who}: every operand must be contiguous float32")
-    rows, v = pred.shape
+    rows, v = target.shape
     g = row_w.numel()
-    if col_w.numel() != v or (mask is not None and tuple(mask.shape) != (g, v)):
-        raise ValueError(f"{who}: col_w [V] / mask [G, V] do not match pred {tuple(pred.shape)} and row_w [{g}]")
-    return rows, v, g
+    if any(t is not None and t.numel() != v for t in (col_w, diff_scale)) or (mask is not None and tuple(mask.shape) != (g, v)):
+        names = "col_w [V] / mask [G, V]" if n_groups is None else "col_w [V] / diff_scale [V] / mask [G, V]"
+        raise ValueError(f"{who}: {names} do not match {'target' if ensemble else 'pred'} {tuple(target.shape)} and row_w [{g}]")
+    if n_groups is not None:
+        n_groups = int(n_groups)
+        if n_groups < 1 or g < 1 or rows % (n_groups * g) != 0:
+            raise ValueError(f"{who}: {rows} {'target ' if ensemble else ''}rows are not {n_groups} groups of a multiple of "
+                             f"G = {g} rows")
+    if upstream is not None:
+        _dev(upstream)
+        if n_groups is None and (upstream.dtype != torch.float32 or upstream.numel() != 1):
+            raise ValueError(f"{who}: upstream must be one float32 value on the device")
+        if n_groups is not None and (upstream.dtype != torch.float32 or not upstream.is_contiguous()
+                                     or tuple(upstream.shape) != (n_groups, v)):
+            raise ValueError(f"{who}: upstream must be contiguous float32 [{n_groups}, {v}] on the device")
+    return rows, v, g, n_groups
+
+
+def _loss_forward(name: str, ws_args: tuple, head: tuple, pred: Tensor, target: Tensor, tail: tuple, out: Tensor) -> Tensor:
+    """The forward launch of the loss entry points ``anemoi_<name>(*head, pred, target, *tail, out, workspace, workspace_floats,
+    stream)``: ask the library for the workspace size, allocate it, run, check.  (The workspace stands in for an empty
+    operand, whose pointer is null.)"""
+    lib = _lib.load()
+    n_ws = getattr(lib, f"anemoi_{name}_workspace_floats")(*ws_args)
+    ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=out.device)
+    with _Timed(name, bytes=(pred.numel() + target.numel()) * 4):
+        st = getattr(lib, f"anemoi_{name}")(*head, _ptr(pred) or ws.data_ptr(), _ptr(target) or ws.data_ptr(), *tail,
+                                            out.data_ptr(), ws.data_ptr(), n_ws, _stream())
+    _lib.check(st, f"anemoi_{name}")
+    return out
 
 
 def weighted_mse(pred: Tensor, target: Tensor, row_w: Tensor, col_w: Tensor, mask: Optional[Tensor] = None,
                  scale: float = 1.0) -> Tensor:
     """``scale * sum keep * row_w[r % G] * col_w[v] * (pred - target)^2`` as an f32 device scalar (``[rows, V]`` operands,
     ``rows`` a multiple of ``G = len(row_w)``; ``mask`` ``[G, V]``, kept where non-zero): deterministic two-stage reduction."""
-    rows, v, g = _wmse_args("weighted_mse", pred, target, row_w, col_w, mask)
-    lib = _lib.load()
+    rows, v, g, _ = _loss_operands("weighted_mse", pred, target, row_w, col_w, mask)
     loss = torch.empty((), dtype=torch.float32, device=pred.device)
-    n_ws = lib.anemoi_weighted_mse_workspace_floats(rows, v)
-    ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=pred.device)
-    with _Timed("weighted_mse", bytes=2 * pred.numel() * 4):
-        st = lib.anemoi_weighted_mse(_ptr(pred) or ws.data_ptr(), _ptr(target) or ws.data_ptr(), rows, v, g, row_w.data_ptr(),
-                                     col_w.data_ptr(), _ptr(mask), float(scale), loss.data_ptr(), ws.data_ptr(), n_ws, _stream())
-    _lib.check(st, "anemoi_weighted_mse")
-    return loss
+    return _loss_forward("weighted_mse", (rows, v), (), pred, target,
+                         (rows, v, g, row_w.data_ptr(), col_w.data_ptr(), _ptr(mask), float(scale)), loss)
 
 
 def weighted_mse_backward(pred: Tensor, target: Tensor, row_w: Tensor, col_w: Tensor, mask: Optional[Tensor], scale: float,
                           upstream: Tensor) -> Tensor:
     """``d loss / d pred`` of :func:`weighted_mse`; ``upstream`` is the f32 DEVICE scalar gradient of the loss (read by the
     kernel: no host synchronisation)."""
-    rows, v, g = _wmse_args("weighted_mse_backward", pred, target, row_w, col_w, mask)
-    _dev(upstream)
-    if upstream.dtype != torch.float32 or upstream.numel() != 1:
-        raise ValueError("weighted_mse_backward: upstream must be one float32 value on the device")
+    rows, v, g, _ = _loss_operands("weighted_mse_backward", pred, target, row_w, col_w, mask, upstream=upstream)
     dpred = torch.empty_like(pred)
     if rows == 0:
         return dpred
@@ -1120,25 +1146,13 @@ def weighted_mse_backward(pred: Tensor, target: Tensor, row_w: Tensor, col_w: Te
 
 
 def _werr_args(who: str, pred: Tensor, target: Tensor, row_w: Tensor, kind: str, delta: float, col_w: Optional[Tensor],
-               mask: Optional[Tensor], diff_scale: Optional[Tensor], n_groups: int):
-    _dev(pred, target, row_w, col_w, mask, diff_scale)
-    _rows(pred)
-    if pred.shape != target.shape or not pred.is_contiguous() or not target.is_contiguous():
-        raise ValueError(f"{who}: pred and target must be contiguous [rows, V] of one shape")
-    tensors = [t for t in (pred, target, row_w, col_w, mask, diff_scale) if t is not None]
-    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
-        raise ValueError(f"{who}: every operand must be contiguous float32")
+               mask: Optional[Tensor], diff_scale: Optional[Tensor], n_groups: int, upstream: Optional[Tensor] = None):
+    shape = _loss_operands(who, pred, target, row_w, col_w, mask, diff_scale, n_groups, upstream=upstream)
     if kind not in _lib.LOSS_KINDS:
         raise ValueError(f"{who}: unknown kind {kind!r} (one of {sorted(_lib.LOSS_KINDS)})")
     if kind == "huber" and not float(delta) > 0:
         raise ValueError(f"{who}: the Huber delta must be positive, got {delta}")
-    rows, v = pred.shape
-    g, n_groups = row_w.numel(), int(n_groups)
-    if any(t is not None and t.numel() != v for t in (col_w, diff_scale)) or (mask is not None and tuple(mask.shape) != (g, v)):
-        raise ValueError(f"{who}: col_w [V] / diff_scale [V] / mask [G, V] do not match pred {tuple(pred.shape)} and row_w [{g}]")
-    if n_groups < 1 or g < 1 or rows % (n_groups * g) != 0:
-        raise ValueError(f"{who}: {rows} rows are not {n_groups} groups of a multiple of G = {g} rows")
-    return rows, v, g, n_groups, _lib.LOSS_KINDS[kind]
+    return (*shape, _lib.LOSS_KINDS[kind])
 
 
 def weighted_error(pred: Tensor, target: Tensor, row_w: Tensor, kind: str, *, delta: float = 1.0,
@@ -1148,16 +1162,9 @@ def weighted_error(pred: Tensor, target: Tensor, row_w: Tensor, kind: str, *, de
     ``[n_groups, V]`` (``[rows, V]`` operands in ``n_groups`` equal groups of consecutive rows, each a multiple of ``G =
     len(row_w)``; ``kind`` one of mse / mae / huber / logcosh): deterministic two-stage reduction, no atomics."""
     rows, v, g, n_groups, code = _werr_args("weighted_error", pred, target, row_w, kind, delta, col_w, mask, diff_scale, n_groups)
-    lib = _lib.load()
     out = torch.empty((n_groups, v), dtype=torch.float32, device=pred.device)
-    n_ws = lib.anemoi_weighted_error_workspace_floats(n_groups, rows // n_groups, v)
-    ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=pred.device)
-    with _Timed("weighted_error", bytes=2 * pred.numel() * 4):
-        st = lib.anemoi_weighted_error(code, float(delta), _ptr(pred) or ws.data_ptr(), _ptr(target) or ws.data_ptr(), rows, v,
-                                       g, n_groups, row_w.data_ptr(), _ptr(col_w), _ptr(mask), _ptr(diff_scale), float(scale),
-                                       out.data_ptr(), ws.data_ptr(), n_ws, _stream())
-    _lib.check(st, "anemoi_weighted_error")
-    return out
+    return _loss_forward("weighted_error", (n_groups, rows // n_groups, v), (code, float(delta)), pred, target,
+                         (rows, v, g, n_groups, row_w.data_ptr(), _ptr(col_w), _ptr(mask), _ptr(diff_scale), float(scale)), out)
 
 
 def weighted_error_backward(pred: Tensor, target: Tensor, row_w: Tensor, kind: str, *, delta: float = 1.0,
@@ -1167,10 +1174,7 @@ def weighted_error_backward(pred: Tensor, target: Tensor, row_w: Tensor, kind: s
     """``d (sum upstream * out) / d pred`` of :func:`weighted_error`; ``upstream`` is the f32 DEVICE ``[n_groups, V]`` gradient
     of its result (read by the kernel: no host synchronisation)."""
     rows, v, g, n_groups, code = _werr_args("weighted_error_backward", pred, target, row_w, kind, delta, col_w, mask,
-                                            diff_scale, n_groups)
-    _dev(upstream)
-    if upstream.dtype != torch.float32 or not upstream.is_contiguous() or tuple(upstream.shape) != (n_groups, v):
-        raise ValueError(f"weighted_error_backward: upstream must be contiguous float32 [{n_groups}, {v}] on the device")
+                                            diff_scale, n_groups, upstream)
     dpred = torch.empty_like(pred)
     if rows == 0:
         return dpred
@@ -1183,13 +1187,10 @@ def weighted_error_backward(pred: Tensor, target: Tensor, row_w: Tensor, kind: s
 
 
 def _ens_args(who: str, pred: Tensor, target: Tensor, row_w: Tensor, kind: str, n_members: int, alpha: float,
-              col_w: Optional[Tensor], mask: Optional[Tensor], diff_scale: Optional[Tensor], n_groups: int):
-    _dev(pred, target, row_w, col_w, mask, diff_scale)
-    _rows(pred)
-    _rows(target)
-    tensors = [t for t in (pred, target, row_w, col_w, mask, diff_scale) if t is not None]
-    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
-        raise ValueError(f"{who}: every operand must be contiguous float32")
+              col_w: Optional[Tensor], mask: Optional[Tensor], diff_scale: Optional[Tensor], n_groups: int,
+              upstream: Optional[Tensor] = None):
+    rows, v, g, n_groups = _loss_operands(who, pred, target, row_w, col_w, mask, diff_scale, n_groups, ensemble=True,
+                                          upstream=upstream)
     if kind not in _lib.ENS_KINDS:
         raise ValueError(f"{who}: unknown kind {kind!r} (one of {sorted(_lib.ENS_KINDS)})")
     e = int(n_members)
@@ -1199,16 +1200,9 @@ def _ens_args(who: str, pred: Tensor, target: Tensor, row_w: Tensor, kind: str, 
         raise NotImplementedError(f"{who}: n_members = {e}, at most {_lib.ENS_MAX_MEMBERS}")
     if not 0.0 <= float(alpha) <= 1.0:
         raise ValueError(f"{who}: alpha must lie in [0, 1], got {alpha}")
-    rows, v = target.shape
     if pred.shape[1] != v or pred.shape[0] != rows * e:
         raise ValueError(f"{who}: pred {tuple(pred.shape)} is not [rows * n_members, V] of target {tuple(target.shape)} with "
                          f"n_members = {e}")
-    g, n_groups = row_w.numel(), int(n_groups)
-    if any(t is not None and t.numel() != v for t in (col_w, diff_scale)) or (mask is not None and tuple(mask.shape) != (g, v)):
-        raise ValueError(f"{who}: col_w [V] / diff_scale [V] / mask [G, V] do not match target {tuple(target.shape)} and "
-                         f"row_w [{g}]")
-    if n_groups < 1 or g < 1 or rows % (n_groups * g) != 0:
-        raise ValueError(f"{who}: {rows} target rows are not {n_groups} groups of a multiple of G = {g} rows")
     return rows, v, g, e, n_groups, _lib.ENS_KINDS[kind]
 
 
@@ -1221,16 +1215,9 @@ def ensemble_score(pred: Tensor, target: Tensor, row_w: Tensor, kind: str, *, n_
     two-stage reduction, no atomics, every member read once."""
     rows, v, g, e, n_groups, code = _ens_args("ensemble_score", pred, target, row_w, kind, n_members, alpha, col_w, mask,
                                               diff_scale, n_groups)
-    lib = _lib.load()
     out = torch.empty((n_groups, v), dtype=torch.float32, device=target.device)
-    n_ws = lib.anemoi_ensemble_score_workspace_floats(n_groups, rows // n_groups, v, e)
-    ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=target.device)
-    with _Timed("ensemble_score", bytes=(pred.numel() + target.numel()) * 4):
-        st = lib.anemoi_ensemble_score(code, float(alpha), _ptr(pred) or ws.data_ptr(), _ptr(target) or ws.data_ptr(), rows, v,
-                                       g, e, n_groups, row_w.data_ptr(), _ptr(col_w), _ptr(mask), _ptr(diff_scale),
-                                       float(scale), out.data_ptr(), ws.data_ptr(), n_ws, _stream())
-    _lib.check(st, "anemoi_ensemble_score")
-    return out
+    return _loss_forward("ensemble_score", (n_groups, rows // n_groups, v, e), (code, float(alpha)), pred, target,
+                         (rows, v, g, e, n_groups, row_w.data_ptr(), _ptr(col_w), _ptr(mask), _ptr(diff_scale), float(scale)), out)
 
 
 def ensemble_score_backward(pred: Tensor, target: Tensor, row_w: Tensor, kind: str, *, n_members: int, alpha: float = 1.0,
@@ -1240,10 +1227,7 @@ def ensemble_score_backward(pred: Tensor, target: Tensor, row_w: Tensor, kind: s
     """``d (sum upstream * out) / d pred`` of :func:`ensemble_score` (afcrps only); ``upstream`` is the f32 DEVICE ``[n_groups,
     V]`` gradient of its result (read by the kernel: no host synchronisation).  The target gets no gradient."""
     rows, v, g, e, n_groups, code = _ens_args("ensemble_score_backward", pred, target, row_w, kind, n_members, alpha, col_w,
-                                              mask, diff_scale, n_groups)
-    _dev(upstream)
-    if upstream.dtype != torch.float32 or not upstream.is_contiguous() or tuple(upstream.shape) != (n_groups, v):
-        raise ValueError(f"ensemble_score_backward: upstream must be contiguous float32 [{n_groups}, {v}] on the device")
+                                              mask, diff_scale, n_groups, upstream)
     dpred = torch.empty_like(pred)
     if rows == 0 and code == _lib.ENS_AFCRPS:
         return dpred

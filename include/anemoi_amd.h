@@ -383,8 +383,9 @@ int anemoi_advance_input(float* x, int B, int T, int Ens, int64_t G, int V_in, c
 /*
  * Rollout training (ABI v47, csrc/rollout.hip): the differentiable state advance between two steps of a training rollout
  * (anemoi-training sums a loss over the steps and lets the gradient flow through `advance_input`), the input gradients of
- * the one-pass I/O kernels above, and the rollout loss.  Every output element is owned by exactly one thread: no atomics, the
- * same bits on every run.  Outputs named "in full" are written completely (no zero-fill by the caller).
+ * the one-pass I/O kernels above, and the rollout loss (anemoi_weighted_mse below, csrc/losses.hip).  Every output element is
+ * owned by exactly one thread: no atomics, the same bits on every run.  Outputs named "in full" are written completely (no
+ * zero-fill by the caller).
  *
  * anemoi_advance_state: the out-of-place form of anemoi_advance_input -- x_out (f32 [B, T, Ens, G, V_in], must not overlap
  * x_in) receives what anemoi_advance_input would leave in a copy of x_in; same colmap / forcing / persist semantics, the
@@ -445,8 +446,9 @@ int anemoi_csr_project(const float* x, int64_t ldx, int64_t xs_outer, int64_t xs
                        anemoi_stream_t stream);
 
 /*
- * Node-weighted, variable-scaled, masked squared error over pred / target (f32 [rows, V] contiguous; rows is a multiple of G
- * and row r belongs to grid node r % G, so a stack of rollout steps, batch and ensemble members is one call):
+ * The rollout loss (csrc/losses.hip, with the loss family below): node-weighted, variable-scaled, masked squared error over
+ * pred / target (f32 [rows, V] contiguous; rows is a multiple of G and row r belongs to grid node r % G, so a stack of rollout
+ * steps, batch and ensemble members is one call):
  *   loss = scale * sum_{r, v} keep(r, v) ? row_w[r % G] * col_w[v] * (pred - target)^2 : 0
  * row_w f32 [G], col_w f32 [V], mask f32 [G, V] or NULL, keep = mask[r % G, v] != 0.  The mask is a SELECT: a masked element
  * contributes exactly 0 even where pred or target is NaN (imputed values); an unmasked NaN propagates.  Two deterministic
@@ -468,9 +470,9 @@ int anemoi_weighted_mse_backward(const float* pred, const float* target, int64_t
                                  const float* upstream, float* dpred, anemoi_stream_t stream);
 
 /*
- * The loss family: per-variable node-weighted error over pred / target (f32 [rows, V] contiguous), one value per group of rows
- * and variable.  rows = n_groups * rows_per_group with rows_per_group a multiple of G; group l is the rows
- * [l * rows_per_group, (l + 1) * rows_per_group) (a rollout step; n_groups = 1: the whole tensor), row r is grid node r % G:
+ * The loss family (ABI v48, csrc/losses.hip): per-variable node-weighted error over pred / target (f32 [rows, V] contiguous),
+ * one value per group of rows and variable.  rows = n_groups * rows_per_group with rows_per_group a multiple of G; group l is
+ * the rows [l * rows_per_group, (l + 1) * rows_per_group) (a rollout step; n_groups = 1: the whole tensor), row r is grid node r % G:
  *   out[l, v] = scale * sum_{r in group l} keep(r, v) ? row_w[r % G] * col_w[v] * f(c[v] * (pred[r, v] - target[r, v])) : 0
  * row_w f32 [G]; col_w f32 [V] or NULL (ones); mask f32 [G, V] or NULL, keep = mask[r % G, v] != 0, a SELECT as in
  * anemoi_weighted_mse; diff_scale c f32 [V] or NULL (ones): the per-variable scale of the difference (de-normalisation).
