@@ -820,7 +820,19 @@ __global__ __launch_bounds__(256) void mhsa_bf16_w4_kernel(const bf16_t* __restr
   for (int qb = 0; qb < W4_QB; ++qb) {
     // (the MFMA row sums already span both K halves of every block: no exchange between the lane halves)
     const float l_tot = DROP ? l_run[qb] + __shfl_xor(l_run[qb], 32, 64) : lacc[qb >> 1][(qb & 1) * 8];
-    if (!(l_tot < 1e37f) && qn[qb] < S) *redo_flag = 1;  // (also NaN) a probability left the f32 range: see the half step
+    // The row sum can pass while the accumulators do not: a sum of 2^122 (< 1e37) times |v| = 100 is past the f32 range, the
+    // stored row was +-inf with the flag clear (tests/test_gpu_mhsa.py, the gap rows).  So the flag also goes up on any
+    // accumulator of this lane that is inf or NaN (all exponent bits set; integer compares: nothing to fold away).
+    uint32_t o_top = 0u;
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const uint32_t bits = __float_as_uint(o_acc[qb][dt][r]) & 0x7fffffffu;
+        o_top = bits > o_top ? bits : o_top;
+      }
+    // (also NaN) a probability or a weighted sum left the f32 range: see the half step
+    if ((!(l_tot < 1e37f) || o_top >= 0x7f800000u) && qn[qb] < S) *redo_flag = 1;
     float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
     if constexpr (DROP) inv *= dr.keep_scale;
     if (lse != nullptr && half == 0 && qn[qb] < S)

@@ -685,6 +685,21 @@ def _seed_dev_ptr(seed_dev: Optional[Tensor], like: Tensor):
     return seed_dev.data_ptr()
 
 
+def _mhsa_shape(who: str, qkv: Tensor, batch_size: int, num_heads: int):
+    """(rows, C, S, D) of a fused ``q | k | v`` matrix, or ValueError: nothing is launched on operands that do not fit."""
+    rows, c3 = _rows(qkv).shape
+    if batch_size <= 0 or num_heads <= 0 or rows % batch_size != 0:
+        raise ValueError(f"{who}: {rows} rows are no whole number of batch_size = {batch_size} sequences")
+    if c3 % 3 != 0 or (c3 // 3) % num_heads != 0:
+        raise ValueError(f"{who}: {c3} columns are not 3 x num_heads = {num_heads} x head size")
+    return rows, c3 // 3, rows // batch_size, c3 // 3 // num_heads
+
+
+def _mhsa_operand(who: str, name: str, t: Tensor, qkv: Tensor, rows: int, c: int) -> None:
+    if _rows(t).shape != (rows, c) or t.dtype != qkv.dtype:
+        raise ValueError(f"{who}: {name} must be [{rows}, {c}] {qkv.dtype} like qkv implies, got {tuple(t.shape)} {t.dtype}")
+
+
 def mhsa(qkv: Tensor, batch_size: int, num_heads: int, window: int = -1, out: Optional[Tensor] = None,
          return_lse: bool = False, dropout_p: float = 0.0, dropout_seed: int = 0, head_offset: int = 0,
          heads_total: int = 0, seed_dev: Optional[Tensor] = None):
@@ -695,11 +710,10 @@ def mhsa(qkv: Tensor, batch_size: int, num_heads: int, window: int = -1, out: Op
     shard of a model group draws the mask of the unsharded attention; 0 = all heads).  ``seed_dev``: a device integer
     whose low 32 bits the kernels add to ``dropout_seed`` when they run (``runtime.DeviceDropout``: the part of the seed a
     captured HIP graph advances between replays)."""
+    rows, c, s_len, d = _mhsa_shape("mhsa", qkv, batch_size, num_heads)
+    if out is not None:
+        _mhsa_operand("mhsa", "out", out, qkv, rows, c)
     _dev(qkv, out)
-    rows, c3 = _rows(qkv).shape
-    c = c3 // 3
-    s_len = rows // batch_size
-    d = c // num_heads
     if out is None:
         out = torch.empty((rows, c), dtype=qkv.dtype, device=qkv.device)
     lib = _lib.load()
@@ -721,14 +735,15 @@ def mhsa_backward(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, batch_siz
     """``d qkv`` ``[B*S, 3C]`` of :func:`mhsa` from the forward's output and log-sum-exp (``anemoi_mhsa_backward``).
     ``use_mfma=False`` withholds the workspace: the call then takes the VALU kernels (plain HIP, any head size / dtype) --
     the yardstick the MFMA route's hand-scheduled kernels are held against in the tests."""
+    rows, c, s_len, _ = _mhsa_shape("mhsa_backward", qkv, batch_size, num_heads)
+    c3 = 3 * c
+    _mhsa_operand("mhsa_backward", "out", out, qkv, rows, c)
+    _mhsa_operand("mhsa_backward", "dout", dout, qkv, rows, c)
+    if lse.dtype != torch.float32 or not lse.is_contiguous() or tuple(lse.shape) != (batch_size, num_heads, s_len):
+        raise ValueError("mhsa_backward: lse must be the contiguous f32 [B, H, S] output of mhsa(return_lse=True)")
     _dev(qkv, out, dout, lse)
-    rows, c3 = _rows(qkv).shape
-    c = c3 // 3
-    s_len = rows // batch_size
     dqkv = torch.empty((rows, c3), dtype=qkv.dtype, device=qkv.device)
     delta = torch.empty((batch_size, num_heads, s_len), dtype=torch.float32, device=qkv.device)
-    if lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() != delta.numel():
-        raise ValueError("mhsa_backward: lse must be the contiguous f32 [B, H, S] output of mhsa(return_lse=True)")
     lib = _lib.load()
     ws_bytes = lib.anemoi_mhsa_backward_workspace_bytes(dtype_code(qkv.dtype), batch_size, s_len, num_heads, c // num_heads)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=qkv.device) if ws_bytes > 0 and use_mfma else None

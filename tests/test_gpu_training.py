@@ -692,26 +692,7 @@ def test_transformer_model_training_step_vs_oracle_autograd(graph_o32, golden_cf
     assert any("attention.lin_qkv" in k for k in used) and any("attention.projection" in k for k in used)
 
 
-def _dropout_keep_mask(seed: int, p: float, b: int, h: int, s: int, h0: int = 0, h_total: int = 0) -> torch.Tensor:
-    """The kernels' counter-based keep mask (csrc/attention.hip::dropout_keep) restated with torch integer arithmetic:
-    [B, H, S, S] of 0 / 1.  One 32-bit hash of (row, key >> 1) -- one multiply, two fold-downs -- decides a key pair, 15 bits
-    per key."""
-    m32 = 0xFFFFFFFF
-    h_total = h_total or h
-    bb = torch.arange(b, dtype=torch.int64).view(b, 1, 1, 1)
-    hh = torch.arange(h, dtype=torch.int64).view(1, h, 1, 1) + h0
-    qq = torch.arange(s, dtype=torch.int64).view(1, 1, s, 1)
-    row = (bb * h_total + hh) * s + qq  # (b * H_total + h0 + h) * S + i
-    col = torch.arange(s, dtype=torch.int64).view(1, 1, 1, s)
-    x = ((row & m32) * 0x9E3779B1) & m32
-    x = x ^ (((row >> 32) * 0x85EBCA77) & m32) ^ (seed & m32)
-    x = x ^ (((col >> 1) * 0xC2B2AE3D) & m32)
-    x = x ^ (x >> 16)
-    x = (x * 0x7FEB352D) & m32
-    x = x ^ (x >> 15)
-    bits = (x >> (16 * (col & 1))) & 0x7FFF
-    thr = min(int(p * 32768.0 + 0.5), 32768)
-    return (bits >= thr).to(torch.float64) if p < 1.0 else torch.zeros(b, h, s, s, dtype=torch.float64)
+from _mhsa_ref import keep_mask as _dropout_keep_mask  # noqa: E402  (the kernels' counter-based keep mask, restated)
 
 
 @pytest.mark.parametrize("processor", ["Transformer", "GraphTransformer"])
