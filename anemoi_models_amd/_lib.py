@@ -49,7 +49,62 @@ def cond_ln_padded_k(k: int) -> int:
     return 4 if k <= 4 else (8 if k <= 8 else (16 if k <= 16 else 32))
 
 
-ABI_VERSION = 52
+ABI_VERSION = 53
+
+LINEAR_ENTRIES = {"linear": 0, "ln": 1, "stats": 2, "dual": 3, "actgrad": 4, "batched": 5}  # ANEMOI_LINEAR_ENTRY_*
+LINEAR_KERNEL_NONE, LINEAR_KERNEL_128, LINEAR_KERNEL_PERSISTENT = 0, 1, 2
+LINEAR_REST_NONE, LINEAR_REST_IN_LAUNCH, LINEAR_REST_SKINNY, LINEAR_REST_128 = 0, 1, 2, 3
+
+
+class LinearArgs(ctypes.Structure):
+    """``anemoi_linear_args`` of include/anemoi_amd.h (``anemoi_linear_route``), field for field."""
+
+    _fields_ = [
+        ("struct_bytes", c_int64),
+        ("entry", ctypes.c_int32), ("dtype", ctypes.c_int32), ("out_dtype", ctypes.c_int32), ("act", ctypes.c_int32),
+        ("x", c_void_p), ("w", c_void_p), ("bias", c_void_p), ("colsum", c_void_p), ("stats", c_void_p),
+        ("residual", c_void_p), ("y", c_void_p),
+        ("ldx", c_int64), ("ldr", c_int64), ("ldy", c_int64), ("M", c_int64),
+        ("N", ctypes.c_int32), ("K", ctypes.c_int32),
+        ("workspace", c_void_p), ("workspace_bytes", c_int64), ("stats_out", c_void_p),
+        ("stride_x", c_int64), ("stride_w", c_int64), ("stride_y", c_int64),
+        ("batch", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ]
+
+
+class LinearRouteLaunch(ctypes.Structure):
+    """``anemoi_linear_route_launch``: one launch of the persistent kernel."""
+
+    _fields_ = [
+        ("row0", c_int64), ("rows", c_int64), ("tiles", c_int64),
+        ("mh", ctypes.c_int32), ("blocks", ctypes.c_int32), ("tail_rows", ctypes.c_int32),
+        ("stagger_phases", ctypes.c_int32), ("stagger_unit", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ]
+
+
+class LinearRoute(ctypes.Structure):
+    """``anemoi_linear_route_info``: what the fused Linear family does with a call (the library's own plan)."""
+
+    _fields_ = [
+        ("struct_bytes", c_int64),
+        ("kernel", ctypes.c_int32), ("n_launches", ctypes.c_int32),
+        ("launch", LinearRouteLaunch * 2),
+        ("main_rows", c_int64),
+        ("rest", ctypes.c_int32), ("nt", ctypes.c_int32),
+        ("rest_row0", c_int64), ("rest_rows", c_int64), ("rs_rows", c_int64),
+        ("vec_ok", ctypes.c_int32), ("split", ctypes.c_int32), ("model", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ]
+
+
+def linear_route(entry: str, **fields):
+    """``(status, LinearRoute)`` of ``anemoi_linear_route`` for the arguments ``fields`` of entry point ``entry`` (pointers as
+    integers; whatever is left out is 0 / NULL).  Launches nothing and needs no GPU: for tests and diagnostics."""
+    args, route = LinearArgs(), LinearRoute()
+    args.struct_bytes, route.struct_bytes = ctypes.sizeof(LinearArgs), ctypes.sizeof(LinearRoute)
+    args.entry = LINEAR_ENTRIES[entry]
+    for name, value in fields.items():
+        setattr(args, name, value)
+    return load().anemoi_linear_route(ctypes.byref(args), ctypes.byref(route)), route
 
 
 class GtBlockArgs(ctypes.Structure):
@@ -146,6 +201,7 @@ SIGNATURES = {
                                                       c_void_p]),
     "anemoi_linear_dual": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
                                    c_int64, c_int, c_int, c_int, c_void_p]),
+    "anemoi_linear_route": (c_int, [ctypes.POINTER(LinearArgs), ctypes.POINTER(LinearRoute)]),
     "anemoi_linear_actgrad": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64,
                                       c_int, c_int, c_int, c_void_p]),
     "anemoi_gt_conv": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,

@@ -15,6 +15,7 @@
 // one barrier per K-slab.  The LDS image is lane-linear (8 rows x 128 B per wave instruction), so the
 // bank swizzle is applied to the per-lane SOURCE address and undone on the fragment read
 // (chunk' = chunk ^ ((row >> 1) & 7)): conflict-free for both fragment shapes.
+#include <array>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -61,7 +62,7 @@ struct LnFold {
   // without reading y again (anemoi_linear_stats)
   float2* rs_partial;
   int rs_slots;
-  int64_t* rs_rows_done;  // host side only: the launcher reports how many leading rows got their partials
+  int64_t* rs_rows_done;  // unused, always null (the route carries that number); kept for the kernels' argument layout
   // batched launch of the four-wave kernel (anemoi_linear_batched): b_count independent problems of b_tiles tiles each,
   // operand bases b * b_sx / b_sw / b_sy elements apart; b_tiles = 0: one problem
   int64_t b_tiles, b_sx, b_sw, b_sy;
@@ -989,277 +990,6 @@ __global__ __launch_bounds__(256) void linear_bf16_w4_kernel(const bf16_t* __res
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS-DMA may outlive the workgroup
 }
 
-template <typename T, typename TO>
-static int linear_launch(const void* x, int64_t ldx, const void* w, const float* bias, const void* residual,
-                         int64_t ldr, void* y, int64_t ldy, int64_t M, int N, int K, int act, hipStream_t st,
-                         LnFold ln, int batch = 1, int64_t sx = 0, int64_t sw = 0, int64_t sy = 0);
-
-constexpr int W4_NEEDS_WHOLE_TILES = -4242;  // internal: the caller has to split the ragged rows off itself
-// Returns through *tail_done whether the up to 8 rows behind M (m_tail) were computed by the same launch.
-static int linear_bf16_256_launch(const void* x, int64_t ldx, const void* w, const float* bias, const void* residual,
-                                  int64_t ldr, void* y, int64_t ldy, int64_t M, int N, int K, int act,
-                                  hipStream_t st, LnFold ln = LnFold{nullptr, nullptr}, int m_tail = 0,
-                                  bool* tail_done = nullptr, int epi = 0) {
-  // epi 1 (DUAL): `residual` / ldr name the second OUTPUT (pre-activation); epi 2 (GMUL): they name the saved
-  // pre-activation and the result is acc * act'(it).  Whole tiles only in both modes.
-  const bool dual = epi == 1, gmul = epi == 2;
-  if (tail_done != nullptr) *tail_done = false;
-  static PerDeviceOnce raised;
-  const int raise_dev = raised.pending();
-  if (raise_dev >= 0) {
-#define RAISE_W4_(A, RES, LNF)                                                                    \
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(linear_bf16_w4_kernel<A, RES, LNF, 8>),  \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, W4_LDS) != hipSuccess ||    \
-      hipFuncSetAttribute(reinterpret_cast<const void*>(linear_bf16_w4_kernel<A, RES, LNF, 6>),  \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, W4_LDS) != hipSuccess ||    \
-      hipFuncSetAttribute(reinterpret_cast<const void*>(linear_bf16_w4_kernel<A, RES, LNF, 5>),  \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, W4_LDS) != hipSuccess ||    \
-      hipFuncSetAttribute(reinterpret_cast<const void*>(linear_bf16_w4_kernel<A, RES, LNF, 4>),  \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, W4_LDS) != hipSuccess ||    \
-      hipFuncSetAttribute(reinterpret_cast<const void*>(linear_bf16_w4_kernel<A, RES, LNF, 3>),  \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, W4_LDS) != hipSuccess)      \
-    return fail(ANEMOI_ERR_LAUNCH, "anemoi_linear: cannot raise the dynamic LDS limit to %d", W4_LDS)
-#define RAISE_W4(A, RES) \
-  RAISE_W4_(A, RES, false); \
-  RAISE_W4_(A, RES, true)
-#define RAISE_W4_RS(RES, LNF, MHV)                                                                              \
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(linear_bf16_w4_kernel<0, RES, LNF, MHV, true>),         \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, W4_LDS) != hipSuccess)                     \
-    return fail(ANEMOI_ERR_LAUNCH, "anemoi_linear: cannot raise the dynamic LDS limit to %d", W4_LDS)
-    RAISE_W4_RS(false, false, 8);
-    RAISE_W4_RS(false, true, 8);
-    RAISE_W4_RS(true, false, 8);
-    RAISE_W4_RS(true, true, 8);
-    RAISE_W4_RS(false, false, 6);
-    RAISE_W4_RS(false, true, 6);
-    RAISE_W4_RS(true, false, 6);
-    RAISE_W4_RS(true, true, 6);
-    RAISE_W4_RS(false, false, 5);
-    RAISE_W4_RS(false, true, 5);
-    RAISE_W4_RS(true, false, 5);
-    RAISE_W4_RS(true, true, 5);
-    RAISE_W4_RS(false, false, 4);
-    RAISE_W4_RS(false, true, 4);
-    RAISE_W4_RS(true, false, 4);
-    RAISE_W4_RS(true, true, 4);
-    RAISE_W4_RS(false, false, 3);
-    RAISE_W4_RS(false, true, 3);
-    RAISE_W4_RS(true, false, 3);
-    RAISE_W4_RS(true, true, 3);
-#undef RAISE_W4_RS
-#define RAISE_W4_DUAL(A, MHV)                                                                                    \
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(linear_bf16_w4_kernel<A, false, false, MHV, false, true>), \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, W4_LDS) != hipSuccess)                      \
-    return fail(ANEMOI_ERR_LAUNCH, "anemoi_linear: cannot raise the dynamic LDS limit to %d", W4_LDS)
-    RAISE_W4_DUAL(1, 8);
-    RAISE_W4_DUAL(1, 4);
-    RAISE_W4_DUAL(2, 8);
-    RAISE_W4_DUAL(2, 4);
-    RAISE_W4_DUAL(3, 8);
-    RAISE_W4_DUAL(3, 4);
-#undef RAISE_W4_DUAL
-#define RAISE_W4_GMUL(A, MHV)                                                                                          \
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(linear_bf16_w4_kernel<A, true, false, MHV, false, false, true>), \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, W4_LDS) != hipSuccess)                            \
-    return fail(ANEMOI_ERR_LAUNCH, "anemoi_linear: cannot raise the dynamic LDS limit to %d", W4_LDS)
-    RAISE_W4_GMUL(1, 8);
-    RAISE_W4_GMUL(1, 4);
-    RAISE_W4_GMUL(2, 8);
-    RAISE_W4_GMUL(2, 4);
-    RAISE_W4_GMUL(3, 8);
-    RAISE_W4_GMUL(3, 4);
-#undef RAISE_W4_GMUL
-    RAISE_W4(0, false);
-    RAISE_W4(0, true);
-    RAISE_W4(1, false);
-    RAISE_W4(1, true);
-    RAISE_W4(2, false);
-    RAISE_W4(2, true);
-    RAISE_W4(3, false);
-    RAISE_W4(3, true);
-#undef RAISE_W4
-#undef RAISE_W4_
-    raised.done(raise_dev);
-  }
-  const int64_t mt = (M + BIG_M - 1) / BIG_M;
-  const int64_t nt = (N + BIG_N - 1) / BIG_N;
-  ANEMOI_REQUIRE(mt * nt < (int64_t)1 << 31, ANEMOI_ERR_UNSUPPORTED, "anemoi_linear: grid too large");
-  const bool vec_ok = (N % 8 == 0) && (ldy % 8 == 0) && ((uintptr_t)y % 16 == 0) &&
-                      (bias == nullptr || (uintptr_t)bias % 16 == 0) && (residual == nullptr || (ldr % 8 == 0 && (uintptr_t)residual % 16 == 0));
-  const bool batched = ln.b_tiles > 0;  // anemoi_linear_batched: b_count problems of mt * nt tiles each
-  const int64_t problems = batched ? ln.b_count : 1;
-  int64_t blocks = problems * mt * nt;
-  constexpr int64_t max_blocks = 256;  // one persistent workgroup per CU
-  if (blocks > max_blocks) blocks = max_blocks;
-  blocks = (blocks + 7) / 8 * 8;          // whole XCD rows; surplus workgroups exit at once
-  if (K >= 128 && ldx < (int64_t)1 << 21 && ldy < (int64_t)1 << 21 && ldr < (int64_t)1 << 21 && vec_ok &&
-      (M % BIG_M == 0 || m_tail == 0) && (ln.colsum == nullptr || (uintptr_t)ln.colsum % 16 == 0)) {
-    const int w4_tail = (m_tail > 0 && m_tail <= 8 && K % 8 == 0) ? m_tail : 0;
-    if (tail_done != nullptr) *tail_done = w4_tail > 0;
-    // Remainder round as HALF tiles: when the tiles beyond the last whole round of 256 would keep at most half of the
-    // CUs busy (N = 1024 at M = 40 960: 640 tiles = 2.5 rounds), their rows go to a second launch with 128 x 256 tiles
-    // (MH = 4): twice as many units of half the work -- 2.5+ instead of 3 rounds, no cross-workgroup traffic.
-    int64_t mt_a = mt, mt_b = 0;  // row tiles of 256 for launch A; rows of launch B = mt_b * 256 as half tiles
-    if (!batched && nt <= 256 && 256 % nt == 0) {
-      const int64_t per_round = 256 / nt;
-      const int64_t rem_mt = mt % per_round;
-      // measured: a half tile costs ~0.75 of a whole one (its 48 KiB slab per 64 MFMAs is bound by the L2 -> LDS
-      // staging rate), and a second launch ~8 us; so split only a remainder that is the whole problem (small M of a
-      // node-partitioned run: 5120 x 1024 x 4096 0.081 -> 0.052 ms) or belongs to long tiles (K >= 2048: 40 962 x 1024
-      // x 4096 0.314 -> 0.295 ms; at K = 1216 the second launch costs what the half tiles save)
-      // (round 2: splitting EVERY remainder of <= 128 tiles off, whatever K, measured -1 ... +9 % on the per-rank shapes
-      //  5121 x {4096, 2048, 2240, 1024} -- profiles/r02_gemm_small_m.txt -- so the rule stays)
-      // (the whole-problem case, rem_mt == mt, is one candidate of the tile-height model below for the plain epilogues)
-      if (rem_mt > 0 && rem_mt * nt <= 128 && ((rem_mt == mt && (dual || gmul)) || (rem_mt != mt && K >= 2048))) {
-        mt_a = mt - rem_mt;
-        mt_b = rem_mt;
-      }
-    }
-#define LAUNCH_W4__(A, RES, LNF, MHV, RSV, XP, RP, YP, LNV, MV, TILES, TAIL)                                       \
-  hipLaunchKernelGGL((linear_bf16_w4_kernel<A, RES, LNF, MHV, RSV>), dim3((unsigned)w4_blocks), dim3(256), W4_LDS, \
-                     st, XP, ldx, static_cast<const bf16_t*>(w), bias, RP, ldr, YP, ldy, MV, N, K,                 \
-                     vec_ok ? 1 : 0, TILES, (int)nt, LNV, TAIL)
-#define LAUNCH_W4_(A, RES, MHV, RSV, XP, RP, YP, LNV, MV, TILES, TAIL)                             \
-  do {                                                                                             \
-    if (ln.stats != nullptr) LAUNCH_W4__(A, RES, true, MHV, RSV, XP, RP, YP, LNV, MV, TILES, TAIL); \
-    else LAUNCH_W4__(A, RES, false, MHV, RSV, XP, RP, YP, LNV, MV, TILES, TAIL);                   \
-  } while (0)
-#define LAUNCH_W4(A, MHV, RSV, XP, RP, YP, LNV, MV, TILES, TAIL)                                \
-  do {                                                                                          \
-    if (residual != nullptr) LAUNCH_W4_(A, true, MHV, RSV, XP, RP, YP, LNV, MV, TILES, TAIL);   \
-    else LAUNCH_W4_(A, false, MHV, RSV, XP, RP, YP, LNV, MV, TILES, TAIL);                      \
-  } while (0)
-#define LAUNCH_W4_DUAL(A, MHV, XP, RP, YP, LNV, MV, TILES, TAIL)                                                      \
-  hipLaunchKernelGGL((linear_bf16_w4_kernel<A, false, false, MHV, false, true>), dim3((unsigned)w4_blocks), dim3(256), \
-                     W4_LDS, st, XP, ldx, static_cast<const bf16_t*>(w), bias, RP, ldr, YP, ldy, MV, N, K,             \
-                     vec_ok ? 1 : 0, TILES, (int)nt, LNV, TAIL)
-#define LAUNCH_W4_GMUL(A, MHV, XP, RP, YP, LNV, MV, TILES, TAIL)                                                            \
-  hipLaunchKernelGGL((linear_bf16_w4_kernel<A, true, false, MHV, false, false, true>), dim3((unsigned)w4_blocks), dim3(256), \
-                     W4_LDS, st, XP, ldx, static_cast<const bf16_t*>(w), bias, RP, ldr, YP, ldy, MV, N, K,                   \
-                     vec_ok ? 1 : 0, TILES, (int)nt, LNV, TAIL)
-#define LAUNCH_W4_PLAIN(MHV, XP, RP, YP, LNV, MV, TILES, TAIL)                                      \
-  switch (act) {                                                                                    \
-    case ANEMOI_ACT_GELU: LAUNCH_W4(ANEMOI_ACT_GELU, MHV, false, XP, RP, YP, LNV, MV, TILES, TAIL); break; \
-    case ANEMOI_ACT_SILU: LAUNCH_W4(ANEMOI_ACT_SILU, MHV, false, XP, RP, YP, LNV, MV, TILES, TAIL); break; \
-    case ANEMOI_ACT_RELU: LAUNCH_W4(ANEMOI_ACT_RELU, MHV, false, XP, RP, YP, LNV, MV, TILES, TAIL); break; \
-    default:                                                                                        \
-      if (rs_on) LAUNCH_W4(ANEMOI_ACT_NONE, MHV, true, XP, RP, YP, LNV, MV, TILES, TAIL);           \
-      else LAUNCH_W4(ANEMOI_ACT_NONE, MHV, false, XP, RP, YP, LNV, MV, TILES, TAIL);                \
-      break;                                                                                        \
-  }
-#define LAUNCH_W4_ACT(MHV, XP, RP, YP, LNV, MV, TILES, TAIL)                                        \
-  if (gmul) {                                                                                       \
-    switch (act) {                                                                                  \
-      case ANEMOI_ACT_GELU: LAUNCH_W4_GMUL(ANEMOI_ACT_GELU, MHV, XP, RP, YP, LNV, MV, TILES, TAIL); break; \
-      case ANEMOI_ACT_SILU: LAUNCH_W4_GMUL(ANEMOI_ACT_SILU, MHV, XP, RP, YP, LNV, MV, TILES, TAIL); break; \
-      default: LAUNCH_W4_GMUL(ANEMOI_ACT_RELU, MHV, XP, RP, YP, LNV, MV, TILES, TAIL); break;         \
-    }                                                                                               \
-  } else if (dual) {                                                                                \
-    switch (act) {                                                                                  \
-      case ANEMOI_ACT_GELU: LAUNCH_W4_DUAL(ANEMOI_ACT_GELU, MHV, XP, RP, YP, LNV, MV, TILES, TAIL); break; \
-      case ANEMOI_ACT_SILU: LAUNCH_W4_DUAL(ANEMOI_ACT_SILU, MHV, XP, RP, YP, LNV, MV, TILES, TAIL); break; \
-      default: LAUNCH_W4_DUAL(ANEMOI_ACT_RELU, MHV, XP, RP, YP, LNV, MV, TILES, TAIL); break;         \
-    }                                                                                               \
-  } else LAUNCH_W4_PLAIN(MHV, XP, RP, YP, LNV, MV, TILES, TAIL)
-    // row-sum partials (LnFold::rs_partial): plain epilogue only, whole 256-column tiles only
-    const bool rs_on = ln.rs_partial != nullptr && act == ANEMOI_ACT_NONE && N % BIG_N == 0;
-    if (rs_on && ln.rs_rows_done != nullptr) *ln.rs_rows_done = M;
-    const bf16_t* xb = static_cast<const bf16_t*>(x);
-    const bf16_t* rb = static_cast<const bf16_t*>(residual);
-    bf16_t* yb = static_cast<bf16_t*>(y);
-    int64_t w4_blocks = blocks;
-    // Small problems (fewer than four rounds of 256-row tiles -- the per-rank shapes of a node-partitioned run, BASELINE
-    // configs 2 and 5): the tile HEIGHT is chosen per launch among 256 / 192 / 160 / 128 rows by a two-term model of the
-    // persistent loop, rounds x (epilogue + slabs x staged bytes): the loop is bound by the bytes it stages, so a tile of
-    // 32 MH rows costs (32 MH + 256) / 512 of a whole one per slab (measured 0.75 for MH = 4, 0.875 for MH = 6) and
-    // MH / 8 of its 6.5 us epilogue; what decides is how the tile count quantises against the 256 CUs
-    // (5121 x 2048: 160 / 216 / 256 / 320 tiles -> 160-row tiles fill the chip exactly once;
-    //  5121 x 4096: 320 / 432 / 512 / 640 -> two balanced rounds of 160-row tiles; profiles/r04_gemm_small_m.txt).
-    // (a half-tile split chosen above competes with the single-launch candidates: its cost by the same model = whole rounds of
-    //  256-row tiles + the rounds of half tiles at 0.75 of the slab cost + ~6 us for the second launch.  20 481 x 1024 x 4096,
-    //  one rank of two: 256 + 128 half tiles = 177 against 158 for two rounds of 160-row tiles)
-    // Staggered start (LnFold::stagger_*); ANEMOI_AMD_GEMM_STAGGER="phases,unit,min rounds" overrides the shipped values
-    // (phases 0: off; A/B runs)
-    static const struct Stagger { int phases, unit, min_rounds; } stagger = [] {
-      Stagger v{STAGGER_PHASES, STAGGER_UNIT, STAGGER_MIN_ROUNDS};
-      if (const char* e = getenv("ANEMOI_AMD_GEMM_STAGGER")) sscanf(e, "%d,%d,%d", &v.phases, &v.unit, &v.min_rounds);
-      return v;
-    }();
-    const bool split_chosen = mt_b > 0 && !dual && !gmul;
-    if (!batched && !dual && !gmul && (mt_b == 0 || split_chosen) && mt * nt < 4 * max_blocks) {
-      static const int forced_mh = [] {  // lab switch for A/B runs: ANEMOI_AMD_GEMM_MH=3|4|5|6|8
-        const char* e = getenv("ANEMOI_AMD_GEMM_MH");
-        return e != nullptr ? atoi(e) : 0;
-      }();
-      int best_mh = 8;
-      double best_cost = 1e30;
-      for (const int mh : {8, 6, 5, 4, 3}) {
-        const int64_t tiles = (M + 32 * mh - 1) / (32 * mh) * nt, rounds = (tiles + max_blocks - 1) / max_blocks;
-        const double cost = (double)rounds * (0.8125 * mh + (K / 64) * 1.44 * (32 * mh + 256) / 512.0);
-        if (forced_mh == mh || (forced_mh == 0 && cost < best_cost * 0.97)) {  // (3 %: ties go to the taller tile)
-          best_cost = cost;
-          best_mh = mh;
-          if (forced_mh == mh) break;
-        }
-      }
-      bool single = best_mh != 8;
-      if (split_chosen) {
-        const int64_t rounds_a = (mt_a * nt + max_blocks - 1) / max_blocks, rounds_b = (mt_b * 2 * nt + max_blocks - 1) / max_blocks;
-        const double split_cost = (double)rounds_a * (0.8125 * 8 + (K / 64) * 1.44) +
-                                  (double)rounds_b * (0.8125 * 4 + (K / 64) * 1.44 * 0.75) + 6.0;
-        single = forced_mh != 0 || best_cost < split_cost * 0.97;  // (a forced height means ONE launch of that height)
-        if (single) {  // one launch of best_mh-row tiles (8 included) instead of the split
-          mt_a = mt;
-          mt_b = 0;
-        }
-      }
-      if (single && best_mh != 8) {
-        const int64_t tiles = (M + 32 * best_mh - 1) / (32 * best_mh) * nt;
-        w4_blocks = tiles < max_blocks ? (tiles + 7) / 8 * 8 : max_blocks;
-        // (no stagger on these launches of one or two rounds: 1 ... 4 units measured 3.20 -> 3.20 ... 3.26 ms at config 2)
-        if (best_mh == 6) { LAUNCH_W4_PLAIN(6, xb, rb, yb, ln, M, tiles, w4_tail) }
-        else if (best_mh == 5) { LAUNCH_W4_PLAIN(5, xb, rb, yb, ln, M, tiles, w4_tail) }
-        else if (best_mh == 3) { LAUNCH_W4_PLAIN(3, xb, rb, yb, ln, M, tiles, w4_tail) }
-        else { LAUNCH_W4_PLAIN(4, xb, rb, yb, ln, M, tiles, w4_tail) }
-        mt_a = 0;  // done
-      }
-    }
-    if (mt_a > 0) {
-      const int64_t m_a = mt_a * BIG_M < M ? mt_a * BIG_M : M, tiles_a = problems * mt_a * nt;
-      const int tail_a = mt_b == 0 ? w4_tail : 0;
-      w4_blocks = tiles_a < max_blocks ? (tiles_a + 7) / 8 * 8 : max_blocks;
-      // Staggered start (LnFold::stagger_*): launches of >= min_rounds rounds of tiles with K >= STAGGER_MIN_K (the K = 256
-      // products measured no gain).  Phase g waits g x unit x 1024 cycles; a SMALL offset is what counts -- 2 x 8 ... 32 units,
-      // 3 x 12, 4 x 8 measured alike, a step of half a tile's time or 16 phases nothing (DESIGN 4.1).
-      LnFold la = ln;
-      if (stagger.phases > 1 && tiles_a >= (int64_t)stagger.min_rounds * max_blocks && K >= STAGGER_MIN_K) {
-        la.stagger_phases = stagger.phases;
-        la.stagger_unit = stagger.unit;
-      }
-      LAUNCH_W4_ACT(8, xb, rb, yb, la, m_a, tiles_a, tail_a)
-    }
-    if (mt_b > 0) {
-      const int64_t m_a = mt_a * BIG_M, m_b = M - m_a, tiles_b = mt_b * 2 * nt;  // m_b may end inside the last tile
-      LnFold lb = ln;
-      if (lb.stats != nullptr) lb.stats += m_a;
-      if (lb.rs_partial != nullptr) lb.rs_partial += m_a * lb.rs_slots;
-      w4_blocks = tiles_b < max_blocks ? (tiles_b + 7) / 8 * 8 : max_blocks;
-      LAUNCH_W4_ACT(4, xb + m_a * ldx, rb != nullptr ? rb + m_a * ldr : nullptr, yb + m_a * ldy, lb, m_b, tiles_b, w4_tail)
-    }
-#undef LAUNCH_W4_ACT
-#undef LAUNCH_W4_PLAIN
-#undef LAUNCH_W4_DUAL
-#undef LAUNCH_W4_GMUL
-#undef LAUNCH_W4
-#undef LAUNCH_W4_
-#undef LAUNCH_W4__
-    return check_launch("anemoi_linear(256x256, 4 waves)");
-  }
-  if (M % BIG_M != 0 || batched || epi != 0) return W4_NEEDS_WHOLE_TILES;  // (the caller splits the ragged rows off / refuses)
-  // shapes the persistent kernel does not take (K = 64, unaligned output, ...): the general 128 x 128 kernel
-  return linear_launch<bf16_t, bf16_t>(x, ldx, w, bias, residual, ldr, y, ldy, M, N, K, act, st, ln);
-}
-
 // =============================================================================================
 // Skinny rows (M <= 8): one wave per output column, K swept with 16-byte loads, f32 accumulation, wave reduction.
 // Used for the ragged last rows of a tall GEMM (M % 256 in 1..8) so that they do not cost a full tile round.
@@ -1277,95 +1007,453 @@ __global__ __launch_bounds__(256) void linear_bf16_skinny_kernel(const bf16_t* _
   skinny_column<ROWS>(X, ldx, W, bias, R, ldr, Y, ldy, M, n, K, act, ln, lane);
 }
 
-template <typename T, typename TO>
-static int linear_launch(const void* x, int64_t ldx, const void* w, const float* bias, const void* residual,
-                         int64_t ldr, void* y, int64_t ldy, int64_t M, int N, int K, int act, hipStream_t st,
-                         LnFold ln, int batch, int64_t sx, int64_t sw, int64_t sy) {
-  const int64_t mt = (M + BM - 1) / BM;
-  const int64_t nt = (N + BN - 1) / BN;
-  ANEMOI_REQUIRE(mt * nt < (int64_t)1 << 31, ANEMOI_ERR_UNSUPPORTED, "anemoi_linear: grid too large");
-  const bool vec_ok = (N % 4 == 0) && (ldy % 4 == 0) && ((uintptr_t)y % 16 == 0) &&
-                      (bias == nullptr || (uintptr_t)bias % 16 == 0) &&
-                      (ln.colsum == nullptr || (uintptr_t)ln.colsum % 16 == 0) &&
-                      (residual == nullptr || (ldr % 4 == 0 && (uintptr_t)residual % 16 == 0));
-  hipLaunchKernelGGL((linear_kernel<T, TO>), dim3((unsigned)(mt * nt), (unsigned)batch), dim3(256), 0, st,
-                     static_cast<const T*>(x), ldx, static_cast<const T*>(w), bias, static_cast<const T*>(residual), ldr,
-                     static_cast<TO*>(y), ldy, M, N, K, act, vec_ok ? 1 : 0, ln, sx, sw, sy);
-  return check_launch("anemoi_linear");
-}
-
 }  // namespace anemoi
 
 using namespace anemoi;
 
-static int linear_dispatch(const char* who, int dtype, int out_dtype, const void* x, int64_t ldx, const void* w,
-                           const float* bias, LnFold ln, const void* residual, int64_t ldr, void* y, int64_t ldy,
-                           int64_t M, int N, int K, int act, anemoi_stream_t stream) {
-  ANEMOI_REQUIRE(x && w && y, ANEMOI_ERR_INVALID, "%s: null pointer", who);
+// =============================================================================================
+// Host side of the fused Linear family.  An entry point gathers its arguments in an anemoi_linear_args (Args), and
+//   linear_validate   refuses bad arguments with the entry point's own status and message,
+//   linear_plan       turns the arguments into a plain-data route (anemoi_linear_route_info, Route): no HIP call, no
+//                     dereferenced pointer, no allocation -- every rule of the dispatch lives there,
+//   linear_run        executes a route and decides nothing.
+// anemoi_linear_route hands the same validation and the same plan to tests and diagnostics.
+// =============================================================================================
+using Args = anemoi_linear_args;
+using Route = anemoi_linear_route_info;
+
+// ---- Kernel table.  w4_exists says which instances of linear_bf16_w4_kernel there are, over the slot space
+//      epilogue x ACT x HAS_RES x LN x MH x RS; W4_TABLE holds the kernel of every slot it admits and nullptr elsewhere.
+//      The once-per-device loop that raises the dynamic LDS limit and the launch's lookup both read W4_TABLE, so an
+//      instance that is launched is one that was raised.
+using W4Kernel = void (*)(const bf16_t*, int64_t, const bf16_t*, const float*, const bf16_t*, int64_t, bf16_t*, int64_t,
+                          int64_t, int, int, int, int64_t, int, LnFold, int);
+enum W4Epi { W4_PLAIN = 0, W4_DUAL = 1, W4_GMUL = 2 };
+constexpr int W4_HEIGHTS[5] = {8, 6, 5, 4, 3};
+constexpr int W4_SLOTS = 3 * 4 * 2 * 2 * 5 * 2;
+
+constexpr int w4_slot(int epi, int act, bool res, bool ln, int mh_index, bool rs) {
+  return ((((epi * 4 + act) * 2 + res) * 2 + ln) * 5 + mh_index) * 2 + rs;
+}
+
+constexpr bool w4_exists(int epi, int act, bool res, bool ln, int mh, bool rs) {
+  // plain epilogue: every activation x residual x fold x height (80); the row sums only without activation (20)
+  if (epi == W4_PLAIN) return !rs || act == ANEMOI_ACT_NONE;
+  // DUAL (R is the second output: no residual) and GMUL (R is the pre-activation): an activation, whole and half tiles (6 + 6)
+  return act != ANEMOI_ACT_NONE && !ln && !rs && (mh == 8 || mh == 4) && res == (epi == W4_GMUL);
+}
+
+constexpr int w4_instances() {
+  int n = 0;
+  for (int s = 0; s < W4_SLOTS; ++s) n += w4_exists(s / 160, s / 40 % 4, s / 20 % 2, s / 10 % 2, W4_HEIGHTS[s / 2 % 5], s % 2);
+  return n;
+}
+static_assert(w4_instances() == 112, "every instance costs compile time and binary size: the table is not a cross product");
+
+template <int SLOT>
+constexpr W4Kernel w4_kernel_of() {
+  constexpr int epi = SLOT / 160, act = SLOT / 40 % 4, mh = W4_HEIGHTS[SLOT / 2 % 5];
+  constexpr bool res = SLOT / 20 % 2, ln = SLOT / 10 % 2, rs = SLOT % 2;
+  static_assert(w4_slot(epi, act, res, ln, SLOT / 2 % 5, rs) == SLOT, "slot numbering");
+  if constexpr (w4_exists(epi, act, res, ln, mh, rs))
+    return linear_bf16_w4_kernel<act, res, ln, mh, rs, epi == W4_DUAL, epi == W4_GMUL>;
+  else
+    return nullptr;
+}
+
+template <int... SLOT>
+constexpr std::array<W4Kernel, sizeof...(SLOT)> w4_table(std::integer_sequence<int, SLOT...>) {
+  return {{w4_kernel_of<SLOT>()...}};
+}
+static const std::array<W4Kernel, W4_SLOTS> W4_TABLE = w4_table(std::make_integer_sequence<int, W4_SLOTS>{});
+
+static int w4_raise_lds_limit() {
+  static PerDeviceOnce raised;
+  const int dev = raised.pending();
+  if (dev < 0) return ANEMOI_OK;
+  for (const W4Kernel k : W4_TABLE)
+    if (k != nullptr && hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            W4_LDS) != hipSuccess)
+      return fail(ANEMOI_ERR_LAUNCH, "anemoi_linear: cannot raise the dynamic LDS limit to %d", W4_LDS);
+  raised.done(dev);
+  return ANEMOI_OK;
+}
+
+// ---- Validation: what an entry point refuses before it plans, with its own status and message.
+static const char* const LINEAR_ENTRY_NAMES[] = {"anemoi_linear",      "anemoi_linear_ln",      "anemoi_linear_stats",
+                                                 "anemoi_linear_dual", "anemoi_linear_actgrad", "anemoi_linear_batched"};
+
+static int linear_validate(const Args& a) {
+  const char* who = LINEAR_ENTRY_NAMES[a.entry];
+  const int esz = a.dtype == ANEMOI_BF16 ? 2 : 4;
+  const int64_t M = a.M;
+  const int N = a.N, K = a.K;
+  if (a.entry == ANEMOI_LINEAR_ENTRY_DUAL || a.entry == ANEMOI_LINEAR_ENTRY_ACTGRAD) {  // (`residual` / ldr: pre / ldp)
+    ANEMOI_REQUIRE(a.x && a.w && a.residual && a.y, ANEMOI_ERR_INVALID, "%s: null pointer", who);
+    ANEMOI_REQUIRE(M >= 0 && N > 0 && K > 0 && a.ldx >= K && a.ldy >= N && a.ldr >= N, ANEMOI_ERR_INVALID, "%s: bad shape", who);
+    ANEMOI_REQUIRE(a.act > ANEMOI_ACT_NONE && a.act <= ANEMOI_ACT_RELU, ANEMOI_ERR_INVALID, "%s: act %d", who, a.act);
+    // (up to 8 rows behind the last whole 256-row tile are computed by the same launch: the skinny pass of the kernel)
+    ANEMOI_REQUIRE(a.dtype == ANEMOI_BF16 && M % BIG_M <= 8 && (M >= BIG_M || M == 0) && N >= 256 && N % 8 == 0 && K >= 128 &&
+                       K % 64 == 0 && (uintptr_t)a.x % 16 == 0 && (uintptr_t)a.w % 16 == 0 && (uintptr_t)a.residual % 16 == 0 &&
+                       (uintptr_t)a.y % 16 == 0 && a.ldx % 8 == 0 && a.ldr % 8 == 0 && a.ldy % 8 == 0,
+                   ANEMOI_ERR_UNSUPPORTED,
+                   "%s: bf16, M = a multiple of 256 (+ at most 8 rows), N >= 256, K >= 128, 16-byte aligned", who);
+    return ANEMOI_OK;
+  }
+  if (a.entry == ANEMOI_LINEAR_ENTRY_BATCHED) {
+    ANEMOI_REQUIRE(a.x && a.w && a.y && a.batch > 0 && a.batch < 65536 && M >= 0 && N > 0 && K > 0 && a.ldx >= K && a.ldy >= N,
+                   ANEMOI_ERR_INVALID, "%s: bad argument", who);
+    ANEMOI_REQUIRE(((int64_t)K * esz) % ROW_BYTES == 0 && (uintptr_t)a.x % 16 == 0 && (uintptr_t)a.w % 16 == 0 &&
+                       (a.ldx * esz) % 16 == 0 && (a.stride_x * esz) % 16 == 0 && (a.stride_w * esz) % 16 == 0,
+                   ANEMOI_ERR_INVALID, "%s: K must be a multiple of %d elements, operands 16-byte aligned", who, ROW_BYTES / esz);
+    return ANEMOI_OK;
+  }
+  if (a.entry == ANEMOI_LINEAR_ENTRY_LN) {
+    ANEMOI_REQUIRE(a.colsum && a.stats, ANEMOI_ERR_INVALID, "%s: null colsum / stats", who);
+    ANEMOI_REQUIRE((uintptr_t)a.stats % 8 == 0, ANEMOI_ERR_INVALID, "%s: stats must be 8-byte aligned", who);
+  }
+  if (a.entry == ANEMOI_LINEAR_ENTRY_STATS) {
+    ANEMOI_REQUIRE(a.stats_out != nullptr && (uintptr_t)a.stats_out % 8 == 0, ANEMOI_ERR_INVALID,
+                   "%s: stats_out must be a non-null 8-byte aligned pointer", who);
+    ANEMOI_REQUIRE((a.colsum == nullptr) == (a.stats == nullptr), ANEMOI_ERR_INVALID, "%s: colsum and stats_in come together", who);
+  }
+  ANEMOI_REQUIRE(a.x && a.w && a.y, ANEMOI_ERR_INVALID, "%s: null pointer", who);
   ANEMOI_REQUIRE(M >= 0 && N > 0 && K > 0, ANEMOI_ERR_INVALID, "%s: bad shape M=%lld N=%d K=%d", who, (long long)M, N, K);
-  ANEMOI_REQUIRE(ldx >= K && ldy >= N && (residual == nullptr || ldr >= N), ANEMOI_ERR_INVALID,
+  ANEMOI_REQUIRE(a.ldx >= K && a.ldy >= N && (a.residual == nullptr || a.ldr >= N), ANEMOI_ERR_INVALID,
                  "%s: leading dimension too small", who);
-  ANEMOI_REQUIRE(act >= ANEMOI_ACT_NONE && act <= ANEMOI_ACT_RELU, ANEMOI_ERR_INVALID, "%s: act %d", who, act);
-  const int esz = dtype == ANEMOI_BF16 ? 2 : 4;
+  ANEMOI_REQUIRE(a.act >= ANEMOI_ACT_NONE && a.act <= ANEMOI_ACT_RELU, ANEMOI_ERR_INVALID, "%s: act %d", who, a.act);
   ANEMOI_REQUIRE(((int64_t)K * esz) % ROW_BYTES == 0, ANEMOI_ERR_INVALID,
                  "%s: K=%d must be a multiple of %d for this dtype (pad with zeros)", who, K, ROW_BYTES / esz);
-  ANEMOI_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)w % 16 == 0 && (ldx * esz) % 16 == 0, ANEMOI_ERR_INVALID,
+  ANEMOI_REQUIRE((uintptr_t)a.x % 16 == 0 && (uintptr_t)a.w % 16 == 0 && (a.ldx * esz) % 16 == 0, ANEMOI_ERR_INVALID,
                  "%s: x / W must be 16-byte aligned with a 16-byte multiple row pitch", who);
-  if (M == 0) return ANEMOI_OK;
-  hipStream_t st = as_stream(stream);
-  if (dtype == ANEMOI_F32 && out_dtype == ANEMOI_F32)
-    return linear_launch<float, float>(x, ldx, w, bias, residual, ldr, y, ldy, M, N, K, act, st, ln);
-  constexpr int64_t big_min_m = 1024;  // rows from which the persistent 256 x 256 kernel takes over
-  if (dtype == ANEMOI_BF16 && out_dtype == ANEMOI_BF16 && M >= big_min_m && N >= 256) {
-    // A ragged last row tile would cost every CU of one XCD a full extra round (161 vs 160 row tiles at M = 40 962:
-    // +10 %): the 256-row multiple goes to the persistent kernel, the few remaining rows to the 128 x 128 kernel.
-    const int64_t m_main = M / BIG_M * BIG_M, m_tail = M - m_main;
-    if (m_tail == 0) return linear_bf16_256_launch(x, ldx, w, bias, residual, ldr, y, ldy, M, N, K, act, st, ln);
-    bool tail_done = false;
-    // tails of more than 8 rows ride along as a ragged last row tile of the persistent kernel (its descriptors end at
-    // row M): the separate 128 x 128 launch they used to get ran ~35 us on a handful of CUs, 14 times per forward
-    if (m_tail > 8 && K >= 128) {
-      const int rr = linear_bf16_256_launch(x, ldx, w, bias, residual, ldr, y, ldy, M, N, K, act, st, ln);
-      if (rr != W4_NEEDS_WHOLE_TILES) return rr;
+  return ANEMOI_OK;
+}
+
+// ---- Route plan.
+constexpr int64_t W4_MAX_BLOCKS = 256;  // one persistent workgroup per CU
+constexpr int64_t W4_MIN_M = 1024;      // rows from which the persistent 256 x 256 kernel takes over
+
+static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+static inline bool is_epi(const Args& a) { return a.entry == ANEMOI_LINEAR_ENTRY_DUAL || a.entry == ANEMOI_LINEAR_ENTRY_ACTGRAD; }
+
+// Lab switches for A/B runs, read once per process: ANEMOI_AMD_GEMM_STAGGER="phases,unit,min rounds" overrides the
+// shipped staggered start (phases 0: off), ANEMOI_AMD_GEMM_MH=3|4|5|6|8 forces ONE launch of that tile height wherever
+// the cost model would choose.
+struct W4Lab {
+  int stagger_phases, stagger_unit, stagger_min_rounds, forced_mh;
+};
+static const W4Lab& w4_lab() {
+  static const W4Lab lab = [] {
+    W4Lab v{STAGGER_PHASES, STAGGER_UNIT, STAGGER_MIN_ROUNDS, 0};
+    if (const char* e = getenv("ANEMOI_AMD_GEMM_STAGGER")) sscanf(e, "%d,%d,%d", &v.stagger_phases, &v.stagger_unit, &v.stagger_min_rounds);
+    if (const char* e = getenv("ANEMOI_AMD_GEMM_MH")) v.forced_mh = atoi(e);
+    return v;
+  }();
+  return lab;
+}
+
+static void w4_add_launch(Route& r, int mh, int64_t row0, int64_t rows, int64_t tiles, int tail_rows) {
+  anemoi_linear_route_launch& l = r.launch[r.n_launches++];
+  l.mh = mh;
+  l.row0 = row0;
+  l.rows = rows;
+  l.tiles = tiles;
+  l.blocks = (int)(tiles < W4_MAX_BLOCKS ? (tiles + 7) / 8 * 8 : W4_MAX_BLOCKS);  // whole XCD rows; surplus workgroups exit at once
+  l.tail_rows = tail_rows;
+}
+
+// The persistent kernel on rows 0 .. M of the call, M a multiple of 256 wherever m_tail > 0: the up to 8 rows behind
+// them go to the skinny pass of the last launch.  false: the kernel does not take the call (K = 64, unaligned output,
+// ...), the route is untouched.
+static bool plan_w4(const Args& a, int64_t M, int m_tail, Route& r) {
+  const int N = a.N, K = a.K;
+  const bool vec_ok = (N % 8 == 0) && (a.ldy % 8 == 0) && ((uintptr_t)a.y % 16 == 0) &&
+                      (a.bias == nullptr || (uintptr_t)a.bias % 16 == 0) &&
+                      (a.residual == nullptr || (a.ldr % 8 == 0 && (uintptr_t)a.residual % 16 == 0));
+  if (!(K >= 128 && a.ldx < (int64_t)1 << 21 && a.ldy < (int64_t)1 << 21 && a.ldr < (int64_t)1 << 21 && vec_ok &&
+        (a.colsum == nullptr || (uintptr_t)a.colsum % 16 == 0)))
+    return false;
+  const bool batched = a.entry == ANEMOI_LINEAR_ENTRY_BATCHED, epi = is_epi(a);
+  const int64_t mt = ceil_div(M, BIG_M), nt = ceil_div(N, BIG_N);
+  const int tail = (m_tail > 0 && m_tail <= 8 && K % 8 == 0) ? m_tail : 0;
+  // Remainder round as HALF tiles: when the tiles beyond the last whole round of 256 would keep at most half of the
+  // CUs busy (N = 1024 at M = 40 960: 640 tiles = 2.5 rounds), their rows go to a second launch with 128 x 256 tiles
+  // (MH = 4): twice as many units of half the work -- 2.5+ instead of 3 rounds, no cross-workgroup traffic.
+  int64_t mt_a = mt, mt_b = 0;  // row tiles of 256 for launch A; rows of launch B = mt_b * 256 as half tiles
+  if (!batched && nt <= 256 && 256 % nt == 0) {
+    const int64_t rem_mt = mt % (256 / nt);
+    // measured: a half tile costs ~0.75 of a whole one (its 48 KiB slab per 64 MFMAs is bound by the L2 -> LDS
+    // staging rate), and a second launch ~8 us; so split only a remainder that is the whole problem (small M of a
+    // node-partitioned run: 5120 x 1024 x 4096 0.081 -> 0.052 ms) or belongs to long tiles (K >= 2048: 40 962 x 1024
+    // x 4096 0.314 -> 0.295 ms; at K = 1216 the second launch costs what the half tiles save)
+    // (round 2: splitting EVERY remainder of <= 128 tiles off, whatever K, measured -1 ... +9 % on the per-rank shapes
+    //  5121 x {4096, 2048, 2240, 1024} -- profiles/r02_gemm_small_m.txt -- so the rule stays)
+    // (the whole-problem case, rem_mt == mt, is one candidate of the tile-height model below for the plain epilogues)
+    if (rem_mt > 0 && rem_mt * nt <= 128 && ((rem_mt == mt && epi) || (rem_mt != mt && K >= 2048))) {
+      mt_a = mt - rem_mt;
+      mt_b = rem_mt;
     }
-    const int rc = linear_bf16_256_launch(x, ldx, w, bias, residual, ldr, y, ldy, m_main, N, K, act, st, ln,
-                                          m_tail <= 8 ? (int)m_tail : 0, &tail_done);
-    if (rc != ANEMOI_OK || tail_done) return rc;
-    const bf16_t* xt = static_cast<const bf16_t*>(x) + m_main * ldx;
-    const bf16_t* rt = residual ? static_cast<const bf16_t*>(residual) + m_main * ldr : nullptr;
-    bf16_t* yt = static_cast<bf16_t*>(y) + m_main * ldy;
-    LnFold lt = ln;
-    if (lt.stats != nullptr) lt.stats += m_main;
-    if (m_tail <= 8 && K % 8 == 0) {
-      hipLaunchKernelGGL((linear_bf16_skinny_kernel<8>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, xt, ldx,
-                         static_cast<const bf16_t*>(w), bias, rt, ldr, yt, ldy, (int)m_tail, N, K, act, lt);
-      return check_launch("anemoi_linear(skinny tail)");
-    }
-    return linear_launch<bf16_t, bf16_t>(xt, ldx, w, bias, rt, ldr, yt, ldy, m_tail, N, K, act, st, lt);
   }
-  if (dtype == ANEMOI_BF16 && out_dtype == ANEMOI_BF16)
-    return linear_launch<bf16_t, bf16_t>(x, ldx, w, bias, residual, ldr, y, ldy, M, N, K, act, st, ln);
-  if (dtype == ANEMOI_BF16 && out_dtype == ANEMOI_F32)
-    return linear_launch<bf16_t, float>(x, ldx, w, bias, residual, ldr, y, ldy, M, N, K, act, st, ln);
-  return fail(ANEMOI_ERR_UNSUPPORTED, "%s: dtype %d -> %d", who, dtype, out_dtype);
+  const W4Lab& lab = w4_lab();
+  // Small problems (fewer than four rounds of 256-row tiles -- the per-rank shapes of a node-partitioned run, BASELINE
+  // configs 2 and 5): the tile HEIGHT is chosen per launch among 256 / 192 / 160 / 128 / 96 rows by a two-term model of the
+  // persistent loop, rounds x (epilogue + slabs x staged bytes): the loop is bound by the bytes it stages, so a tile of
+  // 32 MH rows costs (32 MH + 256) / 512 of a whole one per slab (measured 0.75 for MH = 4, 0.875 for MH = 6) and
+  // MH / 8 of its 6.5 us epilogue; what decides is how the tile count quantises against the 256 CUs
+  // (5121 x 2048: 160 / 216 / 256 / 320 tiles -> 160-row tiles fill the chip exactly once;
+  //  5121 x 4096: 320 / 432 / 512 / 640 -> two balanced rounds of 160-row tiles; profiles/r04_gemm_small_m.txt).
+  // (a half-tile split chosen above competes with the single-launch candidates: its cost by the same model = whole rounds of
+  //  256-row tiles + the rounds of half tiles at 0.75 of the slab cost + ~6 us for the second launch.  20 481 x 1024 x 4096,
+  //  one rank of two: 256 + 128 half tiles = 177 against 158 for two rounds of 160-row tiles)
+  int single_mh = 8;
+  if (!batched && !epi && mt * nt < 4 * W4_MAX_BLOCKS) {
+    r.model = 1;
+    double best_cost = 1e30;
+    for (const int mh : W4_HEIGHTS) {
+      const int64_t rounds = ceil_div(ceil_div(M, 32 * mh) * nt, W4_MAX_BLOCKS);
+      const double cost = (double)rounds * (0.8125 * mh + (K / 64) * 1.44 * (32 * mh + 256) / 512.0);
+      if (lab.forced_mh == mh || (lab.forced_mh == 0 && cost < best_cost * 0.97)) {  // (3 %: ties go to the taller tile)
+        best_cost = cost;
+        single_mh = mh;
+        if (lab.forced_mh == mh) break;
+      }
+    }
+    if (mt_b > 0) {
+      const int64_t rounds_a = ceil_div(mt_a * nt, W4_MAX_BLOCKS), rounds_b = ceil_div(mt_b * 2 * nt, W4_MAX_BLOCKS);
+      const double split_cost = (double)rounds_a * (0.8125 * 8 + (K / 64) * 1.44) +
+                                (double)rounds_b * (0.8125 * 4 + (K / 64) * 1.44 * 0.75) + 6.0;
+      if (lab.forced_mh != 0 || best_cost < split_cost * 0.97) {  // one launch of single_mh-row tiles (8 included)
+        mt_a = mt;                                                // (a forced height means ONE launch of that height)
+        mt_b = 0;
+      } else {
+        single_mh = 8;  // the split stands
+      }
+    }
+  }
+  r.kernel = ANEMOI_LINEAR_KERNEL_PERSISTENT;
+  r.vec_ok = 1;
+  r.nt = (int)nt;
+  r.main_rows = M;
+  r.split = mt_b > 0;
+  if (single_mh != 8) {
+    // (no stagger on these launches of one or two rounds: 1 ... 4 units measured 3.20 -> 3.20 ... 3.26 ms at config 2)
+    w4_add_launch(r, single_mh, 0, M, ceil_div(M, 32 * single_mh) * nt, tail);
+  } else {
+    if (mt_a > 0) {
+      const int64_t tiles_a = (batched ? a.batch : 1) * mt_a * nt;
+      w4_add_launch(r, 8, 0, mt_a * BIG_M < M ? mt_a * BIG_M : M, tiles_a, mt_b == 0 ? tail : 0);
+      // Staggered start (LnFold::stagger_*): launches of >= min_rounds rounds of tiles with K >= STAGGER_MIN_K (the K = 256
+      // products measured no gain).  Phase g waits g x unit x 1024 cycles; a SMALL offset is what counts -- 2 x 8 ... 32 units,
+      // 3 x 12, 4 x 8 measured alike, a step of half a tile's time or 16 phases nothing (DESIGN 4.1).
+      if (lab.stagger_phases > 1 && tiles_a >= (int64_t)lab.stagger_min_rounds * W4_MAX_BLOCKS && K >= STAGGER_MIN_K) {
+        r.launch[0].stagger_phases = lab.stagger_phases;
+        r.launch[0].stagger_unit = lab.stagger_unit;
+      }
+    }
+    if (mt_b > 0)  // (its rows may end inside the last 256-row tile)
+      w4_add_launch(r, 4, mt_a * BIG_M, M - mt_a * BIG_M, mt_b * 2 * nt, tail);
+  }
+  if (tail > 0) {
+    r.rest = ANEMOI_LINEAR_REST_IN_LAUNCH;
+    r.rest_row0 = M;
+    r.rest_rows = tail;
+  }
+  // row-sum partials (LnFold::rs_partial): plain epilogue only, whole 256-column tiles only, a workspace that holds them
+  if (a.entry == ANEMOI_LINEAR_ENTRY_STATS && N % BIG_N == 0 && a.workspace != nullptr && (uintptr_t)a.workspace % 8 == 0 &&
+      a.workspace_bytes >= a.M * (N / 128) * 8)
+    r.rs_rows = M;
+  return true;
+}
+
+static int plan_128(const Args& a, int64_t rows, Route& r) {
+  ANEMOI_REQUIRE(ceil_div(rows, BM) * ceil_div(a.N, BN) < (int64_t)1 << 31, ANEMOI_ERR_UNSUPPORTED, "anemoi_linear: grid too large");
+  r.kernel = ANEMOI_LINEAR_KERNEL_128;
+  r.main_rows = rows;
+  r.vec_ok = (a.N % 4 == 0) && (a.ldy % 4 == 0) && ((uintptr_t)a.y % 16 == 0) &&
+             (a.bias == nullptr || (uintptr_t)a.bias % 16 == 0) && (a.colsum == nullptr || (uintptr_t)a.colsum % 16 == 0) &&
+             (a.residual == nullptr || (a.ldr % 4 == 0 && (uintptr_t)a.residual % 16 == 0));
+  return ANEMOI_OK;
+}
+
+// The route of validated arguments, or the status that refuses them.
+static int linear_plan(const Args& a, Route& r) {
+  r = Route{};
+  r.struct_bytes = sizeof(Route);
+  const char* who = LINEAR_ENTRY_NAMES[a.entry];
+  const int64_t M = a.M;
+  if (M == 0) return ANEMOI_OK;
+  const bool bf16_in = a.dtype == ANEMOI_BF16, bf16_out = a.out_dtype == ANEMOI_BF16;
+  const int64_t m_main = M / BIG_M * BIG_M, m_tail = M - m_main;
+  if (is_epi(a)) {  // whole 256-row tiles and at most 8 rows behind them (validated): the persistent kernel or nothing
+    ANEMOI_REQUIRE(ceil_div(m_main, BIG_M) * ceil_div(a.N, BIG_N) < (int64_t)1 << 31, ANEMOI_ERR_UNSUPPORTED, "anemoi_linear: grid too large");
+    if (!plan_w4(a, m_main, (int)m_tail, r)) return fail(ANEMOI_ERR_UNSUPPORTED, "%s: shape not taken by the fast path", who);
+    return ANEMOI_OK;
+  }
+  if (!((a.dtype == ANEMOI_F32 && a.out_dtype == ANEMOI_F32) || (bf16_in && (bf16_out || a.out_dtype == ANEMOI_F32))))
+    return fail(ANEMOI_ERR_UNSUPPORTED, "%s: dtype %d -> %d", who, a.dtype, a.out_dtype);
+  if (a.entry == ANEMOI_LINEAR_ENTRY_BATCHED) {
+    // bf16: the persistent kernel walks the tiles of all problems as one list
+    if (bf16_in && bf16_out && a.K >= 128 && a.N % 8 == 0 && a.ldy % 8 == 0 && (uintptr_t)a.y % 16 == 0 && (a.stride_y * 2) % 16 == 0) {
+      ANEMOI_REQUIRE(ceil_div(M, BIG_M) * ceil_div(a.N, BIG_N) < (int64_t)1 << 31, ANEMOI_ERR_UNSUPPORTED, "anemoi_linear: grid too large");
+      if (plan_w4(a, M, 0, r)) return ANEMOI_OK;
+    }
+    return plan_128(a, M, r);
+  }
+  if (bf16_in && bf16_out && M >= W4_MIN_M && a.N >= 256) {
+    // A ragged last row tile would cost every CU of one XCD a full extra round (161 vs 160 row tiles at M = 40 962:
+    // +10 %): up to 8 rows behind the 256-row multiple go to the skinny pass of the same launch (or, where the persistent
+    // kernel refuses the shape, to the skinny kernel).  Longer tails ride along as a ragged last row tile (the kernel's
+    // descriptors end at row M): the separate 128 x 128 launch they used to get ran ~35 us on a handful of CUs, 14 times
+    // per forward.
+    const int64_t rows = m_tail > 8 ? M : m_main;
+    ANEMOI_REQUIRE(ceil_div(rows, BIG_M) * ceil_div(a.N, BIG_N) < (int64_t)1 << 31, ANEMOI_ERR_UNSUPPORTED, "anemoi_linear: grid too large");
+    if (plan_w4(a, rows, m_tail > 8 ? 0 : (int)m_tail, r)) {
+      if (m_tail == 0 || m_tail > 8 || r.rest == ANEMOI_LINEAR_REST_IN_LAUNCH) return ANEMOI_OK;
+    } else {
+      const int rc = plan_128(a, m_main, r);
+      if (rc != ANEMOI_OK || m_tail == 0) return rc;
+    }
+    r.rest = (m_tail <= 8 && a.K % 8 == 0) ? ANEMOI_LINEAR_REST_SKINNY : ANEMOI_LINEAR_REST_128;
+    r.rest_row0 = m_main;
+    r.rest_rows = m_tail;
+    return ANEMOI_OK;
+  }
+  return plan_128(a, M, r);
+}
+
+// ---- Launch: executes a route.
+template <typename T, typename TO>
+static int launch_128(const Args& a, int64_t row0, int64_t rows, bool vec_ok, hipStream_t st) {
+  LnFold ln{a.colsum, reinterpret_cast<const float2*>(a.stats)};
+  if (ln.stats != nullptr) ln.stats += row0;
+  const T* res = static_cast<const T*>(a.residual);
+  hipLaunchKernelGGL((linear_kernel<T, TO>),
+                     dim3((unsigned)(ceil_div(rows, BM) * ceil_div(a.N, BN)), (unsigned)(a.batch > 0 ? a.batch : 1)), dim3(256), 0,
+                     st, static_cast<const T*>(a.x) + row0 * a.ldx, a.ldx, static_cast<const T*>(a.w), a.bias,
+                     res != nullptr ? res + row0 * a.ldr : nullptr, a.ldr, static_cast<TO*>(a.y) + row0 * a.ldy, a.ldy, rows, a.N,
+                     a.K, a.act, vec_ok ? 1 : 0, ln, a.stride_x, a.stride_w, a.stride_y);
+  return check_launch("anemoi_linear");
+}
+
+static int launch_w4(const Args& a, const Route& r, hipStream_t st) {
+  const int raised = w4_raise_lds_limit();
+  if (raised != ANEMOI_OK) return raised;
+  // DUAL: `residual` / ldr name the second OUTPUT (pre-activation); GMUL: they name the saved pre-activation and the
+  // result is acc * act'(it)
+  const int epi = a.entry == ANEMOI_LINEAR_ENTRY_DUAL ? W4_DUAL : a.entry == ANEMOI_LINEAR_ENTRY_ACTGRAD ? W4_GMUL : W4_PLAIN;
+  const bool has_res = epi == W4_PLAIN ? a.residual != nullptr : epi == W4_GMUL, rs = r.rs_rows > 0;
+  LnFold ln{a.colsum, reinterpret_cast<const float2*>(a.stats)};
+  if (rs) {
+    ln.rs_partial = static_cast<float2*>(a.workspace);
+    ln.rs_slots = a.N / 128;
+  }
+  if (a.entry == ANEMOI_LINEAR_ENTRY_BATCHED) {  // batch problems of mt * nt tiles each, walked as one list
+    ln.b_tiles = ceil_div(a.M, BIG_M) * r.nt;
+    ln.b_sx = a.stride_x;
+    ln.b_sw = a.stride_w;
+    ln.b_sy = a.stride_y;
+    ln.b_count = a.batch;
+  }
+  const bf16_t* res = static_cast<const bf16_t*>(a.residual);
+  for (int i = 0; i < r.n_launches; ++i) {
+    const anemoi_linear_route_launch& l = r.launch[i];
+    const int mh_index = l.mh == 8 ? 0 : l.mh == 6 ? 1 : l.mh == 5 ? 2 : l.mh == 4 ? 3 : 4;
+    const W4Kernel kernel = W4_TABLE[w4_slot(epi, a.act, has_res, ln.stats != nullptr, mh_index, rs)];
+    if (kernel == nullptr || W4_HEIGHTS[mh_index] != l.mh)
+      return fail(ANEMOI_ERR_LAUNCH, "anemoi_linear: no persistent kernel for epilogue %d act %d height %d", epi, a.act, l.mh);
+    LnFold ll = ln;  // this launch's rows: statistics and partials from its first row on, its own stagger
+    if (ll.stats != nullptr) ll.stats += l.row0;
+    if (ll.rs_partial != nullptr) ll.rs_partial += l.row0 * ll.rs_slots;
+    ll.stagger_phases = l.stagger_phases;
+    ll.stagger_unit = l.stagger_unit;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)l.blocks), dim3(256), W4_LDS, st, static_cast<const bf16_t*>(a.x) + l.row0 * a.ldx,
+                       a.ldx, static_cast<const bf16_t*>(a.w), a.bias, res != nullptr ? res + l.row0 * a.ldr : nullptr, a.ldr,
+                       static_cast<bf16_t*>(a.y) + l.row0 * a.ldy, a.ldy, l.rows, a.N, a.K, 1, l.tiles, r.nt, ll, l.tail_rows);
+  }
+  return check_launch("anemoi_linear(256x256, 4 waves)");
+}
+
+static int linear_run(const Args& a, const Route& r, hipStream_t st) {
+  int rc = ANEMOI_OK;
+  if (r.kernel == ANEMOI_LINEAR_KERNEL_PERSISTENT)
+    rc = launch_w4(a, r, st);
+  else if (r.kernel == ANEMOI_LINEAR_KERNEL_128)
+    rc = a.dtype == ANEMOI_F32      ? launch_128<float, float>(a, 0, r.main_rows, r.vec_ok, st)
+         : a.out_dtype == ANEMOI_F32 ? launch_128<bf16_t, float>(a, 0, r.main_rows, r.vec_ok, st)
+                                     : launch_128<bf16_t, bf16_t>(a, 0, r.main_rows, r.vec_ok, st);
+  if (rc != ANEMOI_OK) return rc;
+  if (r.rest == ANEMOI_LINEAR_REST_SKINNY) {
+    LnFold ln{a.colsum, reinterpret_cast<const float2*>(a.stats)};
+    if (ln.stats != nullptr) ln.stats += r.rest_row0;
+    const bf16_t* res = static_cast<const bf16_t*>(a.residual);
+    hipLaunchKernelGGL((linear_bf16_skinny_kernel<8>), dim3((unsigned)((a.N + 3) / 4)), dim3(256), 0, st,
+                       static_cast<const bf16_t*>(a.x) + r.rest_row0 * a.ldx, a.ldx, static_cast<const bf16_t*>(a.w), a.bias,
+                       res != nullptr ? res + r.rest_row0 * a.ldr : nullptr, a.ldr,
+                       static_cast<bf16_t*>(a.y) + r.rest_row0 * a.ldy, a.ldy, (int)r.rest_rows, a.N, a.K, a.act, ln);
+    return check_launch("anemoi_linear(skinny tail)");
+  }
+  if (r.rest == ANEMOI_LINEAR_REST_128) return launch_128<bf16_t, bf16_t>(a, r.rest_row0, r.rest_rows, r.vec_ok, st);
+  return ANEMOI_OK;
+}
+
+// validate, plan, execute: what every entry point of the family does before it notes its outputs on the trail
+static int linear_call(const Args& a, Route& r, anemoi_stream_t stream) {
+  int rc = linear_validate(a);
+  if (rc == ANEMOI_OK) rc = linear_plan(a, r);
+  if (rc == ANEMOI_OK) rc = linear_run(a, r, as_stream(stream));
+  return rc;
+}
+
+static Args linear_args(int entry, int dtype, int out_dtype, const void* x, int64_t ldx, const void* w, const float* bias,
+                        const void* residual, int64_t ldr, void* y, int64_t ldy, int64_t M, int N, int K, int act) {
+  Args a{};
+  a.struct_bytes = sizeof(Args);
+  a.entry = entry;
+  a.dtype = dtype;
+  a.out_dtype = out_dtype;
+  a.act = act;
+  a.x = x;
+  a.w = w;
+  a.bias = bias;
+  a.residual = residual;
+  a.y = y;
+  a.ldx = ldx;
+  a.ldr = ldr;
+  a.ldy = ldy;
+  a.M = M;
+  a.N = N;
+  a.K = K;
+  return a;
+}
+
+extern "C" int anemoi_linear_route(const anemoi_linear_args* args, anemoi_linear_route_info* route) {
+  ANEMOI_REQUIRE(args != nullptr && route != nullptr, ANEMOI_ERR_INVALID, "anemoi_linear_route: null argument");
+  ANEMOI_REQUIRE(args->struct_bytes == (int64_t)sizeof(Args) && route->struct_bytes == (int64_t)sizeof(Route), ANEMOI_ERR_INVALID,
+                 "anemoi_linear_route: argument blocks out of sync with the library (%lld / %lld bytes, expected %lld / %lld)",
+                 (long long)args->struct_bytes, (long long)route->struct_bytes, (long long)sizeof(Args), (long long)sizeof(Route));
+  ANEMOI_REQUIRE(args->entry >= ANEMOI_LINEAR_ENTRY_LINEAR && args->entry <= ANEMOI_LINEAR_ENTRY_BATCHED, ANEMOI_ERR_INVALID,
+                 "anemoi_linear_route: entry %d", args->entry);
+  const int rc = linear_validate(*args);
+  return rc != ANEMOI_OK ? rc : linear_plan(*args, *route);
 }
 
 extern "C" int anemoi_linear(int dtype, int out_dtype, const void* x, int64_t ldx, const void* w, const float* bias,
                              const void* residual, int64_t ldr, void* y, int64_t ldy, int64_t M, int N, int K, int act,
                              anemoi_stream_t stream) {
-  const int rc = linear_dispatch("anemoi_linear", dtype, out_dtype, x, ldx, w, bias, LnFold{nullptr, nullptr}, residual, ldr,
-                                 y, ldy, M, N, K, act, stream);
+  const Args a = linear_args(ANEMOI_LINEAR_ENTRY_LINEAR, dtype, out_dtype, x, ldx, w, bias, residual, ldr, y, ldy, M, N, K, act);
+  Route r;
+  const int rc = linear_call(a, r, stream);
   return trail::note(rc, "anemoi_linear", "out", out_dtype, y, ldy, M, N, as_stream(stream));
 }
 
 extern "C" int anemoi_linear_ln(int dtype, int out_dtype, const void* x, int64_t ldx, const void* w, const float* bias,
                                 const float* colsum, const float* stats, const void* residual, int64_t ldr, void* y,
                                 int64_t ldy, int64_t M, int N, int K, int act, anemoi_stream_t stream) {
-  ANEMOI_REQUIRE(colsum && stats, ANEMOI_ERR_INVALID, "anemoi_linear_ln: null colsum / stats");
-  ANEMOI_REQUIRE((uintptr_t)stats % 8 == 0, ANEMOI_ERR_INVALID, "anemoi_linear_ln: stats must be 8-byte aligned");
-  const int rc = linear_dispatch("anemoi_linear_ln", dtype, out_dtype, x, ldx, w, bias,
-                                 LnFold{colsum, reinterpret_cast<const float2*>(stats)}, residual, ldr, y, ldy, M, N, K, act,
-                                 stream);
+  Args a = linear_args(ANEMOI_LINEAR_ENTRY_LN, dtype, out_dtype, x, ldx, w, bias, residual, ldr, y, ldy, M, N, K, act);
+  a.colsum = colsum;
+  a.stats = stats;
+  Route r;
+  const int rc = linear_call(a, r, stream);
   return trail::note(rc, "anemoi_linear_ln", "out", out_dtype, y, ldy, M, N, as_stream(stream));
 }
 
@@ -1439,29 +1527,14 @@ __global__ __launch_bounds__(256) void row_sums_finalize_kernel(const float2* __
 }  // namespace anemoi
 
 // y = act(x W^T + b) AND pre = x W^T + b (bf16) from one launch of the persistent kernel (training forward: the backward
-// needs act'(pre)).  bf16, whole 256-row tiles, the fast path's shape / alignment rules; ANEMOI_ERR_UNSUPPORTED otherwise
-// (the caller then runs anemoi_linear + anemoi_act_forward).
+// needs act'(pre)).  bf16, whole 256-row tiles and at most 8 rows behind them, the fast path's shape / alignment rules;
+// ANEMOI_ERR_UNSUPPORTED otherwise (the caller then runs anemoi_linear + anemoi_act_forward).
 extern "C" int anemoi_linear_dual(int dtype, const void* x, int64_t ldx, const void* w, const float* bias, void* pre,
                                   int64_t ldp, void* y, int64_t ldy, int64_t M, int N, int K, int act,
                                   anemoi_stream_t stream) {
-  using namespace anemoi;
-  ANEMOI_REQUIRE(x && w && pre && y, ANEMOI_ERR_INVALID, "anemoi_linear_dual: null pointer");
-  ANEMOI_REQUIRE(M >= 0 && N > 0 && K > 0 && ldx >= K && ldy >= N && ldp >= N, ANEMOI_ERR_INVALID,
-                 "anemoi_linear_dual: bad shape");
-  ANEMOI_REQUIRE(act > ANEMOI_ACT_NONE && act <= ANEMOI_ACT_RELU, ANEMOI_ERR_INVALID, "anemoi_linear_dual: act %d", act);
-  // (up to 8 rows behind the last whole 256-row tile are computed by the same launch: the skinny pass of the kernel)
-  ANEMOI_REQUIRE(dtype == ANEMOI_BF16 && M % BIG_M <= 8 && (M >= BIG_M || M == 0) && N >= 256 && N % 8 == 0 && K >= 128 &&
-                     K % 64 == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)w % 16 == 0 && (uintptr_t)pre % 16 == 0 &&
-                     (uintptr_t)y % 16 == 0 && ldx % 8 == 0 && ldp % 8 == 0 && ldy % 8 == 0,
-                 ANEMOI_ERR_UNSUPPORTED,
-                 "anemoi_linear_dual: bf16, M = a multiple of 256 (+ at most 8 rows), N >= 256, K >= 128, 16-byte aligned");
-  if (M == 0) return ANEMOI_OK;
-  bool tail_done = false;
-  const int rc = linear_bf16_256_launch(x, ldx, w, bias, pre, ldp, y, ldy, M / BIG_M * BIG_M, N, K, act, as_stream(stream),
-                                        LnFold{nullptr, nullptr}, (int)(M % BIG_M), &tail_done, 1);
-  if (rc == ANEMOI_OK && M % BIG_M != 0 && !tail_done)
-    return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_linear_dual: the ragged rows were not taken by the fast path");
-  if (rc == W4_NEEDS_WHOLE_TILES) return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_linear_dual: shape not taken by the fast path");
+  const Args a = linear_args(ANEMOI_LINEAR_ENTRY_DUAL, dtype, dtype, x, ldx, w, bias, pre, ldp, y, ldy, M, N, K, act);
+  Route r;
+  const int rc = linear_call(a, r, stream);
   const int rt = trail::note(rc, "anemoi_linear_dual", "out", dtype, y, ldy, M, N, as_stream(stream));
   return trail::note(rt, "anemoi_linear_dual", "pre", dtype, pre, ldp, M, N, as_stream(stream));
 }
@@ -1471,24 +1544,9 @@ extern "C" int anemoi_linear_dual(int dtype, const void* x, int64_t ldx, const v
 // anemoi_linear_dual; ANEMOI_ERR_UNSUPPORTED otherwise (the caller then runs anemoi_linear + anemoi_act_backward).
 extern "C" int anemoi_linear_actgrad(int dtype, const void* x, int64_t ldx, const void* w, const void* pre, int64_t ldp,
                                      void* y, int64_t ldy, int64_t M, int N, int K, int act, anemoi_stream_t stream) {
-  using namespace anemoi;
-  ANEMOI_REQUIRE(x && w && pre && y, ANEMOI_ERR_INVALID, "anemoi_linear_actgrad: null pointer");
-  ANEMOI_REQUIRE(M >= 0 && N > 0 && K > 0 && ldx >= K && ldy >= N && ldp >= N, ANEMOI_ERR_INVALID,
-                 "anemoi_linear_actgrad: bad shape");
-  ANEMOI_REQUIRE(act > ANEMOI_ACT_NONE && act <= ANEMOI_ACT_RELU, ANEMOI_ERR_INVALID, "anemoi_linear_actgrad: act %d", act);
-  ANEMOI_REQUIRE(dtype == ANEMOI_BF16 && M % BIG_M <= 8 && (M >= BIG_M || M == 0) && N >= 256 && N % 8 == 0 && K >= 128 &&
-                     K % 64 == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)w % 16 == 0 && (uintptr_t)pre % 16 == 0 &&
-                     (uintptr_t)y % 16 == 0 && ldx % 8 == 0 && ldp % 8 == 0 && ldy % 8 == 0,
-                 ANEMOI_ERR_UNSUPPORTED,
-                 "anemoi_linear_actgrad: bf16, M = a multiple of 256 (+ at most 8 rows), N >= 256, K >= 128, 16-byte aligned");
-  if (M == 0) return ANEMOI_OK;
-  bool tail_done = false;
-  const int rc = linear_bf16_256_launch(x, ldx, w, nullptr, pre, ldp, y, ldy, M / BIG_M * BIG_M, N, K, act, as_stream(stream),
-                                        LnFold{nullptr, nullptr}, (int)(M % BIG_M), &tail_done, 2);
-  if (rc == ANEMOI_OK && M % BIG_M != 0 && !tail_done)
-    return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_linear_actgrad: the ragged rows were not taken by the fast path");
-  if (rc == W4_NEEDS_WHOLE_TILES)
-    return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_linear_actgrad: shape not taken by the fast path");
+  const Args a = linear_args(ANEMOI_LINEAR_ENTRY_ACTGRAD, dtype, dtype, x, ldx, w, nullptr, pre, ldp, y, ldy, M, N, K, act);
+  Route r;
+  const int rc = linear_call(a, r, stream);
   return trail::note(rc, "anemoi_linear_actgrad", "out", dtype, y, ldy, M, N, as_stream(stream));
 }
 
@@ -1496,28 +1554,21 @@ extern "C" int anemoi_linear_stats(int dtype, const void* x, int64_t ldx, const 
                                    const float* colsum, const float* stats_in, const void* residual, int64_t ldr,
                                    void* y, int64_t ldy, int64_t M, int N, int K, void* workspace,
                                    int64_t workspace_bytes, float eps, float* stats_out, anemoi_stream_t stream) {
-  using namespace anemoi;
-  ANEMOI_REQUIRE(stats_out != nullptr && (uintptr_t)stats_out % 8 == 0, ANEMOI_ERR_INVALID,
-                 "anemoi_linear_stats: stats_out must be a non-null 8-byte aligned pointer");
-  ANEMOI_REQUIRE((colsum == nullptr) == (stats_in == nullptr), ANEMOI_ERR_INVALID,
-                 "anemoi_linear_stats: colsum and stats_in come together");
-  int64_t rows_done = 0;
-  LnFold ln{colsum, reinterpret_cast<const float2*>(stats_in), nullptr, 0, nullptr};
-  const int slots = N / 128;
-  if (dtype == ANEMOI_BF16 && N % 256 == 0 && workspace != nullptr && (uintptr_t)workspace % 8 == 0 &&
-      workspace_bytes >= M * slots * 8) {
-    ln.rs_partial = static_cast<float2*>(workspace);
-    ln.rs_slots = slots;
-    ln.rs_rows_done = &rows_done;
-  }
-  const int rc = linear_dispatch("anemoi_linear_stats", dtype, dtype, x, ldx, w, bias, ln, residual, ldr, y, ldy, M, N,
-                                 K, ANEMOI_ACT_NONE, stream);
+  Args a = linear_args(ANEMOI_LINEAR_ENTRY_STATS, dtype, dtype, x, ldx, w, bias, residual, ldr, y, ldy, M, N, K, ANEMOI_ACT_NONE);
+  a.colsum = colsum;
+  a.stats = stats_in;
+  a.workspace = workspace;
+  a.workspace_bytes = workspace_bytes;
+  a.stats_out = stats_out;
+  Route r;
+  const int rc = linear_call(a, r, stream);
   if (rc != ANEMOI_OK) return rc;
+  int64_t rows_done = r.rs_rows;  // leading rows whose partials the persistent kernel left in the workspace
   if (rows_done > 0) {
     // rows behind the tiled part (at most 8, from the skinny pass) are folded in by extra blocks of the same launch
     const int64_t tail = (M - rows_done <= 8 && dtype == ANEMOI_BF16) ? M - rows_done : 0;
     hipLaunchKernelGGL(row_sums_finalize_kernel, dim3((unsigned)((rows_done + 255) / 256 + tail)), dim3(256), 0,
-                       as_stream(stream), static_cast<const float2*>(workspace), slots, rows_done, N, eps,
+                       as_stream(stream), static_cast<const float2*>(workspace), N / 128, rows_done, N, eps,
                        reinterpret_cast<float2*>(stats_out), static_cast<const bf16_t*>(y), ldy, rows_done + tail);
     const int rl = check_launch("anemoi_linear_stats(finalize)");
     if (rl != ANEMOI_OK) return rl;
@@ -1534,54 +1585,23 @@ extern "C" int anemoi_linear_stats(int dtype, const void* x, int64_t ldx, const 
 }
 
 
+
 // ---------------------------------------------------------------------------------------------
-// `batch` independent products y[b] = x[b] w[b]^T (no bias / activation) on the 128 x 128 kernel, problems along grid.y.
+// `batch` independent products y[b] = x[b] w[b]^T (no bias / activation): one list of tiles on the persistent kernel
+// (bf16), problems along grid.y on the 128 x 128 kernel otherwise.
 // The weight-gradient GEMMs use it as a deterministic split of their long reduction (anemoi_models_amd/autograd.py):
 // dW = sum_b dpre[b]^T X[b] over row chunks b, so that a small [N, K] result still fills the chip.
 // ---------------------------------------------------------------------------------------------
-static int linear_batched_impl(int dtype, int out_dtype, const void* x, int64_t ldx, int64_t stride_x, const void* w,
-                               int64_t stride_w, void* y, int64_t ldy, int64_t stride_y, int batch, int64_t M, int N, int K,
-                               anemoi_stream_t stream) {
-  using namespace anemoi;
-  ANEMOI_REQUIRE(x && w && y && batch > 0 && batch < 65536 && M >= 0 && N > 0 && K > 0 && ldx >= K && ldy >= N,
-                 ANEMOI_ERR_INVALID, "anemoi_linear_batched: bad argument");
-  const int esz = dtype == ANEMOI_BF16 ? 2 : 4;
-  ANEMOI_REQUIRE(((int64_t)K * esz) % ROW_BYTES == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)w % 16 == 0 &&
-                     (ldx * esz) % 16 == 0 && (stride_x * esz) % 16 == 0 && (stride_w * esz) % 16 == 0,
-                 ANEMOI_ERR_INVALID, "anemoi_linear_batched: K must be a multiple of %d elements, operands 16-byte aligned",
-                 ROW_BYTES / esz);
-  if (M == 0) return ANEMOI_OK;
-  hipStream_t st = as_stream(stream);
-  const LnFold none{nullptr, nullptr, nullptr, 0, nullptr};
-  if (dtype == ANEMOI_F32 && out_dtype == ANEMOI_F32)
-    return linear_launch<float, float>(x, ldx, w, nullptr, nullptr, 0, y, ldy, M, N, K, ANEMOI_ACT_NONE, st, none, batch,
-                                       stride_x, stride_w, stride_y);
-  if (dtype == ANEMOI_BF16 && out_dtype == ANEMOI_F32)
-    return linear_launch<bf16_t, float>(x, ldx, w, nullptr, nullptr, 0, y, ldy, M, N, K, ANEMOI_ACT_NONE, st, none, batch,
-                                        stride_x, stride_w, stride_y);
-  if (dtype == ANEMOI_BF16 && out_dtype == ANEMOI_BF16) {
-    if (K >= 128 && N % 8 == 0 && ldy % 8 == 0 && (uintptr_t)y % 16 == 0 && (stride_y * 2) % 16 == 0) {
-      // the persistent 256 x 256 kernel walks the tiles of all problems as one list
-      LnFold bl = none;
-      bl.b_tiles = ((M + BIG_M - 1) / BIG_M) * ((N + BIG_N - 1) / BIG_N);
-      bl.b_sx = stride_x;
-      bl.b_sw = stride_w;
-      bl.b_sy = stride_y;
-      bl.b_count = batch;
-      const int rc = linear_bf16_256_launch(x, ldx, w, nullptr, nullptr, 0, y, ldy, M, N, K, ANEMOI_ACT_NONE, st, bl);
-      if (rc != W4_NEEDS_WHOLE_TILES) return rc;
-    }
-    return linear_launch<bf16_t, bf16_t>(x, ldx, w, nullptr, nullptr, 0, y, ldy, M, N, K, ANEMOI_ACT_NONE, st, none,
-                                         batch, stride_x, stride_w, stride_y);
-  }
-  return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_linear_batched: dtype %d -> %d", dtype, out_dtype);
-}
-
 extern "C" int anemoi_linear_batched(int dtype, int out_dtype, const void* x, int64_t ldx, int64_t stride_x,
                                      const void* w, int64_t stride_w, void* y, int64_t ldy, int64_t stride_y, int batch,
                                      int64_t M, int N, int K, anemoi_stream_t stream) {
-  using namespace anemoi;
-  int rc = linear_batched_impl(dtype, out_dtype, x, ldx, stride_x, w, stride_w, y, ldy, stride_y, batch, M, N, K, stream);
+  Args a = linear_args(ANEMOI_LINEAR_ENTRY_BATCHED, dtype, out_dtype, x, ldx, w, nullptr, nullptr, 0, y, ldy, M, N, K, ANEMOI_ACT_NONE);
+  a.batch = batch;
+  a.stride_x = stride_x;
+  a.stride_w = stride_w;
+  a.stride_y = stride_y;
+  Route r;
+  int rc = linear_call(a, r, stream);
   if (M == 0 || trail::armed_state() == nullptr) return rc;
   if (stride_y == M * ldy)  // the problems' outputs are one [batch * M, N] matrix
     return trail::note(rc, "anemoi_linear_batched", "out", out_dtype, y, ldy, (int64_t)batch * M, N, as_stream(stream));
@@ -1591,3 +1611,4 @@ extern "C" int anemoi_linear_batched(int dtype, int out_dtype, const void* x, in
                      as_stream(stream));
   return rc;
 }
+

@@ -1358,6 +1358,18 @@ def row_scale(x: Tensor, s: Tensor, alpha: float = 1.0, out: Optional[Tensor] = 
     return out
 
 
+def _fused_epilogue_rows(dtype, m: int, n: int, k: int, ldx: int, ldp: int = 0) -> int:
+    """Rows that ``linear_dual`` / ``linear_actgrad`` hand to the persistent kernel's DUAL / GMUL epilogue (``ldp``: pitch of the
+    saved pre-activation, 0 where the call allocates it): the whole 256-row tiles of a bf16 product the library takes, from
+    1024 of them on, and up to 8 ragged rows behind them (the launch's skinny pass).  0: the two-pass pair does it all."""
+    if not (dtype == torch.bfloat16 and n >= 256 and n % 8 == 0 and k >= 128 and k % 64 == 0 and ldx % 8 == 0 and ldp % 8 == 0):
+        return 0
+    m_main = (m // 256) * 256
+    if m_main < 1024:
+        return 0
+    return m if m - m_main <= 8 else m_main
+
+
 def linear_dual(x: Tensor, w: Tensor, bias: Optional[Tensor], act: str):
     """``(pre, y) = (x @ w.T + bias, act(pre))``: the training forward of Linear + activation.  One launch
     (``anemoi_linear_dual``) for the whole 256-row tiles of a bf16 product and up to 8 rows behind them, the GEMM +
@@ -1367,15 +1379,12 @@ def linear_dual(x: Tensor, w: Tensor, bias: Optional[Tensor], act: str):
     n = w.shape[0]
     if w.dtype != x.dtype or not w.is_contiguous() or w.shape[1] != k:
         raise ValueError("linear_dual: weight must be contiguous [N, K] in the activation dtype, K as x")
-    m_main = (m // 256) * 256 if (x.dtype == torch.bfloat16 and n >= 256 and n % 8 == 0 and k >= 128 and k % 64 == 0
-                                  and _ld(x) % 8 == 0) else 0
-    if m_main < 1024:
+    m_main = _fused_epilogue_rows(x.dtype, m, n, k, _ld(x))
+    if m_main == 0:
         pre = linear(x, w, bias)
         return pre, act_forward(pre, act)
     pre = torch.empty((m, n), dtype=x.dtype, device=x.device)
     y = torch.empty((m, n), dtype=x.dtype, device=x.device)
-    if m - m_main <= 8:  # the launch computes up to 8 ragged rows itself (its skinny pass)
-        m_main = m
     with _Timed("linear", flops=2 * m_main * n * k, bytes=(m_main * k + n * k + 2 * m_main * n) * 2, m=m_main, n=n, k=k):
         st = _lib.load().anemoi_linear_dual(dtype_code(x.dtype), x.data_ptr(), _ld(x), w.data_ptr(), _ptr(bias),
                                             pre.data_ptr(), n, y.data_ptr(), n, m_main, n, k, _lib.ACT_CODES[act], _stream())
@@ -1394,13 +1403,10 @@ def linear_actgrad(x: Tensor, w: Tensor, pre: Tensor, act: str) -> Tensor:
     n = w.shape[0]
     if w.dtype != x.dtype or not w.is_contiguous() or w.shape[1] != k or tuple(_rows(pre).shape) != (m, n):
         raise ValueError("linear_actgrad: w must be contiguous [N, K] in the activation dtype, pre [M, N]")
-    m_main = (m // 256) * 256 if (x.dtype == torch.bfloat16 and n >= 256 and n % 8 == 0 and k >= 128 and k % 64 == 0
-                                  and _ld(x) % 8 == 0 and _ld(_rows(pre)) % 8 == 0) else 0
-    if m_main < 1024:
+    m_main = _fused_epilogue_rows(x.dtype, m, n, k, _ld(x), _ld(_rows(pre)))
+    if m_main == 0:
         return act_backward(pre, linear(x, w), act)
     out = torch.empty((m, n), dtype=x.dtype, device=x.device)
-    if m - m_main <= 8:  # (as linear_dual)
-        m_main = m
     with _Timed("linear", flops=2 * m_main * n * k, bytes=(m_main * k + n * k + 2 * m_main * n) * 2, m=m_main, n=n, k=k):
         st = _lib.load().anemoi_linear_actgrad(dtype_code(x.dtype), x.data_ptr(), _ld(x), w.data_ptr(), pre.data_ptr(),
                                                _ld(_rows(pre)), out.data_ptr(), n, m_main, n, k, _lib.ACT_CODES[act],

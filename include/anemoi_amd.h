@@ -754,6 +754,73 @@ int anemoi_linear_actgrad(int dtype, const void* x, int64_t ldx, const void* w, 
                           int64_t ldy, int64_t M, int N, int K, int act, anemoi_stream_t stream);
 
 /*
+ * Route query of the fused Linear family (tests and diagnostics; nothing on the hot path calls it).  Every entry point
+ * above gathers its arguments in an anemoi_linear_args, validates them, plans an anemoi_linear_route_info and executes it;
+ * anemoi_linear_route runs the same validation and the same plan on the same two types, launches nothing and touches no
+ * device, and returns the status the entry point would return before its first launch.  Pointers are looked at for NULL
+ * and alignment only.  Fields an entry point does not have stay 0 / NULL.  `struct_bytes` of both blocks must be their
+ * sizeof (layout check across the FFI).
+ */
+enum {
+  ANEMOI_LINEAR_ENTRY_LINEAR = 0,
+  ANEMOI_LINEAR_ENTRY_LN = 1,
+  ANEMOI_LINEAR_ENTRY_STATS = 2,
+  ANEMOI_LINEAR_ENTRY_DUAL = 3,
+  ANEMOI_LINEAR_ENTRY_ACTGRAD = 4,
+  ANEMOI_LINEAR_ENTRY_BATCHED = 5
+};
+enum { ANEMOI_LINEAR_KERNEL_NONE = 0, ANEMOI_LINEAR_KERNEL_128 = 1, ANEMOI_LINEAR_KERNEL_PERSISTENT = 2 };
+enum {
+  ANEMOI_LINEAR_REST_NONE = 0,
+  ANEMOI_LINEAR_REST_IN_LAUNCH = 1, /* the persistent kernel's own skinny pass */
+  ANEMOI_LINEAR_REST_SKINNY = 2,    /* the stand-alone skinny kernel */
+  ANEMOI_LINEAR_REST_128 = 3        /* a launch of the 128 x 128 kernel */
+};
+
+typedef struct anemoi_linear_args {
+  int64_t struct_bytes;
+  int32_t entry, dtype, out_dtype, act;
+  const void* x;
+  const void* w;
+  const float* bias;
+  const float* colsum; /* LayerNorm fold (_ln, _stats) */
+  const float* stats;
+  const void* residual; /* the residual; `pre` of _dual (an output) and _actgrad (an input), ldr = ldp */
+  void* y;
+  int64_t ldx, ldr, ldy, M;
+  int32_t N, K;
+  void* workspace; /* _stats */
+  int64_t workspace_bytes;
+  float* stats_out;
+  int64_t stride_x, stride_w, stride_y; /* _batched */
+  int32_t batch, reserved;
+} anemoi_linear_args;
+
+typedef struct anemoi_linear_route_launch { /* one launch of the persistent kernel */
+  int64_t row0, rows, tiles;                 /* first row, rows, tiles of 32 mh x 256 (all problems of a batched call) */
+  int32_t mh, blocks, tail_rows;             /* tile height / 32; workgroups; rows behind `rows` on the in-launch skinny pass */
+  int32_t stagger_phases, stagger_unit, reserved;
+} anemoi_linear_route_launch;
+
+typedef struct anemoi_linear_route_info {
+  int64_t struct_bytes;
+  int32_t kernel;     /* ANEMOI_LINEAR_KERNEL_*: what computes rows 0 .. main_rows (NONE: M = 0, nothing to do) */
+  int32_t n_launches; /* persistent kernel: 1 or 2 */
+  anemoi_linear_route_launch launch[2];
+  int64_t main_rows;
+  int32_t rest; /* ANEMOI_LINEAR_REST_*: what computes the rest_rows rows from rest_row0 on */
+  int32_t nt;   /* persistent kernel: column tiles of 256 */
+  int64_t rest_row0, rest_rows;
+  int64_t rs_rows; /* leading rows whose row-sum partials the launches leave in the workspace (_stats); 0: none */
+  int32_t vec_ok;  /* the epilogue's vector path (the kernel family's own rule) */
+  int32_t split;   /* the launches are the half-tile split: [256-row tiles,] 128-row tiles of the remainder round */
+  int32_t model;   /* the tile-height cost model ran */
+  int32_t reserved;
+} anemoi_linear_route_info;
+
+int anemoi_linear_route(const anemoi_linear_args* args, anemoi_linear_route_info* route);
+
+/*
  * LayerNorm backward from the forward's row statistics (stats [rows, 2] = { rstd, -mean * rstd }, anemoi_row_stats):
  *   dx = rstd * (g - mean_c(g) - xhat * mean_c(g * xhat)), g = dy * gamma, xhat = x * rstd - mean * rstd;
  *   dgamma[c] = sum_r dy * xhat, dbeta[c] = sum_r dy (f32).  workspace: anemoi_layer_norm_backward_workspace_floats.

@@ -113,7 +113,7 @@ def _generic(M, N, ldy, ldr, ptrs, res, fold, tail="none"):
 
 
 def _w4(M, N, K, ldx, ldy, ldr, ptrs, act, res, fold, stats, epi, batch, m_tail):
-    """linear_bf16_256_launch: None when the persistent kernel refuses the shape."""
+    """csrc/gemm.hip::plan_w4: None when the persistent kernel refuses the shape."""
     y, b, r, cs = ptrs
     vec = N % 8 == 0 and ldy % 8 == 0 and y % 16 == 0 and b % 16 == 0 and (not res or (ldr % 8 == 0 and r % 16 == 0))
     if not (K >= 128 and max(ldx, ldy, ldr) < 1 << 21 and vec and (M % BIG == 0 or m_tail == 0) and (not fold or cs % 16 == 0)):
@@ -162,8 +162,8 @@ def _w4(M, N, K, ldx, ldy, ldr, ptrs, act, res, fold, stats, epi, batch, m_tail)
 
 def route(dtype, out_dtype, M, N, K, ldx, ldy, ldr, ptrs=(0, 0, 0, 0), act="Identity", res=False, fold=False, stats=False,
           epi=0, batch=0):
-    """What ``linear_dispatch`` / ``linear_bf16_256_launch`` / ``linear_batched_impl`` (and, for dual / actgrad, ops.py in front of
-    them) do with these arguments.  ``ptrs`` = (y, bias, residual, colsum) addresses, ``epi`` 1 = dual, 2 = actgrad, ``batch`` =
+    """What csrc/gemm.hip::linear_plan (and, for dual / actgrad, ops.py in front of it) does with these arguments, restated
+    without the library; tests/test_linear_ref_cpu.py holds it against ``anemoi_linear_route``.  ``ptrs`` = (y, bias, residual, colsum) addresses, ``epi`` 1 = dual, 2 = actgrad, ``batch`` =
     problems of ``linear_heads`` (0: not batched).  ``main_rows``: rows computed by the persistent kernel's tiles."""
     if batch > 0:
         if dtype == BF16 and out_dtype == BF16 and K >= 128 and N % 8 == 0 and ldy % 8 == 0 and ptrs[0] % 16 == 0:

@@ -39,6 +39,31 @@ def test_argument_validation_without_gpu():
     assert st == _lib.ANEMOI_ERR_INVALID and b"multiple" in lib.anemoi_last_error()
 
 
+def test_linear_route_query_without_gpu():
+    """anemoi_linear_route: the struct_bytes handshake of both blocks, the entry point's own refusal, and a route."""
+    from anemoi_models_amd import _lib
+
+    lib = _lib.load()
+    args, route = _lib.LinearArgs(), _lib.LinearRoute()
+    assert lib.anemoi_linear_route(None, ctypes.byref(route)) == _lib.ANEMOI_ERR_INVALID
+    args.struct_bytes, route.struct_bytes = ctypes.sizeof(_lib.LinearArgs), ctypes.sizeof(_lib.LinearRoute) - 8
+    assert lib.anemoi_linear_route(ctypes.byref(args), ctypes.byref(route)) == _lib.ANEMOI_ERR_INVALID
+    assert b"out of sync" in lib.anemoi_last_error()
+    args.struct_bytes, route.struct_bytes = 8, ctypes.sizeof(_lib.LinearRoute)
+    assert lib.anemoi_linear_route(ctypes.byref(args), ctypes.byref(route)) == _lib.ANEMOI_ERR_INVALID
+    assert b"out of sync" in lib.anemoi_last_error()
+    shape = dict(dtype=_lib.BF16, out_dtype=_lib.BF16, x=16, w=16, y=16, ldx=48, ldy=8, M=4, N=8, K=48)  # K = 48, as above
+    st, _ = _lib.linear_route("linear", **shape)
+    assert st == _lib.ANEMOI_ERR_INVALID and b"anemoi_linear: K=48 must be a multiple" in lib.anemoi_last_error()
+    st, _ = _lib.linear_route("dual", **dict(shape, K=128, ldx=128, residual=16, ldr=8, act=_lib.ACT_GELU))
+    assert st == _lib.ANEMOI_ERR_UNSUPPORTED and b"anemoi_linear_dual: bf16, M = a multiple of 256" in lib.anemoi_last_error()
+    st, r = _lib.linear_route("linear", **dict(shape, K=64, ldx=64))
+    assert st == _lib.ANEMOI_OK and (r.kernel, r.main_rows, r.n_launches, r.rest) == (_lib.LINEAR_KERNEL_128, 4, 0, _lib.LINEAR_REST_NONE)
+    st, r = _lib.linear_route("linear", **dict(shape, M=1027, N=256, K=128, ldx=128, ldy=256))
+    assert st == _lib.ANEMOI_OK and (r.kernel, r.main_rows, r.rest, r.rest_row0, r.rest_rows) == \
+        (_lib.LINEAR_KERNEL_PERSISTENT, 1024, _lib.LINEAR_REST_IN_LAUNCH, 1024, 3)
+
+
 def test_block_level_entry_points_validate_their_argument_block_without_gpu():
     """anemoi_gt_block_tail / anemoi_gt_processor_block_forward (SURVEY section 8b's block-level boundary): the ctypes
     mirror of ``anemoi_gt_block_args`` has the size the library was compiled with, and a bad block is refused with a

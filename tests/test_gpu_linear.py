@@ -5,7 +5,9 @@ bound 0, compared by bits).  tests/test_linear_ref_cpu.py shows that emulations 
 bounds and that the wrong kernels listed there do not, and that the case table reaches every route.
 
 Every case restates the launcher's dispatch on its own tensors (``_linear_ref.route``) and asserts the route it names; a case
-whose route differs FAILS.  Operands sit in NaN-guarded buffers (rows before and after x, W, the residual and pre, the pad
+whose route differs FAILS.  The restatement is then held against the launcher's own plan for the same pointers
+(``anemoi_linear_route``: kernel, launches, tiles, workgroups, tail, stagger), so the route a case names is the one that ran.
+Operands sit in NaN-guarded buffers (rows before and after x, W, the residual and pre, the pad
 columns K..ldx and N..ldr, the entries behind the bias, the column sums and the statistics); ``y`` (and, through the library
 entry points, ``pre``) sit in buffers holding a bit pattern that must be untouched outside the view, the pad N..ldy included.
 Every case runs twice and must repeat bit for bit.
@@ -57,6 +59,7 @@ import pytest
 import torch
 
 import _linear_ref as R
+from test_linear_ref_cpu import assert_same_route, case_library_route
 
 pytestmark = pytest.mark.gpu
 
@@ -144,6 +147,9 @@ def _call(c, o):
             0 if gcs is None else gcs.view.data_ptr())
     rt = R.case_route(c, ptrs)
     assert R.route_str(rt) == c.expect, f"{R.case_id(c)}: the launcher takes {R.route_str(rt)}, the case names {c.expect}"
+    # ... and the launcher's own plan on these pointers (anemoi_linear_route) is the restated one, launch for launch
+    st, lib_rt, rows = case_library_route(c, ptrs, x=gx.view.data_ptr(), w=gw.view.data_ptr())
+    assert_same_route(rt, st, lib_rt, c.m, c.n, c.h, rows, R.case_id(c))
     out = {}
     what = R.case_id(c)
     if c.kind == "linear":

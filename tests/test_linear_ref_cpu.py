@@ -2,6 +2,9 @@
   * the restated dispatch reaches every route on the case table (every tile height whole and ragged, every tail template, the
     stand-alone skinny kernel, the 128 x 128 tail, nt in {1, < 8, 16, 17..23, 24}, split, stagger, the skipped cost model, the
     batched walk, both vector states of the 128 x 128 kernel) and every case names the route it gets;
+  * the restated dispatch IS the library's: ``anemoi_linear_route`` (the entry points' own validation and plan, no GPU) gives
+    the same route on every case of the table and on a sweep of 443 520 argument sets, launch for launch; the two lab
+    switches reach the plan (a fresh child process each);
   * emulations of the kernels' arithmetic stay inside the bounds on every data kind: bf16 products exact in f32, f32
     accumulation in slab order, the skinny passes' lane-strided fmaf chain and butterfly, the epilogue in f32 with the
     documented polynomials (as numbers, _linear_ref.GELU_Q / DGELU_Q), round / add residual / round again -- at every case small
@@ -282,6 +285,176 @@ def test_tile_walk_covers_every_tile_once():
         for mt in (1, 4, 11):
             seen = {R.tile_coords(t, nt, mt) for t in range(mt * nt)}
             assert seen == {(i, j) for i in range(mt) for j in range(nt)}, (nt, mt)
+
+
+# ------------------------------------------------------------------------------------------------ the library's own route
+# ``anemoi_linear_route`` runs the validation and the plan of the entry points on integers (no GPU, nothing launched): the
+# restatement above is held against it, so "the launcher takes X" in tests/test_gpu_linear.py describes the launcher itself.
+FAKE = dict(x=0x10000000, w=0x20000000, y=0x30000000, bias=0x40000000, residual=0x50000000, colsum=0x60000000,
+            stats=0x70000000, workspace=0x80000000, stats_out=0x90000000)  # 16-byte aligned stand-ins: only looked at, never read
+
+
+def library_route(dtype, out_dtype, M, N, K, ldx, ldy, ldr, ptrs, act="Identity", res=False, fold=False, stats=False, epi=0,
+                  batch=0, x=FAKE["x"], w=FAKE["w"]):
+    """The arguments of ``_linear_ref.route`` handed to the library the way ops.py hands them over; ``ptrs`` = (y, bias, residual
+    or pre, colsum) are real addresses here, 0 = absent.  (status, raw route, rows handed to the library)."""
+    from anemoi_models_amd import _lib, ops
+
+    code = {F32: _lib.F32, BF16: _lib.BF16}
+    y, b, r, cs = ptrs
+    a = dict(dtype=code[dtype], out_dtype=code[out_dtype], x=x, w=w, y=y, bias=b, ldx=ldx, ldy=ldy, M=M, N=N, K=K,
+             act=_lib.ACT_CODES[act])
+    if batch > 0:  # ops.linear_heads: problem h at x + h K, w + h N K, y + h N
+        return _lib.linear_route("batched", **{**a, "batch": batch, "stride_x": K, "stride_w": N * K, "stride_y": N}) + (M,)
+    if epi != 0:  # ops.linear_dual allocates pre (pitch N); ops.linear_actgrad is given it
+        rows = ops._fused_epilogue_rows(dtype, M, N, K, ldx, 0 if epi == 1 else ldr)
+        if rows == 0:
+            return None, None, 0
+        a.update(M=rows, out_dtype=code[dtype], residual=r or FAKE["residual"], ldr=N if epi == 1 else ldr)
+        if epi == 2:
+            a["bias"] = 0
+        return _lib.linear_route("dual" if epi == 1 else "actgrad", **a) + (rows,)
+    if res:
+        a.update(residual=r, ldr=ldr)
+    if fold:
+        a.update(colsum=cs, stats=FAKE["stats"])
+    if stats and act == "Identity" and out_dtype == dtype:  # ops.linear(stats_eps=): the workspace it allocates
+        a.update(workspace=FAKE["workspace"], workspace_bytes=M * max(N // 128, 1) * 8, stats_out=FAKE["stats_out"])
+        return _lib.linear_route("stats", **a) + (M,)
+    return _lib.linear_route("ln" if fold else "linear", **a) + (M,)
+
+
+def library_route_restated(st, r, M, N, batch, rows):
+    """The library's route in the terms of ``_linear_ref.route`` (``rows`` of ``M`` were handed over; the rest is ops.py's)."""
+    from anemoi_models_amd import _lib
+
+    py = types.SimpleNamespace(kernel="py", tail="none", batched=False, vec_ok=False, main_rows=0, m_a=0, rs=False)
+    if rows == 0 or st == _lib.ANEMOI_ERR_UNSUPPORTED:
+        return py
+    assert st == _lib.ANEMOI_OK, (st, _lib.load().anemoi_last_error())
+    tail = {_lib.LINEAR_REST_NONE: "none", _lib.LINEAR_REST_SKINNY: "skinny", _lib.LINEAR_REST_128: "k128",
+            _lib.LINEAR_REST_IN_LAUNCH: "in%d" % (1 if r.rest_rows == 1 else 2 if r.rest_rows == 2 else 4 if r.rest_rows <= 4 else 8)}[r.rest]
+    if rows < M:
+        assert tail == "none"
+        tail = "py"
+    assert r.main_rows + (r.rest_rows if r.rest else 0) == rows and (r.rest == 0 or r.rest_row0 == r.main_rows)
+    if r.kernel == _lib.LINEAR_KERNEL_128:
+        assert r.n_launches == 0 and r.rs_rows == 0
+        return types.SimpleNamespace(kernel="k128", vec_ok=bool(r.vec_ok), tail=tail, batched=batch > 0, main_rows=0, m_a=0, rs=False)
+    assert r.kernel == _lib.LINEAR_KERNEL_PERSISTENT and r.n_launches in (1, 2) and r.vec_ok == 1 and r.rs_rows in (0, r.main_rows)
+    first, last, second = r.launch[0], r.launch[r.n_launches - 1], bool(r.split)
+    assert (r.n_launches == 1 or second) and sum(r.launch[i].rows for i in range(r.n_launches)) == r.main_rows
+    groups = max(r.nt // R.SUPER_N, 1)
+    return types.SimpleNamespace(
+        kernel="w4", mh=first.mh, second=second, tail=tail, ragged_m=last.rows % (128 if second else 32 * last.mh) != 0,
+        ragged_n=N % R.BIG != 0, nt=r.nt, rem=r.nt - (groups - 1) * R.SUPER_N, vec_ok=True, stagger=first.stagger_phases > 1,
+        model=bool(r.model), rs=r.rs_rows > 0, batched=batch > 0, main_rows=r.main_rows,
+        m_a=r.main_rows if not second else (first.rows if r.n_launches == 2 else 0))
+
+
+def restated_launches(rt, batch):
+    """(mh, first row, rows, tiles) per launch of a restated persistent route."""
+    mt = -(-rt.main_rows // R.BIG)
+    if not rt.second:
+        return [(rt.mh, 0, rt.main_rows, max(batch, 1) * -(-rt.main_rows // (32 * rt.mh)) * rt.nt)]
+    mt_a = rt.m_a // R.BIG
+    return ([(8, 0, rt.m_a, mt_a * rt.nt)] if mt_a else []) + [(4, rt.m_a, rt.main_rows - rt.m_a, (mt - mt_a) * 2 * rt.nt)]
+
+
+def assert_same_route(rt, st, r, M, N, batch, rows, what):
+    """The restated route ``rt`` equals the library's (status ``st``, raw route ``r``): every field ``route_str`` prints, ``m_a``,
+    ``main_rows``, the row sums, and per launch of the persistent kernel its height, rows, tiles, workgroups and stagger; the
+    rows of the in-launch pass ride on the last launch."""
+    lib = library_route_restated(st, r, M, N, batch, rows)
+    assert R.route_str(lib) == R.route_str(rt), f"{what}: the library takes {R.route_str(lib)}, the restatement {R.route_str(rt)}"
+    assert (lib.main_rows, lib.m_a, lib.rs) == (rt.main_rows, rt.m_a, rt.rs), what
+    if rt.kernel != "w4":
+        return
+    want = restated_launches(rt, batch)
+    assert r.n_launches == len(want), what
+    for i, (mh, row0, nrows, tiles) in enumerate(want):
+        l = r.launch[i]
+        assert (l.mh, l.row0, l.rows, l.tiles, l.blocks) == (mh, row0, nrows, tiles, min(256, -(-tiles // 8) * 8)), (what, i)
+        assert l.tail_rows == (r.rest_rows if i == len(want) - 1 and lib.tail.startswith("in") else 0), (what, i)
+        assert (l.stagger_phases > 1) == (rt.stagger and i == 0), (what, i)
+
+
+def _case_ptrs(c):
+    return (FAKE["y"], FAKE["bias"] if c.bias and c.kind != "actgrad" else 0,
+            FAKE["residual"] if c.res or c.kind == "actgrad" else 0, FAKE["colsum"] if c.fold else 0)
+
+
+def case_library_route(c, ptrs, **xw):
+    """``library_route`` on the arguments ``_linear_ref.case_route`` restates."""
+    ldx, ldy, ldr = (c.k * c.h if c.h else c.k) + c.pads[0], (c.n * c.h if c.h else c.n) + c.pads[1], c.n + c.pads[2]
+    epi = {"linear": 0, "dual": 1, "actgrad": 2, "heads": 0}[c.kind]
+    return library_route(c.dtype, c.out, c.m, c.n, c.k, ldx, ldy, ldr, ptrs, c.act, c.res or epi == 2, c.fold, c.stats, epi, c.h, **xw)
+
+
+def test_the_library_routes_every_case_as_restated():
+    for c in R.all_cases():
+        ptrs = _case_ptrs(c)
+        rt = R.case_route(c, ptrs)
+        assert R.route_str(rt) == c.expect, R.case_id(c)
+        st, r, rows = case_library_route(c, ptrs)
+        assert_same_route(rt, st, r, c.m, c.n, c.h, rows, R.case_id(c))
+        if c.kind in ("dual", "actgrad"):  # the rows ops.py hands over: all, the whole tiles, or none (restated as py)
+            assert rows == (0 if rt.kernel == "py" else rt.main_rows if rt.tail == "py" else c.m), R.case_id(c)
+
+
+SWEEP_M = (1024, 1025, 1032, 1033, 2569, 5121, 10242, 20481, 40960, 40962, 65545)
+SWEEP_N = (256, 264, 512, 1024, 2048, 2240, 4096, 4288, 4352, 6144)
+SWEEP_K = (64, 128, 256, 512, 1216, 2048, 4096)
+
+
+def test_the_library_routes_a_sweep_as_restated():
+    """bf16 -> bf16 over SWEEP_M x SWEEP_N x SWEEP_K x activation x residual x fold x row sums x {pitches as tight as they go,
+    padded by 8} x {y, bias, residual, colsum each 16-byte aligned or off by 8 bytes, where the operand exists}: 443 520 sets
+    of integer arguments."""
+    n = 0
+    for M in SWEEP_M:
+        for N in SWEEP_N:
+            for K in SWEEP_K:
+                for act in R.ACTS:
+                    for res in (False, True):
+                        for fold in (False, True):
+                            offs = [(oy, ob, orr, oc) for oy in (0, 8) for ob in (0, 8) for orr in (0, 8)[:1 + res]
+                                    for oc in (0, 8)[:1 + fold]]
+                            for stats in (False, True):
+                                for pad in (0, 8):
+                                    for off in offs:
+                                        ptrs = (FAKE["y"] + off[0], FAKE["bias"] + off[1], (FAKE["residual"] + off[2]) * res,
+                                                (FAKE["colsum"] + off[3]) * fold)
+                                        args = (BF16, BF16, M, N, K, K + pad, N + pad, N + pad, ptrs, act, res, fold, stats)
+                                        st, r, rows = library_route(*args)
+                                        assert_same_route(R.route(*args), st, r, M, N, 0, rows, args)
+                                        n += 1
+    assert n == 11 * 10 * 7 * 4 * (4 + 8 + 8 + 16) * 2 * 2 == 443520
+
+
+@pytest.mark.parametrize("switch,value,shape,default,forced", [
+    ("ANEMOI_AMD_GEMM_MH", "5", (1056, 256, 128), "1 3 0", "1 5 0"),  # a small-problem shape: one launch of 96-row tiles
+    ("ANEMOI_AMD_GEMM_STAGGER", "0,0,2", (8192, 4096, 512), "1 8 2", "1 8 0"),  # 512 tiles, K = 512: staggered as shipped
+])
+def test_lab_switches_reach_the_plan(switch, value, shape, default, forced):
+    """The switches are read once per process: a fresh child each; without the switch, this process (unless it runs under one)."""
+    import os
+    import subprocess
+    import sys
+
+    from conftest import ROOT
+
+    code = ("from anemoi_models_amd import _lib\n"
+            "st, r = _lib.linear_route('linear', dtype=1, out_dtype=1, x=4096, w=8192, y=12288, ldx=%d, ldy=%d, M=%d, N=%d, K=%d)\n"
+            "print(st, r.n_launches, r.launch[0].mh, r.launch[0].stagger_phases)\n" % (shape[2], shape[1], *shape))
+    env = {k: v for k, v in os.environ.items() if not k.startswith("ANEMOI_AMD_GEMM_")}
+    out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=dict(env, **{switch: value}), capture_output=True, text=True,
+                         timeout=120)
+    assert out.returncode == 0, out.stderr
+    assert out.stdout.split() == ["0"] + forced.split(), out.stdout
+    if len(env) == len(os.environ):
+        st, r, _ = library_route(BF16, BF16, *shape, shape[2], shape[1], 0, (FAKE["y"], 0, 0, 0))
+        assert [str(v) for v in (st, r.n_launches, r.launch[0].mh, r.launch[0].stagger_phases)] == ["0"] + default.split()
 
 
 # ------------------------------------------------------------------------------------------------ emulations inside the bounds
