@@ -49,7 +49,7 @@ def cond_ln_padded_k(k: int) -> int:
     return 4 if k <= 4 else (8 if k <= 8 else (16 if k <= 16 else 32))
 
 
-ABI_VERSION = 53
+ABI_VERSION = 54
 
 LINEAR_ENTRIES = {"linear": 0, "ln": 1, "stats": 2, "dual": 3, "actgrad": 4, "batched": 5}  # ANEMOI_LINEAR_ENTRY_*
 LINEAR_KERNEL_NONE, LINEAR_KERNEL_128, LINEAR_KERNEL_PERSISTENT = 0, 1, 2
@@ -151,6 +151,35 @@ class TfmBlockArgs(ctypes.Structure):
         ("w_fc1", c_void_p), ("b_fc1", c_void_p), ("w_fc2", c_void_p), ("b_fc2", c_void_p),
         ("h_ln", c_void_p), ("qkv", c_void_p), ("att", c_void_p), ("y", c_void_p), ("h", c_void_p),
         ("mhsa_ws", c_void_p), ("out", c_void_p),
+    ]
+
+
+OPT_MAX_TENSORS = 88  # tensors per launch of the multi-tensor optimizer kernels (anemoi_multi_tensor_max_tensors())
+OPT_CHUNK = 4096      # elements per workgroup (anemoi_multi_tensor_chunk())
+OPT_CONSTS = 8        # floats per block of anemoi_adamw_constants
+OPT_SUMSQ_DEPTH = OPT_CHUNK // 256 + 6 + 3  # longest chain of f32 additions in anemoi_multi_sumsq (csrc/optim.hip)
+
+
+class MultiTensorArgs(ctypes.Structure):
+    """``anemoi_multi_tensor_args`` of include/anemoi_amd.h, field for field."""
+
+    _fields_ = [
+        ("struct_bytes", c_int64), ("n_tensors", c_int64),
+        ("numel", c_void_p), ("params", c_void_p), ("grads", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
+        ("workspace", c_void_p), ("workspace_floats", c_int64), ("sumsq", c_void_p), ("consts", c_void_p), ("coef", c_void_p),
+        ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+    ]
+
+
+class AdamwConstantsArgs(ctypes.Structure):
+    """``anemoi_adamw_constants_args`` of include/anemoi_amd.h, field for field."""
+
+    _fields_ = [
+        ("struct_bytes", c_int64), ("n_groups", c_int64),
+        ("step", c_void_p), ("lr_dev", c_void_p), ("lr", c_void_p), ("beta1", c_void_p), ("beta2", c_void_p),
+        ("weight_decay", c_void_p), ("sumsq", c_void_p), ("skipped", c_void_p), ("consts", c_void_p),
+        ("max_norm", c_float), ("has_max_norm", ctypes.c_int32), ("skip_nonfinite", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
     ]
 
 
@@ -320,6 +349,13 @@ SIGNATURES = {
                                     c_int64, c_int, c_int, c_int, c_void_p]),
     "anemoi_weight_grad_split": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,
                                          c_int, c_void_p]),
+    "anemoi_multi_tensor_max_tensors": (c_int, []),
+    "anemoi_multi_tensor_chunk": (c_int, []),
+    "anemoi_multi_sumsq_workspace_floats": (c_int64, [c_void_p, c_int64]),
+    "anemoi_multi_sumsq": (c_int, [ctypes.POINTER(MultiTensorArgs), c_void_p]),
+    "anemoi_adamw_constants": (c_int, [ctypes.POINTER(AdamwConstantsArgs), c_void_p]),
+    "anemoi_multi_adamw": (c_int, [ctypes.POINTER(MultiTensorArgs), c_void_p]),
+    "anemoi_multi_scale": (c_int, [ctypes.POINTER(MultiTensorArgs), c_void_p]),
     "anemoi_trail_begin": (c_int, [c_void_p, c_int64]),
     "anemoi_trail_end": (c_int, [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
     "anemoi_trail_entry": (c_int, [c_int64, ctypes.POINTER(c_char_p), ctypes.POINTER(c_int), ctypes.POINTER(c_int64),

@@ -1698,3 +1698,143 @@ def weight_grad_split(dpre: Tensor, x: Tensor, k: int, want_bias: bool = False, 
             col_sum(dpre, out=total[n * k:])
     dw = total[: n * k].view(n, k)
     return (dw, total[n * k:]) if want_bias else dw
+
+
+# ---------------------------------------------------------------- the optimizer step (csrc/optim.hip, DESIGN.md section 7 "8f-10")
+def multi_tensor_chunks(numels) -> int:
+    """(tensor, chunk) pairs of a list of lengths: the workspace floats of :func:`multi_sumsq` (empty tensors have none)."""
+    return sum((int(n) + _lib.OPT_CHUNK - 1) // _lib.OPT_CHUNK for n in numels)
+
+
+def ptr_array(tensors):
+    """The host array of device pointers the multi-tensor entry points take (a ``ctypes`` array; it may be kept and reused
+    for as long as the tensors stay where they are)."""
+    import ctypes
+
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def numel_array(tensors):
+    import ctypes
+
+    return (ctypes.c_int64 * len(tensors))(*[t.numel() for t in tensors])
+
+
+def _check_list(who: str, what: str, tensors, like=None) -> None:
+    for i, t in enumerate(tensors):
+        if not t.is_cuda:
+            _dev(t)
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise NotImplementedError(f"{who}: {what}[{i}] must be a contiguous float32 tensor, got {t.dtype} "
+                                      f"strides {t.stride()}")
+        if like is not None and t.numel() != like[i].numel():
+            raise ValueError(f"{who}: {what}[{i}] has {t.numel()} elements, the parameter {like[i].numel()}")
+
+
+def _multi_args(n: int, numel, **fields):
+    import ctypes
+
+    a = _lib.MultiTensorArgs()
+    a.struct_bytes, a.n_tensors = ctypes.sizeof(_lib.MultiTensorArgs), n
+    a.numel = ctypes.cast(numel, ctypes.c_void_p)
+    a._keep = [numel, *fields.values()]  # the host arrays live as long as the block
+    for name, value in fields.items():
+        setattr(a, name, ctypes.cast(value, ctypes.c_void_p) if isinstance(value, ctypes.Array) else value)
+    return a
+
+
+def multi_sumsq(grads, out: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
+    """``sum over the list of g^2`` as an f32 device scalar: deterministic two-stage reduction without atomics, a function of
+    the values and the ordered list of lengths alone (``anemoi_multi_sumsq``).  ``grads``: contiguous f32 tensors of any
+    length and 4-byte alignment.  ``out`` (f32 ``[]`` or ``[1]``) and ``workspace`` (f32, at least
+    :func:`multi_tensor_chunks` floats) are allocated when not given."""
+    import ctypes
+
+    grads = list(grads)
+    _check_list("multi_sumsq", "grads", grads)
+    if out is None:
+        if not grads:
+            raise ValueError("multi_sumsq: an empty list needs `out` (there is no device to allocate on)")
+        out = torch.empty((), dtype=torch.float32, device=grads[0].device)
+    n_ws = multi_tensor_chunks(t.numel() for t in grads)
+    if workspace is None or workspace.numel() < n_ws:
+        workspace = torch.empty(max(n_ws, 1), dtype=torch.float32, device=out.device)
+    a = _multi_args(len(grads), numel_array(grads), grads=ptr_array(grads), workspace=workspace.data_ptr(),
+                    workspace_floats=workspace.numel(), sumsq=out.data_ptr())
+    with _Timed("multi_sumsq", bytes=4 * sum(t.numel() for t in grads)):
+        st = _lib.load().anemoi_multi_sumsq(ctypes.byref(a), _stream())
+    _lib.check(st, "anemoi_multi_sumsq")
+    return out
+
+
+def adamw_constants(consts: Tensor, steps=(), lrs=(), betas=(), weight_decays=(), *, sumsq: Optional[Tensor] = None,
+                    max_norm: Optional[float] = None, skip_nonfinite: bool = False,
+                    skipped: Optional[Tensor] = None) -> Tensor:
+    """The scalars of one AdamW step (``anemoi_adamw_constants``), written to ``consts`` (f32 ``[1 + n_groups, 8]``: block 0 =
+    norm, clip, finite, skip; block 1 + g = clip, 1 - lr wd, lr / bc1, sqrt(bc2), skip, lr, t) by one tiny kernel.  ``steps``:
+    one f32 device counter per group, advanced in place; ``lrs``: floats or 0-dim f32 device tensors (read on the device);
+    ``betas``: ``(beta1, beta2)`` per group.  No group: block 0 alone."""
+    import ctypes
+
+    n = len(steps)
+    if not (len(lrs) == len(betas) == len(weight_decays) == n):
+        raise ValueError("adamw_constants: steps, lrs, betas and weight_decays must have one entry per group")
+    _dev(consts, sumsq, skipped, *steps)
+    if consts.dtype != torch.float32 or not consts.is_contiguous() or consts.numel() < (1 + n) * _lib.OPT_CONSTS:
+        raise ValueError(f"adamw_constants: consts must be contiguous float32 with {(1 + n) * _lib.OPT_CONSTS} elements")
+    for i, lr in enumerate(lrs):
+        if isinstance(lr, Tensor) and (not lr.is_cuda or lr.dtype != torch.float32 or lr.numel() != 1):
+            raise ValueError(f"adamw_constants: lrs[{i}] must be a float or a one-element float32 device tensor")
+    fa = ctypes.c_double * max(n, 1)
+    c = _lib.AdamwConstantsArgs()
+    c.struct_bytes, c.n_groups = ctypes.sizeof(_lib.AdamwConstantsArgs), n
+    step_a, lr_dev_a = ptr_array(steps), (ctypes.c_void_p * max(n, 1))(*[lr.data_ptr() if isinstance(lr, Tensor) else None
+                                                                        for lr in lrs])
+    lr_a = fa(*[0.0 if isinstance(lr, Tensor) else float(lr) for lr in lrs])
+    b1_a, b2_a = fa(*[float(b[0]) for b in betas]), fa(*[float(b[1]) for b in betas])
+    wd_a = fa(*[float(w) for w in weight_decays])
+    for name, arr in (("step", step_a), ("lr_dev", lr_dev_a), ("lr", lr_a), ("beta1", b1_a), ("beta2", b2_a),
+                      ("weight_decay", wd_a)):
+        setattr(c, name, ctypes.cast(arr, ctypes.c_void_p))
+    c.sumsq, c.skipped, c.consts = _ptr(sumsq), _ptr(skipped), consts.data_ptr()
+    c.max_norm, c.has_max_norm, c.skip_nonfinite = float(max_norm or 0.0), int(max_norm is not None), int(skip_nonfinite)
+    st = _lib.load().anemoi_adamw_constants(ctypes.byref(c), _stream())
+    _lib.check(st, "anemoi_adamw_constants")
+    return consts
+
+
+def multi_adamw(params, grads, exp_avg, exp_avg_sq, consts_block: Tensor, beta1: float, beta2: float, eps: float) -> None:
+    """One AdamW update of the list in one pass (``anemoi_multi_adamw``): ``g' = clip g`` on load (``grads`` are not
+    modified), ``m``, ``v`` and ``p`` updated in place with torch.optim.AdamW's arithmetic in correctly rounded f32.
+    ``consts_block``: the group's 8 floats of :func:`adamw_constants`."""
+    import ctypes
+
+    params, grads, exp_avg, exp_avg_sq = list(params), list(grads), list(exp_avg), list(exp_avg_sq)
+    if not (len(params) == len(grads) == len(exp_avg) == len(exp_avg_sq)):
+        raise ValueError("multi_adamw: the four lists must have one tensor per parameter")
+    _check_list("multi_adamw", "params", params)
+    _check_list("multi_adamw", "grads", grads, params)
+    _check_list("multi_adamw", "exp_avg", exp_avg, params)
+    _check_list("multi_adamw", "exp_avg_sq", exp_avg_sq, params)
+    _dev(consts_block)
+    a = _multi_args(len(params), numel_array(params), params=ptr_array(params), grads=ptr_array(grads),
+                    exp_avg=ptr_array(exp_avg), exp_avg_sq=ptr_array(exp_avg_sq),
+                    consts=consts_block.data_ptr(), beta1=float(beta1), beta2=float(beta2), eps=float(eps))
+    with _Timed("multi_adamw", bytes=28 * sum(t.numel() for t in params)):
+        st = _lib.load().anemoi_multi_adamw(ctypes.byref(a), _stream())
+    _lib.check(st, "anemoi_multi_adamw")
+
+
+def multi_scale(grads, coef: Tensor) -> None:
+    """``g <- coef * g`` in place over the list, ``coef`` a one-element f32 device tensor (``anemoi_multi_scale``)."""
+    import ctypes
+
+    grads = list(grads)
+    _check_list("multi_scale", "grads", grads)
+    _dev(coef)
+    if coef.dtype != torch.float32 or coef.numel() != 1:
+        raise ValueError("multi_scale: coef must be a one-element float32 device tensor")
+    a = _multi_args(len(grads), numel_array(grads), grads=ptr_array(grads), coef=coef.data_ptr())
+    with _Timed("multi_scale", bytes=8 * sum(t.numel() for t in grads)):
+        st = _lib.load().anemoi_multi_scale(ctypes.byref(a), _stream())
+    _lib.check(st, "anemoi_multi_scale")

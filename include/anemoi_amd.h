@@ -1037,6 +1037,86 @@ int anemoi_weight_grad_split(const float* dy, int64_t ldy, const float* x, int64
                              int64_t partial_stride, int64_t M, int N, int K, int chunk_rows, anemoi_stream_t stream);
 
 /*
+ * The optimizer step (ABI v54, csrc/optim.hip, DESIGN.md section 7 "8f-10"): multi-tensor kernels over LISTS of f32 tensors.
+ * The list is given as HOST arrays of n_tensors device pointers and lengths; the entry point copies them into the argument
+ * blocks of its launches (at most anemoi_multi_tensor_max_tensors() tensors per launch, chunks of anemoi_multi_tensor_chunk()
+ * elements per workgroup), so the arrays may be freed on return and nothing of them lives in device memory.  A tensor of
+ * numel 0 is skipped (its pointers may be NULL); any other pointer need only be 4-byte aligned.  Fields an entry point does not
+ * read stay 0 / NULL.  `struct_bytes` must be sizeof of the block (layout check across the FFI).
+ * Checked before any launch, else ANEMOI_ERR_INVALID with a message naming the argument: a null block or pointer, a negative
+ * count or length, a workspace that is too small, beta1 / beta2 outside [0, 1), eps < 0, lr < 0, weight_decay < 0.
+ */
+typedef struct anemoi_multi_tensor_args {
+  int64_t struct_bytes;
+  int64_t n_tensors;
+  const int64_t* numel;     /* host [n_tensors] */
+  void* const* params;      /* host [n_tensors] of device f32 pointers: anemoi_multi_adamw (read and written) */
+  void* const* grads;       /* sumsq, adamw: read only; scale: scaled in place */
+  void* const* exp_avg;     /* adamw (read and written) */
+  void* const* exp_avg_sq;  /* adamw (read and written) */
+  float* workspace;         /* sumsq: device, anemoi_multi_sumsq_workspace_floats(numel, n_tensors) floats */
+  int64_t workspace_floats;
+  float* sumsq;             /* sumsq: device f32 [1], the result */
+  const float* consts;      /* adamw: device, the group's constants block (anemoi_adamw_constants) */
+  const float* coef;        /* scale: device f32 [1] */
+  double beta1, beta2, eps; /* adamw: as torch takes them; the kernel sees f32(1 - beta1), f32(beta2), f32(1 - beta2), f32(eps) */
+} anemoi_multi_tensor_args;
+
+int anemoi_multi_tensor_max_tensors(void);
+int anemoi_multi_tensor_chunk(void);
+
+/* sumsq[0] = sum over the list of g^2, two deterministic stages without atomics: one f32 partial per (tensor, chunk) in list
+ * order to `workspace`, then one workgroup that adds the partials in f64 and writes the f32-rounded total.  The result is a
+ * function of the values and of the ordered list of lengths alone (csrc/optim.hip states every sum order).  An empty list
+ * gives 0.  Trail: "sumsq". */
+int64_t anemoi_multi_sumsq_workspace_floats(const int64_t* numel, int64_t n_tensors);
+int anemoi_multi_sumsq(const anemoi_multi_tensor_args* args, anemoi_stream_t stream);
+
+/*
+ * The scalars of one AdamW step, by one tiny kernel; nothing is read back.  consts is device f32 [(1 + n_groups) * 8]:
+ *   block 0       norm = sqrt(sumsq), clip = min(1, max_norm / (norm + 1e-6)) (1 without max_norm), finite, skip, 0 ...
+ *   block 1 + g   clip, 1 - lr wd, lr / (1 - beta1^t), sqrt(1 - beta2^t), skip, lr, t, 0         t = step[g] + 1
+ * (bias corrections and the decay factor evaluated in f64, rounded once).  step: host [n_groups] of device f32 [1] counters,
+ * advanced here; lr_dev: NULL, or host [n_groups] of device f32 [1] learning rates, an entry may be NULL: lr[g] by value.
+ * sumsq NULL: no norm was taken (clip = 1, finite).  skip_nonfinite with a non-finite norm: no counter is advanced, the device
+ * int64 `skipped` (may be NULL) is advanced by one and every block carries skip = 1, which turns anemoi_multi_adamw into a
+ * no-op.  n_groups = 0 writes block 0 alone (the stand-alone clip reads its coefficient there).  Trail: "consts".
+ */
+typedef struct anemoi_adamw_constants_args {
+  int64_t struct_bytes;
+  int64_t n_groups;
+  void* const* step;
+  void* const* lr_dev;
+  const double* lr;           /* host [n_groups] each */
+  const double* beta1;
+  const double* beta2;
+  const double* weight_decay;
+  const float* sumsq;         /* device, or NULL */
+  void* skipped;              /* device int64 [1], or NULL */
+  float* consts;              /* device f32 [(1 + n_groups) * 8] */
+  float max_norm;
+  int32_t has_max_norm;
+  int32_t skip_nonfinite;
+  int32_t reserved;
+} anemoi_adamw_constants_args;
+
+int anemoi_adamw_constants(const anemoi_adamw_constants_args* args, anemoi_stream_t stream);
+
+/*
+ * One pass over params, grads, exp_avg, exp_avg_sq (16 bytes read, 12 written per element), torch.optim.AdamW's arithmetic
+ * with the clip applied on load -- grads are NOT modified:
+ *   g' = clip g;  m <- m + (g' - m)(1 - beta1);  v <- beta2 v + (1 - beta2) g'^2
+ *   p  <- p (1 - lr wd) - (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
+ * in correctly rounded f32 operations (no fast sqrt or division).  `consts` points at the group's block (block 1 + g).  Under
+ * its skip flag nothing is read or written.  Trail (only while one is armed): "params[i]", "exp_avg[i]", "exp_avg_sq[i]" per
+ * non-empty tensor i of the list, each as [1, numel].
+ */
+int anemoi_multi_adamw(const anemoi_multi_tensor_args* args, anemoi_stream_t stream);
+
+/* grads[i] <- coef[0] * grads[i] in place, coef on the device.  Trail: "grads[i]" per non-empty tensor. */
+int anemoi_multi_scale(const anemoi_multi_tensor_args* args, anemoi_stream_t stream);
+
+/*
  * Launch trail -- opt-in per-launch output digests (csrc/trail.hip).
  *
  * While a trail is armed on the calling thread, every entry point of this header that writes device memory appends one
