@@ -49,7 +49,7 @@ def cond_ln_padded_k(k: int) -> int:
     return 4 if k <= 4 else (8 if k <= 8 else (16 if k <= 16 else 32))
 
 
-ABI_VERSION = 54
+ABI_VERSION = 55
 
 LINEAR_ENTRIES = {"linear": 0, "ln": 1, "stats": 2, "dual": 3, "actgrad": 4, "batched": 5}  # ANEMOI_LINEAR_ENTRY_*
 LINEAR_KERNEL_NONE, LINEAR_KERNEL_128, LINEAR_KERNEL_PERSISTENT = 0, 1, 2
@@ -157,6 +157,7 @@ class TfmBlockArgs(ctypes.Structure):
 OPT_MAX_TENSORS = 88  # tensors per launch of the multi-tensor optimizer kernels (anemoi_multi_tensor_max_tensors())
 OPT_CHUNK = 4096      # elements per workgroup (anemoi_multi_tensor_chunk())
 OPT_CONSTS = 8        # floats per block of anemoi_adamw_constants
+OPT_SKIP_ALL = 3      # index of the list-wide skip flag in block 0 (norm, clip, finite, skip)
 OPT_SUMSQ_DEPTH = OPT_CHUNK // 256 + 6 + 3  # longest chain of f32 additions in anemoi_multi_sumsq (csrc/optim.hip)
 
 
@@ -180,6 +181,46 @@ class AdamwConstantsArgs(ctypes.Structure):
         ("weight_decay", c_void_p), ("sumsq", c_void_p), ("skipped", c_void_p), ("consts", c_void_p),
         ("max_norm", c_float), ("has_max_norm", ctypes.c_int32), ("skip_nonfinite", ctypes.c_int32),
         ("reserved", ctypes.c_int32),
+    ]
+
+
+AVERAGE_EMA, AVERAGE_SWA = 0, 1  # ANEMOI_AVERAGE_EMA / ANEMOI_AVERAGE_SWA
+AVG_CONSTS = 4                    # floats of the block of anemoi_average_constants: w, active, copy, n_after
+LR_MAX_GROUPS = 32                # parameter groups per call of anemoi_lr_schedule
+
+
+class AverageConstantsArgs(ctypes.Structure):
+    """``anemoi_average_constants_args`` of include/anemoi_amd.h, field for field."""
+
+    _fields_ = [
+        ("struct_bytes", c_int64), ("n_averaged", c_void_p), ("step", c_void_p), ("skip", c_void_p), ("avg", c_void_p),
+        ("decay", ctypes.c_double), ("start_step", c_int64), ("every", c_int64),
+        ("kind", ctypes.c_int32), ("use_warmup", ctypes.c_int32),
+    ]
+
+
+class MultiAverageArgs(ctypes.Structure):
+    """``anemoi_multi_average_args`` of include/anemoi_amd.h, field for field."""
+
+    _fields_ = [
+        ("struct_bytes", c_int64), ("n_tensors", c_int64), ("numel", c_void_p), ("params", c_void_p), ("shadow", c_void_p),
+        ("avg", c_void_p),
+    ]
+
+
+class MultiSwapArgs(ctypes.Structure):
+    """``anemoi_multi_swap_args`` of include/anemoi_amd.h, field for field."""
+
+    _fields_ = [("struct_bytes", c_int64), ("n_tensors", c_int64), ("numel", c_void_p), ("a", c_void_p), ("b", c_void_p)]
+
+
+class LrScheduleArgs(ctypes.Structure):
+    """``anemoi_lr_schedule_args`` of include/anemoi_amd.h, field for field."""
+
+    _fields_ = [
+        ("struct_bytes", c_int64), ("n_groups", c_int64), ("step", c_void_p), ("lr", c_void_p), ("base", c_void_p),
+        ("lr_min", c_void_p), ("warmup_start", c_void_p), ("warmup_steps", c_void_p), ("total_steps", c_void_p),
+        ("warmup_prefix", c_void_p),
     ]
 
 
@@ -356,6 +397,10 @@ SIGNATURES = {
     "anemoi_adamw_constants": (c_int, [ctypes.POINTER(AdamwConstantsArgs), c_void_p]),
     "anemoi_multi_adamw": (c_int, [ctypes.POINTER(MultiTensorArgs), c_void_p]),
     "anemoi_multi_scale": (c_int, [ctypes.POINTER(MultiTensorArgs), c_void_p]),
+    "anemoi_average_constants": (c_int, [ctypes.POINTER(AverageConstantsArgs), c_void_p]),
+    "anemoi_multi_average": (c_int, [ctypes.POINTER(MultiAverageArgs), c_void_p]),
+    "anemoi_multi_swap": (c_int, [ctypes.POINTER(MultiSwapArgs), c_void_p]),
+    "anemoi_lr_schedule": (c_int, [ctypes.POINTER(LrScheduleArgs), c_void_p]),
     "anemoi_trail_begin": (c_int, [c_void_p, c_int64]),
     "anemoi_trail_end": (c_int, [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
     "anemoi_trail_entry": (c_int, [c_int64, ctypes.POINTER(c_char_p), ctypes.POINTER(c_int), ctypes.POINTER(c_int64),

@@ -884,7 +884,7 @@ int anemoi_bound_output(float* y, int V_out, int64_t rows, int n_ops, const int3
                      as_stream(stream));
 }
 
-int anemoi_abi_version(void) { return 54; }
+int anemoi_abi_version(void) { return 55; }
 
 #ifndef ANEMOI_HIPCC_VERSION
 #define ANEMOI_HIPCC_VERSION "unknown (built without anemoi_models_amd/_build.py)"

@@ -2,14 +2,8 @@
 // step count on one multi-tensor frame.  All operands f32; parameters, gradients and both moments are separate allocations of
 // any length.
 //
-// The frame.  One launch serves up to OPT_MAX_TENSORS tensors whose device pointers, lengths and chunk prefix counts travel BY
-// VALUE in the kernel argument block (HIP's 4 KB limit fixes OPT_MAX_TENSORS): there is no table in device memory, so nothing
-// on the host has to stay alive for a graph replay and a gradient that moved between two captures costs nothing.  A tensor is
-// cut into chunks of OPT_CHUNK elements; workgroup b owns the (tensor, chunk) pair found by a binary search of b in the
-// prefix counts -- scalar loads from the argument block, wave-uniform.  A longer list is several launches.  Within a chunk,
-// pass u of thread t owns the four elements (u * 256 + t) * 4 .. + 3: one 16-byte access when every pointer of the tensor is
-// 16-byte aligned, else (a view at an odd element offset) up to four dword accesses of the SAME elements -- the arithmetic and
-// its order do not know which.  The ragged tail of a tensor is the last, short group.
+// The frame (csrc/multi_tensor.hpp, shared with csrc/average.hip): up to OPT_MAX_TENSORS tensors per launch, pointers by value in
+// the argument block, chunks of OPT_CHUNK elements, pass u of thread t owning the four elements (u * 256 + t) * 4 .. + 3.
 //
 // anemoi_multi_sumsq, the determinism rule: the result is a function of the gradient VALUES and the ordered list of lengths
 // alone -- not of addresses, alignment or what else ran.  Stage 1: a thread adds the squares of its elements in ascending index
@@ -29,27 +23,16 @@
 //   v  <- fmaf((1 - beta2) * g', g', beta2 * v)                   [5: g' enters twice]
 //   p  <- fmaf(-(lr / bc1), m / (sqrtf(v) / sqrt(bc2) + eps), p * (1 - lr * wd))      [6, from the stored m and v]
 // .grad is only read.  Under the skip flag the kernel returns before its first load.
-#include "common.hpp"
-#include "trail.hpp"
+#include "multi_tensor.hpp"
 
 #pragma clang fp contract(off)
 
 namespace anemoi {
 
-constexpr int OPT_MAX_TENSORS = 88;
-constexpr int OPT_CHUNK = 4096;
-constexpr int OPT_PASSES = OPT_CHUNK / (256 * 4);
 constexpr int OPT_CONSTS = 8;       // floats per constants block
-constexpr int OPT_MAX_GROUPS = 32;  // parameter groups per launch of the constants kernel
 // constants block 0 (the list): norm, clip, finite, skip.  Block 1 + g (group g): clip, decay, step_size, sqrt(bc2), skip, lr, t.
 constexpr int OPTC_NORM = 0, OPTC_CLIP_ALL = 1, OPTC_FINITE = 2, OPTC_SKIP_ALL = 3;
 constexpr int OPTC_CLIP = 0, OPTC_DECAY = 1, OPTC_STEP_SIZE = 2, OPTC_BC2_SQRT = 3, OPTC_SKIP = 4, OPTC_LR = 5, OPTC_T = 6;
-
-struct OptFrame {
-  int32_t n;                                 // tensors of this launch
-  int32_t chunk_start[OPT_MAX_TENSORS + 1];  // workgroups before tensor i; [n] = the grid
-  int64_t numel[OPT_MAX_TENSORS];
-};
 
 struct SumsqArgs {
   OptFrame f;
@@ -83,40 +66,6 @@ struct ConstantsArgs {
   double lr[OPT_MAX_GROUPS], beta1[OPT_MAX_GROUPS], beta2[OPT_MAX_GROUPS], weight_decay[OPT_MAX_GROUPS];
 };
 static_assert(sizeof(ConstantsArgs) <= 4096, "the argument block of one launch is limited to 4 KB");
-
-// the tensor of workgroup b: the last i with chunk_start[i] <= b (empty tensors never enter a frame, so the counts rise strictly)
-__device__ __forceinline__ int opt_find(const OptFrame& f, int b) {
-  int lo = 0, hi = f.n;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (f.chunk_start[mid] <= b) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// Elements i .. i + 3 of a chunk of `cnt` elements; those at and behind cnt read as 0.  FULL (a whole chunk of a 16-byte
-// aligned tensor: a workgroup-uniform choice) is straight-line 16-byte code; the other form serves tails and odd views.
-template <bool FULL>
-__device__ __forceinline__ void opt_load4(const float* __restrict__ base, int i, int cnt, bool vec, float (&r)[4]) {
-  if (FULL || (vec && i + 4 <= cnt)) {
-    VecIO<float, 4>::load(base + i, r);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) r[k] = i + k < cnt ? base[i + k] : 0.f;
-  }
-}
-
-template <bool FULL>
-__device__ __forceinline__ void opt_store4(float* __restrict__ base, int i, int cnt, bool vec, const float (&r)[4]) {
-  if (FULL || (vec && i + 4 <= cnt)) {
-    VecIO<float, 4>::store(base + i, r);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (i + k < cnt) base[i + k] = r[k];
-  }
-}
 
 template <bool FULL>
 __device__ __forceinline__ float opt_sumsq_chunk(const float* __restrict__ g, int cnt, bool vec) {
@@ -278,58 +227,6 @@ __global__ __launch_bounds__(256) void multi_scale_kernel(const ScaleArgs a, con
   const bool vec = ((uintptr_t)a.g[ti] & 15) == 0;
   if (vec && cnt == OPT_CHUNK) opt_scale_chunk<true>(g, cnt, vec, coef);
   else opt_scale_chunk<false>(g, cnt, vec, coef);
-}
-
-static inline int64_t opt_chunks(int64_t numel) { return (numel + OPT_CHUNK - 1) / OPT_CHUNK; }
-
-// The checks every list entry point makes before any launch.  `arrays` / `names`: the host pointer arrays the entry point
-// reads, each n_tensors device pointers, non-null wherever the length is not 0.
-static int opt_check_list(const char* who, const anemoi_multi_tensor_args* a, int n_arrays, void* const* const* arrays,
-                          const char* const* names) {
-  ANEMOI_REQUIRE(a != nullptr, ANEMOI_ERR_INVALID, "%s: null argument block", who);
-  ANEMOI_REQUIRE(a->struct_bytes == (int64_t)sizeof(anemoi_multi_tensor_args), ANEMOI_ERR_INVALID,
-                 "%s: argument block of %lld bytes, this library expects %lld (header / library out of sync)", who,
-                 (long long)a->struct_bytes, (long long)sizeof(anemoi_multi_tensor_args));
-  ANEMOI_REQUIRE(a->n_tensors >= 0, ANEMOI_ERR_INVALID, "%s: negative n_tensors %lld", who, (long long)a->n_tensors);
-  if (a->n_tensors == 0) return ANEMOI_OK;
-  ANEMOI_REQUIRE(a->numel != nullptr, ANEMOI_ERR_INVALID, "%s: null pointer (numel)", who);
-  for (int k = 0; k < n_arrays; ++k)
-    ANEMOI_REQUIRE(arrays[k] != nullptr, ANEMOI_ERR_INVALID, "%s: null pointer (%s)", who, names[k]);
-  for (int64_t i = 0; i < a->n_tensors; ++i) {
-    ANEMOI_REQUIRE(a->numel[i] >= 0, ANEMOI_ERR_INVALID, "%s: negative numel[%lld] = %lld", who, (long long)i,
-                   (long long)a->numel[i]);
-    if (a->numel[i] == 0) continue;
-    for (int k = 0; k < n_arrays; ++k)
-      ANEMOI_REQUIRE(arrays[k][i] != nullptr, ANEMOI_ERR_INVALID, "%s: null pointer (%s[%lld])", who, names[k], (long long)i);
-  }
-  return ANEMOI_OK;
-}
-
-// Walks the list in frames of at most OPT_MAX_TENSORS non-empty tensors (and fewer than 2^31 chunks) and calls
-// launch(frame, index of each frame tensor in the list, chunks of the list before the frame).
-template <typename Launch>
-static void opt_for_each_frame(const anemoi_multi_tensor_args* a, Launch launch) {
-  OptFrame f;
-  int64_t idx[OPT_MAX_TENSORS];
-  int64_t chunks_before = 0, frame_chunks = 0;
-  f.n = 0;
-  f.chunk_start[0] = 0;
-  for (int64_t i = 0; i <= a->n_tensors; ++i) {
-    const bool end = i == a->n_tensors;
-    const int64_t c = end ? 0 : opt_chunks(a->numel[i]);
-    if (!end && c == 0) continue;
-    if (f.n > 0 && (end || f.n == OPT_MAX_TENSORS || frame_chunks + c > 0x7fffffff)) {
-      launch(f, idx, chunks_before);
-      chunks_before += frame_chunks;
-      frame_chunks = 0;
-      f.n = 0;
-    }
-    if (end) break;
-    idx[f.n] = i;
-    f.numel[f.n] = a->numel[i];
-    frame_chunks += c;
-    f.chunk_start[++f.n] = (int32_t)frame_chunks;
-  }
 }
 
 // While a launch trail is armed: one record per non-empty tensor of the list, "who:what[i]" with i the tensor's index in the list

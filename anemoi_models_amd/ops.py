@@ -1838,3 +1838,104 @@ def multi_scale(grads, coef: Tensor) -> None:
     with _Timed("multi_scale", bytes=8 * sum(t.numel() for t in grads)):
         st = _lib.load().anemoi_multi_scale(ctypes.byref(a), _stream())
     _lib.check(st, "anemoi_multi_scale")
+
+
+# ---------------------------------------------------------------- weight averaging, device LR schedule (csrc/average.hip, DESIGN.md "8f-11")
+def _scalar_f32(who: str, name: str, t: Optional[Tensor], numel: int = 1) -> None:
+    if t is None:
+        return
+    _dev(t)
+    if t.dtype != torch.float32 or t.numel() != numel or not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous float32 device tensor of {numel} element(s)")
+
+
+def average_constants(avg: Tensor, n_averaged: Tensor, *, kind: str = "ema", decay: float = 0.999, warmup: bool = False,
+                      start_step: int = 0, every: int = 1, step: Optional[Tensor] = None,
+                      skip: Optional[Tensor] = None) -> Tensor:
+    """The scalars of one averaging update (``anemoi_average_constants``), written to ``avg`` (f32 ``[4]``: w, active, copy,
+    n_after) by one tiny kernel.  ``n_averaged``: the f32 device counter, advanced in place when the update is active;
+    ``step``: the optimizer's f32 device step counter (steps completed) that ``start_step`` / ``every`` gate on, or ``None``
+    (every call counts); ``skip``: the optimizer's one-element skip flag, or ``None``."""
+    import ctypes
+
+    if kind not in ("ema", "swa"):
+        raise ValueError(f"average_constants: kind must be 'ema' or 'swa', got {kind!r}")
+    _scalar_f32("average_constants", "avg", avg, _lib.AVG_CONSTS)
+    _scalar_f32("average_constants", "n_averaged", n_averaged)
+    _scalar_f32("average_constants", "step", step)
+    _scalar_f32("average_constants", "skip", skip)
+    c = _lib.AverageConstantsArgs()
+    c.struct_bytes = ctypes.sizeof(_lib.AverageConstantsArgs)
+    c.n_averaged, c.step, c.skip, c.avg = n_averaged.data_ptr(), _ptr(step), _ptr(skip), avg.data_ptr()
+    c.decay, c.start_step, c.every = float(decay), int(start_step), int(every)
+    c.kind, c.use_warmup = _lib.AVERAGE_EMA if kind == "ema" else _lib.AVERAGE_SWA, int(bool(warmup))
+    st = _lib.load().anemoi_average_constants(ctypes.byref(c), _stream())
+    _lib.check(st, "anemoi_average_constants")
+    return avg
+
+
+def multi_average(params, shadow, avg: Tensor) -> None:
+    """One averaging update of the list in one pass (``anemoi_multi_average``): under the block ``avg`` of
+    :func:`average_constants`, ``shadow`` is left alone (inactive), becomes a bit copy of ``params`` (the first update) or
+    ``s <- fmaf(p - s, w, s)``.  ``params`` are only read."""
+    import ctypes
+
+    params, shadow = list(params), list(shadow)
+    if len(params) != len(shadow):
+        raise ValueError("multi_average: the two lists must have one tensor per parameter")
+    _check_list("multi_average", "params", params)
+    _check_list("multi_average", "shadow", shadow, params)
+    _scalar_f32("multi_average", "avg", avg, _lib.AVG_CONSTS)
+    a = _lib.MultiAverageArgs()
+    a.struct_bytes, a.n_tensors = ctypes.sizeof(_lib.MultiAverageArgs), len(params)
+    keep = (numel_array(params), ptr_array(params), ptr_array(shadow))
+    a.numel, a.params, a.shadow = (ctypes.cast(k, ctypes.c_void_p) for k in keep)
+    a.avg = avg.data_ptr()
+    with _Timed("multi_average", bytes=12 * sum(t.numel() for t in params)):
+        st = _lib.load().anemoi_multi_average(ctypes.byref(a), _stream())
+    _lib.check(st, "anemoi_multi_average")
+
+
+def multi_swap(a_list, b_list) -> None:
+    """``a[i] <-> b[i]`` over the two lists, exactly (``anemoi_multi_swap``).  The lists must not overlap."""
+    import ctypes
+
+    a_list, b_list = list(a_list), list(b_list)
+    if len(a_list) != len(b_list):
+        raise ValueError("multi_swap: the two lists must have one tensor per parameter")
+    _check_list("multi_swap", "a", a_list)
+    _check_list("multi_swap", "b", b_list, a_list)
+    a = _lib.MultiSwapArgs()
+    a.struct_bytes, a.n_tensors = ctypes.sizeof(_lib.MultiSwapArgs), len(a_list)
+    keep = (numel_array(a_list), ptr_array(a_list), ptr_array(b_list))
+    a.numel, a.a, a.b = (ctypes.cast(k, ctypes.c_void_p) for k in keep)
+    with _Timed("multi_swap", bytes=16 * sum(t.numel() for t in a_list)):
+        st = _lib.load().anemoi_multi_swap(ctypes.byref(a), _stream())
+    _lib.check(st, "anemoi_multi_swap")
+
+
+def lr_schedule(lrs, steps, bases, *, warmup_steps, total_steps, lr_min, warmup_start, warmup_prefix) -> None:
+    """Linear warm-up and cosine decay evaluated on the device (``anemoi_lr_schedule``): ``lrs[g]`` (one-element f32 device
+    tensors) is written from ``steps[g]`` (the group's f32 device step counter, steps completed).  Every other argument is a
+    list with one entry per group; at most ``_lib.LR_MAX_GROUPS`` groups."""
+    import ctypes
+
+    lrs, steps = list(lrs), list(steps)
+    n = len(lrs)
+    per_group = (steps, bases, warmup_steps, total_steps, lr_min, warmup_start, warmup_prefix)
+    if any(len(v) != n for v in per_group):
+        raise ValueError("lr_schedule: every argument must have one entry per group")
+    for i in range(n):
+        _scalar_f32("lr_schedule", f"lrs[{i}]", lrs[i])
+        _scalar_f32("lr_schedule", f"steps[{i}]", steps[i])
+    fa, ia, ba = ctypes.c_double * max(n, 1), ctypes.c_int64 * max(n, 1), ctypes.c_int32 * max(n, 1)
+    s = _lib.LrScheduleArgs()
+    s.struct_bytes, s.n_groups = ctypes.sizeof(_lib.LrScheduleArgs), n
+    keep = dict(step=ptr_array(steps), lr=ptr_array(lrs), base=fa(*[float(v) for v in bases]),
+                lr_min=fa(*[float(v) for v in lr_min]), warmup_start=fa(*[float(v) for v in warmup_start]),
+                warmup_steps=ia(*[int(v) for v in warmup_steps]), total_steps=ia(*[int(v) for v in total_steps]),
+                warmup_prefix=ba(*[int(bool(v)) for v in warmup_prefix]))
+    for name, arr in keep.items():
+        setattr(s, name, ctypes.cast(arr, ctypes.c_void_p))
+    st = _lib.load().anemoi_lr_schedule(ctypes.byref(s), _stream())
+    _lib.check(st, "anemoi_lr_schedule")

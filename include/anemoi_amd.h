@@ -1117,6 +1117,96 @@ int anemoi_multi_adamw(const anemoi_multi_tensor_args* args, anemoi_stream_t str
 int anemoi_multi_scale(const anemoi_multi_tensor_args* args, anemoi_stream_t stream);
 
 /*
+ * Weight averaging and the learning-rate schedule on the device (ABI v55, csrc/average.hip, DESIGN.md section 7 "8f-11"), on the
+ * multi-tensor frame above: lists as HOST arrays of device f32 pointers and lengths, anemoi_multi_tensor_max_tensors() tensors
+ * per launch, a tensor of numel 0 skipped, an empty list launches nothing, any pointer 4-byte aligned.  Each entry point has its
+ * own argument block with the `struct_bytes` layout check.
+ * Checked before any launch, else ANEMOI_ERR_INVALID with a message naming the argument: a null block or pointer, a negative
+ * count or length, decay outside [0, 1), every < 1, start_step < 0, warmup_steps < 0, total_steps < 1, a negative learning
+ * rate, more than 32 groups.
+ */
+#define ANEMOI_AVERAGE_EMA 0
+#define ANEMOI_AVERAGE_SWA 1
+
+/*
+ * The scalars of one averaging update, by one tiny kernel; nothing is read back.  avg is device f32 [4] = {w, active, copy,
+ * n_after}.  n = n_averaged[0] (a device f32 counter, advanced here when active); step (may be NULL): the optimizer's device
+ * f32 step counter, steps COMPLETED (read after anemoi_adamw_constants advanced it); skip (may be NULL): the optimizer's
+ * list-wide skip flag (consts[3] of anemoi_adamw_constants).
+ *   active = !skip && (step == NULL || (t >= start_step && (t - start_step) % every == 0))
+ *   inactive: w = 0, n_averaged keeps its value.  Active: n == 0: copy = 1 (w = 1);
+ *   EMA: w = 1 - d, d = use_warmup ? min(decay, (1 + n) / (10 + n)) : decay;   SWA: w = 1 / (n + 1)
+ * (w evaluated in f64, rounded once).  Trail: "avg".
+ */
+typedef struct anemoi_average_constants_args {
+  int64_t struct_bytes;
+  float* n_averaged;  /* device f32 [1] */
+  const float* step;  /* device f32 [1], or NULL */
+  const float* skip;  /* device f32 [1], or NULL */
+  float* avg;         /* device f32 [4] */
+  double decay;       /* EMA: in [0, 1) */
+  int64_t start_step; /* >= 0 */
+  int64_t every;      /* >= 1 */
+  int32_t kind;       /* ANEMOI_AVERAGE_EMA / ANEMOI_AVERAGE_SWA */
+  int32_t use_warmup;
+} anemoi_average_constants_args;
+
+int anemoi_average_constants(const anemoi_average_constants_args* args, anemoi_stream_t stream);
+
+/*
+ * shadow[i] <- the average of shadow[i] and params[i] under the block `avg` of anemoi_average_constants, one pass (8 bytes read,
+ * 4 written per element; params are only read): inactive: nothing is read or written; copy: shadow <- params bit for bit;
+ * else shadow <- fmaf(params - shadow, w, shadow) in correctly rounded f32 (two roundings).  Trail: "shadow[i]" per non-empty
+ * tensor i of the list, as [1, numel].
+ */
+typedef struct anemoi_multi_average_args {
+  int64_t struct_bytes;
+  int64_t n_tensors;
+  const int64_t* numel; /* host [n_tensors] */
+  void* const* params;  /* host [n_tensors] of device f32 pointers, read only */
+  void* const* shadow;  /* host [n_tensors] of device f32 pointers, read and written */
+  const float* avg;     /* device f32 [4] */
+} anemoi_multi_average_args;
+
+int anemoi_multi_average(const anemoi_multi_average_args* args, anemoi_stream_t stream);
+
+/* a[i] <-> b[i], element for element and exactly (bit patterns move, no arithmetic); the two lists must not overlap.
+ * Trail: "a[i]", then "b[i]", per non-empty tensor. */
+typedef struct anemoi_multi_swap_args {
+  int64_t struct_bytes;
+  int64_t n_tensors;
+  const int64_t* numel; /* host [n_tensors] */
+  void* const* a;       /* host [n_tensors] of device f32 pointers each */
+  void* const* b;
+} anemoi_multi_swap_args;
+
+int anemoi_multi_swap(const anemoi_multi_swap_args* args, anemoi_stream_t stream);
+
+/*
+ * lr[g][0] <- the schedule of group g at t = step[g][0] (the group's device f32 step counter, steps completed), by one tiny
+ * kernel, at most 32 groups; evaluated in f64 and rounded once:
+ *   t < warmup_steps:  warmup_start + t (base - warmup_start) / warmup_steps
+ *   else, tc = warmup_prefix ? t - warmup_steps : t:   tc < total_steps: lr_min + 0.5 (base - lr_min)(1 + cos(pi tc / total_steps))
+ *                                                      else lr_min
+ * warmup_prefix = 1 is torch's SequentialLR(LinearLR, CosineAnnealingLR); warmup_prefix = 0 with warmup_start = 0 restates
+ * timm's CosineLRScheduler as anemoi-training configures it.  Trail: "lr[g]" per group.
+ */
+typedef struct anemoi_lr_schedule_args {
+  int64_t struct_bytes;
+  int64_t n_groups;
+  void* const* step;            /* host [n_groups] of device f32 [1], read only */
+  void* const* lr;              /* host [n_groups] of device f32 [1], written */
+  const double* base;           /* host [n_groups] each; >= 0 */
+  const double* lr_min;         /* >= 0 */
+  const double* warmup_start;   /* >= 0 */
+  const int64_t* warmup_steps;  /* >= 0 */
+  const int64_t* total_steps;   /* >= 1 */
+  const int32_t* warmup_prefix; /* 0 / 1 */
+} anemoi_lr_schedule_args;
+
+int anemoi_lr_schedule(const anemoi_lr_schedule_args* args, anemoi_stream_t stream);
+
+/*
  * Launch trail -- opt-in per-launch output digests (csrc/trail.hip).
  *
  * While a trail is armed on the calling thread, every entry point of this header that writes device memory appends one
