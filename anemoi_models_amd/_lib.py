@@ -107,6 +107,24 @@ def linear_route(entry: str, **fields):
     return load().anemoi_linear_route(ctypes.byref(args), ctypes.byref(route)), route
 
 
+class LinearThinArgs(ctypes.Structure):
+    """``anemoi_linear_thin_args`` of include/anemoi_amd.h (``anemoi_linear_thin``), field for field."""
+
+    _fields_ = [
+        ("struct_bytes", c_int64),
+        ("out_dtype", ctypes.c_int32), ("batch", ctypes.c_int32),
+        ("x", c_void_p), ("w", c_void_p), ("bias", c_void_p), ("colsum", c_void_p), ("stats", c_void_p),
+        ("residual", c_void_p), ("y", c_void_p), ("stats_out", c_void_p),
+        ("ldx", c_int64), ("ldr", c_int64), ("ldy", c_int64), ("M", c_int64),
+        ("N", ctypes.c_int32), ("K", ctypes.c_int32),
+        ("stride_x", c_int64), ("stride_w", c_int64), ("stride_y", c_int64), ("stride_r", c_int64),
+        ("eps", c_float), ("reserved", ctypes.c_int32),
+    ]
+
+
+THIN_SHAPES = ((256, 64), (64, 256), (256, 256), (80, 1024), (16, 1024), (16, 256), (256, 128))  # (N, K) of csrc/gemm_thin_plan.hpp::SHAPES
+
+
 class GtBlockArgs(ctypes.Structure):
     """``anemoi_gt_block_args`` of include/anemoi_amd.h (block-level entry points), field for field."""
 
@@ -272,6 +290,7 @@ SIGNATURES = {
     "anemoi_linear_dual": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
                                    c_int64, c_int, c_int, c_int, c_void_p]),
     "anemoi_linear_route": (c_int, [ctypes.POINTER(LinearArgs), ctypes.POINTER(LinearRoute)]),
+    "anemoi_linear_thin": (c_int, [ctypes.POINTER(LinearThinArgs), c_void_p]),
     "anemoi_linear_actgrad": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64,
                                       c_int, c_int, c_int, c_void_p]),
     "anemoi_gt_conv": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,

@@ -92,7 +92,13 @@ class EmbeddedRows:
         t = self._packed.get((self._tag, "embstats", self.dtype, kp, self.one_col), [self.emb.weight, self.emb.bias],
                              lambda: runtime.embedding_stats_operator(self.emb.weight, self.emb.bias, kp, self.one_col,
                                                                       self.dtype))
-        return ops.row_stats(runtime.linear(self.x_aug, t, None, stats_eps=eps), eps)
+        # nothing but these statistics is read of T x_aug: the thin kernel can keep the product in registers and store only
+        # them.  Measured slower than the persistent kernel + finalize at config 3 (0.189 against 0.132 ms: four waves share a
+        # row block and meet at two barriers per block, profiles/r11_thin_hoist.md), so this site is opt-in:
+        # ANEMOI_AMD_THIN_STATS=1 (under ANEMOI_AMD_THIN).
+        thin = ops.thin_enabled() and os.environ.get("ANEMOI_AMD_THIN_STATS", "0") == "1"
+        st = ops.linear_thin(self.x_aug, t, stats_eps=eps) if thin else None
+        return st if st is not None else ops.row_stats(runtime.linear(self.x_aug, t, None, stats_eps=eps), eps)
 
 
 class BaseBlock(nn.Module, ABC):
@@ -741,11 +747,27 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
         up = self.fold_width(dtype)
         sq_layers = [self.lin_self, self.lin_query]
         wp, bp = self._folded_out(dtype, up)
-        sq = self._ln_linear(self._ln_begin(self.layer_norm2, x_dst), "squ",
-                             lambda: self._folded_in("squ", sq_layers, dtype, up),
-                             lambda: self._folded_rows(sq_layers, up), self._fold_params(sq_layers))  # x_r | q | u
         per_head = w_qt.dim() == 3
-        qt = ops.linear_heads(sq[:, c:2 * c], w_qt) if per_head else runtime.linear(sq[:, c:2 * c], w_qt)
+
+        def dst_side():
+            sq = self._ln_linear(self._ln_begin(self.layer_norm2, x_dst), "squ",
+                                 lambda: self._folded_in("squ", sq_layers, dtype, up),
+                                 lambda: self._folded_rows(sq_layers, up), self._fold_params(sq_layers))  # x_r | q | u
+            return sq, (ops.linear_heads(sq[:, c:2 * c], w_qt) if per_head else runtime.linear(sq[:, c:2 * c], w_qt))
+
+        # hoisted destination rows (the encoder's mesh rows on the inference path): x_r | q | u and qt depend on parameters
+        # only -- both are read, never written, below.  Sources: the rows' own, this block's destination-side parameters, and
+        # the source-side ones that form A_k in w_qt.
+        sources = runtime.static_sources(x_dst) if runtime.enc_hoist_enabled() else None
+        if sources is not None:
+            ln1, ln2, emb = self.layer_norm1, self.layer_norm2, x_src.emb
+            sources = (sources + [h_dst, ln2.weight, ln2.bias] + self._fold_params(sq_layers)
+                       + [self.lin_key.weight, self.lin_key.bias, self.lin_value.weight, self.lin_value.bias, ln1.weight,
+                          ln1.bias, emb.weight, emb.bias])
+            sq, qt = runtime.hoisted(self._packed, ("squ|qt", dtype, tuple(h_dst.shape), up, x_src.x_aug.shape[1], x_src.one_col),
+                                     sources, dst_side)
+        else:
+            sq, qt = dst_side()
         att = torch.empty((sq.shape[0], wp.shape[1]), dtype=dtype, device=sq.device)
         if wp.shape[1] > c + h * up:
             att[:, c + h * up:].zero_()
@@ -753,8 +775,7 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
                                       plan.col, h, self.out_channels_conv, up, sum_col, att[:, c:c + h * up])
         del qt
         if per_head:
-            ops.linear_heads(g, w_g, out=att[:, :c])
-            ops.add(att[:, :c], sq[:, :c], out=att[:, :c])
+            ops.linear_heads(g, w_g, out=att[:, :c], residual=sq[:, :c])
         else:
             runtime.linear(g, w_g, residual=sq[:, :c], out=att[:, :c])
         del g

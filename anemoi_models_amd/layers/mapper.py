@@ -157,14 +157,22 @@ class GraphTransformerBaseMapper(GraphEdgeMixin, BaseMapper):
         self._plans = runtime.PlanCache()
 
     # ---- hooks specialised by the forward / backward mapper ------------------------------------
-    def _embed(self, x_src: Tensor, x_dst: Tensor, one_cols=(None, None)):
+    def _embed(self, x_src: Tensor, x_dst: Tensor, one_cols=(None, None), dst_static: bool = False):
         return x_src, x_dst  # the base mapper embeds nothing (reference BaseMapper.pre_process, layers/mapper.py:87-96)
 
     def _embedded(self, tag: str, lin: nn.Linear, x: Tensor, eps: Optional[float], one_col: Optional[int],
-                  materialise: bool):
+                  materialise: bool, static: bool = False):
         """``lin(x)`` for the block -- as an ``EmbeddedRows`` handle when the block's LayerNorm -> Linear on these rows can
         run on the raw features instead (few input features, bf16 LayerNorm-fold path): ``x`` with a constant-1 column
-        in its K padding (``one_col``: the caller already wrote it; None: an augmented copy is made here)."""
+        in its K padding (``one_col``: the caller already wrote it; None: an augmented copy is made here).
+
+        ``static``: ``x`` is a hoisted, call-invariant operand (``runtime.mark_static``): so is the embedding, with the
+        statistics it carries -- kept until ``x``'s sources or the embedding's parameters change."""
+        sources = runtime.static_sources(x) if static else None
+        if sources is not None:
+            sources = sources + [x, lin.weight, lin.bias]
+            return runtime.hoisted(self._packed, (tag, x.dtype, tuple(x.shape), one_col, eps, materialise), sources,
+                                   lambda: runtime.mark_static(self._embedded(tag, lin, x, eps, one_col, materialise), sources))
         k_in = lin.in_features
         if eps is None or not runtime.embed_fold_enabled(x.dtype) or 2 * (k_in + 1) > lin.out_features:
             return linear_native(self._packed, tag, lin, x, stats_eps=eps)
@@ -197,7 +205,9 @@ class GraphTransformerBaseMapper(GraphEdgeMixin, BaseMapper):
 
     def native(self, x_src: Tensor, x_dst: Tensor, batch_size: int, out_dtype: Optional[torch.dtype] = None,
                src_map: Optional[Tensor] = None, dst_map: Optional[Tensor] = None, one_cols=(None, None)) -> Tensor:
-        """Inputs in the compute dtype (optionally K padded).  Returns the mapped destination nodes.
+        """Inputs in the compute dtype (optionally K padded).  Returns the mapped destination nodes.  An ``x_dst`` marked
+        ``runtime.mark_static`` (the model root's hoisted mesh rows) lets the embedding and the block keep what they derive
+        from it alone; the chunked path recomputes.
 
         ``src_map`` / ``dst_map``: optional external-id -> row relabelling when the caller keeps a node set in an
         internal order (the model root does this for the mesh).  ``one_cols = (src, dst)``: column of ``x_src`` /
@@ -206,8 +216,8 @@ class GraphTransformerBaseMapper(GraphEdgeMixin, BaseMapper):
         plan = self._plans.get(self.edge_index_base, n_src, n_dst, batch_size, self.edge_inc, src_map, dst_map)
         ea = runtime.edge_attr_csr_cached(self._packed, self.edge_attr, self.trainable.trainable, plan,
                                           *self.proc.edge_layout(x_dst.dtype))
-        h_src, h_dst = self._embed(x_src, x_dst, one_cols)
         num_chunks = self.proc.num_chunks if self.training else inference_num_chunks()
+        h_src, h_dst = self._embed(x_src, x_dst, one_cols, dst_static=num_chunks <= 1 and runtime.enc_hoist_enabled())
         _, h_dst = self.proc.native(h_src, h_dst, ea, plan, num_chunks, out_stats_eps=self._extract_ln_eps(h_dst.dtype))
         return self._extract(h_dst, out_dtype)
 
@@ -282,12 +292,13 @@ class GraphTransformerForwardMapper(ForwardMapperPreProcessMixin, GraphTransform
                          src_grid_size=src_grid_size, dst_grid_size=dst_grid_size)
         self.emb_nodes_src = nn.Linear(self.in_channels_src, self.hidden_dim)
 
-    def _embed(self, x_src: Tensor, x_dst: Tensor, one_cols=(None, None)):
+    def _embed(self, x_src: Tensor, x_dst: Tensor, one_cols=(None, None), dst_static: bool = False):
         eps1, eps2 = self._block_ln_eps(x_src.dtype)  # the embeddings enter the block's layer_norm1 / layer_norm2
         # source rows feed k | v only: their embedding is never written out when it can be folded away
         return (self._embedded("emb_nodes_src", self.emb_nodes_src, x_src, eps1, one_cols[0],
                                materialise=self.proc.update_src_nodes),
-                self._embedded("emb_nodes_dst", self.emb_nodes_dst, x_dst, eps2, one_cols[1], materialise=True))
+                self._embedded("emb_nodes_dst", self.emb_nodes_dst, x_dst, eps2, one_cols[1], materialise=True,
+                               static=dst_static))
 
     def forward(self, x, batch_size: int, shard_shapes, model_comm_group=None):
         x_dst = self._run(x, batch_size, shard_shapes, model_comm_group)
@@ -322,9 +333,9 @@ class GraphTransformerBackwardMapper(BackwardMapperPostProcessMixin, GraphTransf
         return (x_src, self._apply_module(self.emb_nodes_dst, x_dst), change_channels_in_shape(shapes_src, self.hidden_dim),
                 change_channels_in_shape(shapes_dst, self.hidden_dim))
 
-    def _embed(self, x_src: Tensor, x_dst: Tensor, one_cols=(None, None)):
+    def _embed(self, x_src: Tensor, x_dst: Tensor, one_cols=(None, None), dst_static: bool = False):
         return x_src, self._embedded("emb_nodes_dst", self.emb_nodes_dst, x_dst, self._block_ln_eps(x_dst.dtype)[1],
-                                     one_cols[1], materialise=True)
+                                     one_cols[1], materialise=True)  # (the grid rows carry input data: never static)
 
     def _extract(self, x_dst: Tensor, out_dtype) -> Tensor:
         ln, lin = self.node_data_extractor[0], self.node_data_extractor[1]
@@ -333,7 +344,10 @@ class GraphTransformerBackwardMapper(BackwardMapperPostProcessMixin, GraphTransf
             wf, bf, cs = self._packed.get(("extract", "lnfold", x_dst.dtype), [lin.weight, lin.bias, ln.weight, ln.bias],
                                           lambda: runtime.fold_layer_norm(lin.weight.detach().float(), lin.bias,
                                                                           ln.weight, ln.bias, x_dst.dtype))
-            return runtime.linear(x_dst, wf, bf, out_dtype=out_dtype, ln=(ops.row_stats(x_dst, ln.eps), cs))
+            fold = (ops.row_stats(x_dst, ln.eps), cs)
+            # few output variables from a wide latent: the weight stays in registers and x_dst streams through once
+            y = ops.linear_thin(x_dst, wf, bf, out_dtype=out_dtype, ln=fold) if ops.thin_enabled() else None
+            return y if y is not None else runtime.linear(x_dst, wf, bf, out_dtype=out_dtype, ln=fold)
         h = ops.layer_norm(x_dst, runtime.f32c(ln.weight), runtime.f32c(ln.bias), ln.eps)
         return linear_native(self._packed, "extract", lin, h, out_dtype=out_dtype)
 

@@ -98,6 +98,7 @@ class AnemoiModelEncProcDec(nn.Module):
             ]
         )
         self._idx_cache: dict = {}
+        self._hoisted = runtime.PackedWeights()  # call-invariant activations of the inference path (runtime.hoisted)
         self._set_truncation(truncation_data)
 
     def _set_truncation(self, truncation_data) -> None:
@@ -323,13 +324,24 @@ class AnemoiModelEncProcDec(nn.Module):
         order, inv = self._mesh_order(x.device)
         tr_hidden = na.trainable_tensors[hidden].trainable
         w_hidden = na.attr_ndims[hidden]
-        x_hidden = ops.assemble_nodes(None, na.latlons(hidden)[order],
-                                      self._with_ones(None if tr_hidden is None else tr_hidden[order], order.numel(), fold),
-                                      batch_size, dtype, ld_out=self._feature_ld(w_hidden + int(fold), dtype, fold))
         one_data, one_hidden = (width, w_hidden) if fold else (None, None)
 
-        enc = self.encoder.native(x_data, x_hidden, batch_size, dst_map=inv,
-                                  **self._one_cols(self.encoder, one_data, one_hidden))
+        def hidden_rows():
+            return ops.assemble_nodes(None, na.latlons(hidden)[order],
+                                      self._with_ones(None if tr_hidden is None else tr_hidden[order], order.numel(), fold),
+                                      batch_size, dtype, ld_out=self._feature_ld(w_hidden + int(fold), dtype, fold))
+
+        # no input data enters the mesh rows: on the inference path they, and what the encoder derives from them alone, are
+        # built once per parameter state (runtime.hoisted) -- GraphTransformer encoder only, the others take per-call rows
+        enc_kw = self._one_cols(self.encoder, one_data, one_hidden)
+        if runtime.enc_hoist_enabled() and enc_kw:
+            sources = [tr_hidden, na.latlons(hidden), order]
+            x_hidden = runtime.hoisted(self._hoisted, ("x_hidden", dtype, batch_size, str(x.device), fold), sources,
+                                       lambda: runtime.mark_static(hidden_rows(), sources))
+        else:
+            x_hidden = hidden_rows()
+
+        enc = self.encoder.native(x_data, x_hidden, batch_size, dst_map=inv, **enc_kw)
         # GraphTransformer forward mapper hands the RAW data input on to the decoder (reference layers/mapper.py:345);
         # the GNN forward mapper hands on its UPDATED source embedding (reference layers/mapper.py:522)
         x_data_latent, x_latent = (x_data, enc) if not isinstance(enc, tuple) else enc

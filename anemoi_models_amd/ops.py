@@ -9,6 +9,8 @@ them with CPU tensors raises.  (CPU tests of the host logic substitute this modu
 
 from __future__ import annotations
 
+import ctypes
+import os
 from typing import NamedTuple
 from typing import Optional
 
@@ -26,10 +28,11 @@ PROFILE: Optional[list] = None
 
 
 class _Timed:
-    __slots__ = ("name", "work", "start")
+    __slots__ = ("name", "work", "start", "launched")
 
     def __init__(self, name: str, **work) -> None:
         self.name, self.work, self.start = name, work, None
+        self.launched = True  # set to False inside the block when the library refused the call and launched nothing
 
     def __enter__(self):
         if PROFILE is not None:
@@ -38,7 +41,7 @@ class _Timed:
         return self
 
     def __exit__(self, *exc):
-        if self.start is not None:
+        if self.start is not None and self.launched:
             end = torch.cuda.Event(enable_timing=True)
             end.record(torch.cuda.current_stream())
             PROFILE.append((self.name, self.start, end, self.work))
@@ -523,11 +526,17 @@ def gt_edge_attention_folded(q: Tensor, k: Tensor, v: Tensor, x_r: Optional[Tens
     return out
 
 
-def linear_heads(x: Tensor, w: Tensor, out: Optional[Tensor] = None) -> Tensor:
-    """``H`` independent products ``out[:, h*N:(h+1)*N] = x[:, h*K:(h+1)*K] @ w[h].T`` as ONE launch
-    (``anemoi_linear_batched``; no bias / activation).  ``w`` is contiguous ``[H, N, K]`` in x's dtype; ``x`` / ``out`` are
-    row-major ``[M, >= H*K]`` / ``[M, >= H*N]`` slices.  The small products on either side of the raw-row edge phase."""
-    _dev(x, w, out)
+def linear_heads(x: Tensor, w: Tensor, out: Optional[Tensor] = None, residual: Optional[Tensor] = None) -> Tensor:
+    """``H`` independent products ``out[:, h*N:(h+1)*N] = x[:, h*K:(h+1)*K] @ w[h].T`` (``+ residual[:, h*N:(h+1)*N]``) as
+    ONE launch (no bias / activation).  ``w`` is contiguous ``[H, N, K]`` in x's dtype; ``x`` / ``out`` / ``residual`` are
+    row-major ``[M, >= H*K]`` / ``[M, >= H*N]`` slices.  The small products on either side of the raw-row edge phase: per-head
+    shapes the thin kernel holds in registers run on it (``linear_thin``, residual fused); everything else, and everything
+    under ``ANEMOI_AMD_THIN=0``, is ``anemoi_linear_batched`` followed by ``add`` for the residual."""
+    _dev(x, w, out, residual)
+    if thin_enabled() and w.dim() == 3:
+        y = linear_thin(x, w, out=out, residual=residual)
+        if y is not None:
+            return y
     _rows(x)
     if w.dim() != 3 or w.dtype != x.dtype or not w.is_contiguous():
         raise ValueError("linear_heads: weight must be contiguous [H, N, K] in the activation dtype")
@@ -547,7 +556,90 @@ def linear_heads(x: Tensor, w: Tensor, out: Optional[Tensor] = None) -> Tensor:
         st = _lib.load().anemoi_linear_batched(code, code, x.data_ptr(), _ld(x), k, w.data_ptr(), n * k, out.data_ptr(),
                                                _ld(out), n, h, m, n, k, _stream())
     _lib.check(st, "anemoi_linear_batched")
+    if residual is not None:
+        add(out[:, :h * n], residual[:, :h * n], out=out[:, :h * n])
     return out
+
+
+def thin_enabled() -> bool:
+    """The thin-Linear route (``anemoi_linear_thin``) is taken where a call site asks for it; ``ANEMOI_AMD_THIN=0`` keeps the
+    fused Linear family's launches at every such site."""
+    return os.environ.get("ANEMOI_AMD_THIN", "1") != "0"
+
+
+def linear_thin(x: Tensor, w: Tensor, bias: Optional[Tensor] = None, *, residual: Optional[Tensor] = None,
+                out: Optional[Tensor] = None, out_dtype: Optional[torch.dtype] = None, ln=None,
+                stats_eps: Optional[float] = None) -> Optional[Tensor]:
+    """``x @ w.T (+ bias) (+ residual)`` on the register-resident thin kernel (``csrc/gemm_thin.hip``), or ``None`` when the
+    library does not take the call (shape outside its table, an unsupported combination): NOTHING is launched then and the
+    caller keeps its route through the fused Linear family.  bf16 ``x`` and ``w`` only.
+
+    ``w [N, K]``: one product.  ``w [H, N, K]``: ``H`` products over the column blocks of ``x [M, >= H K]``, ``out`` and
+    ``residual [M, >= H N]`` and ``bias [H N]``, as ``linear_heads``.  ``ln=(stats, colsum)``: the LayerNorm fold of
+    ``linear(ln=)``.  ``stats_eps``: statistics only -- returns ``row_stats(x @ w.T + bias, stats_eps)`` ``[M, 2]`` of the
+    product as ``out_dtype`` (default bf16) would store it, and stores no product."""
+    if not x.is_cuda:  # (host-logic tests substitute the fused family's functions: their tensors keep that route)
+        return None
+    _dev(x, w, bias, residual, out)
+    _rows(x)
+    if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16 or not w.is_contiguous() or w.dim() not in (2, 3):
+        return None
+    h = w.shape[0] if w.dim() == 3 else 1
+    n, k = w.shape[-2], w.shape[-1]
+    m = x.shape[0]
+    if (n, k) not in _lib.THIN_SHAPES or m == 0 or x.shape[1] < h * k:
+        return None
+    odt = out.dtype if out is not None else (out_dtype or x.dtype)
+    if odt not in _DT:
+        return None
+    # operands the kernel's 16-byte accesses cannot take are a refusal, not an error: the fused family may take them
+    mult = 8 if odt == torch.bfloat16 else 4
+    for t, md in ((x, 8), (w, 8), (out, mult), (residual, 8)):
+        if t is not None and (t.data_ptr() % 16 != 0 or (t.dim() == 2 and _ld(_rows(t)) % md != 0)):
+            return None
+    for t in (bias,) + (tuple(ln) if ln is not None else ()):
+        if t is not None and t.data_ptr() % 16 != 0:
+            return None
+    a = _lib.LinearThinArgs()
+    a.struct_bytes = ctypes.sizeof(_lib.LinearThinArgs)
+    a.out_dtype, a.batch = _DT[odt], h
+    a.x, a.w, a.bias = x.data_ptr(), w.data_ptr(), _ptr(bias)
+    a.ldx, a.M, a.N, a.K = _ld(x), m, n, k
+    a.stride_x, a.stride_w, a.stride_y, a.stride_r = k, n * k, n, n
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous() or bias.numel() < h * n):
+        raise ValueError("linear_thin: bias must be a contiguous f32 vector with one entry per output column")
+    if ln is not None:
+        stats, colsum = ln
+        _dev(stats, colsum)
+        if stats.shape != (m, 2) or stats.dtype != torch.float32 or not stats.is_contiguous():
+            raise ValueError("linear_thin: ln stats must be the contiguous [M, 2] f32 result of row_stats(x)")
+        if colsum.numel() < n or colsum.dtype != torch.float32 or not colsum.is_contiguous():
+            raise ValueError("linear_thin: ln colsum must be a contiguous f32 vector with one entry per output column")
+        a.stats, a.colsum = stats.data_ptr(), colsum.data_ptr()
+    if residual is not None:
+        if residual.dtype != torch.bfloat16 or _rows(residual).shape[0] != m or residual.shape[1] < h * n:
+            raise ValueError("linear_thin: the residual must be bf16 [M, >= H*N]")
+        a.residual, a.ldr = residual.data_ptr(), _ld(residual)
+    result = None
+    if stats_eps is not None:
+        result = torch.empty((m, 2), dtype=torch.float32, device=x.device)
+        a.stats_out, a.eps = result.data_ptr(), stats_eps
+        moved = (m * h * k + h * n * k) * 2 + m * 8
+    else:
+        if out is None:
+            out = torch.empty((m, h * n), dtype=odt, device=x.device)
+        if _rows(out).shape[0] != m or out.shape[1] < h * n:
+            raise ValueError("linear_thin: out must be [M, >= H*N]")
+        result = out
+        a.y, a.ldy = out.data_ptr(), _ld(out)
+        moved = (m * h * k + h * n * k) * 2 + m * h * n * (out.element_size() + (0 if residual is None else 2))
+    with _Timed("linear", flops=2 * m * h * n * k, bytes=moved, m=m, n=h * n, k=k, thin=True) as timed:
+        st = _lib.load().anemoi_linear_thin(ctypes.byref(a), _stream())
+        timed.launched = st == _lib.ANEMOI_OK
+    if st == _lib.ANEMOI_ERR_UNSUPPORTED:
+        return None
+    _lib.check(st, "anemoi_linear_thin")
+    return result
 
 
 def gt_edge_attention_raw(qt: Tensor, x_raw: Tensor, src_stats: Tensor, u: Tensor, edge_attr: Tensor, rowptr: Tensor,
@@ -1289,8 +1381,9 @@ def add(a: Tensor, b: Tensor, out: Optional[Tensor] = None) -> Tensor:
         raise ValueError("add: shape / dtype mismatch")
     if out is None:
         out = torch.empty(a.shape, dtype=a.dtype, device=a.device)
-    st = _lib.load().anemoi_add(dtype_code(a.dtype), a.data_ptr(), _ld(_rows(a)), b.data_ptr(), _ld(_rows(b)),
-                                out.data_ptr(), _ld(_rows(out)), a.shape[0], a.shape[1], _stream())
+    with _Timed("add", bytes=3 * a.shape[0] * a.shape[1] * a.element_size(), m=a.shape[0], n=a.shape[1]):
+        st = _lib.load().anemoi_add(dtype_code(a.dtype), a.data_ptr(), _ld(_rows(a)), b.data_ptr(), _ld(_rows(b)),
+                                    out.data_ptr(), _ld(_rows(out)), a.shape[0], a.shape[1], _stream())
     _lib.check(st, "anemoi_add")
     return out
 

@@ -521,7 +521,9 @@ class PlanCache:
         key = (edge_index.data_ptr(), edge_index._version, tuple(edge_index.shape), str(edge_index.device), n_src,
                n_dst, batch_size, None if src_map is None else src_map.data_ptr(),
                None if dst_map is None else dst_map.data_ptr())
-        plan = self._plans.get(key)
+        # (the entry holds the two maps: while it lives their addresses cannot be handed to other maps, so the pointers in the
+        # key do name these tensors -- the model root rebuilds its mesh order on request)
+        plan = self._plans.get(key, (None,))[0]
         if plan is None:
             path = self._disk_path(edge_index, n_src, n_dst, batch_size, edge_inc, src_map, dst_map)
             if path is not None and os.path.exists(path):
@@ -539,7 +541,7 @@ class PlanCache:
                     save_edge_plan(plan, path)
             if len(self._plans) > 16:
                 self._plans.clear()
-            self._plans[key] = plan
+            self._plans[key] = (plan, src_map, dst_map)
         return plan
 
 
@@ -625,6 +627,37 @@ class PackedWeights:
 
     def clear(self) -> None:
         self._store.clear()
+
+
+ROUTE_SWITCHES = ("ANEMOI_AMD_THIN", "ANEMOI_AMD_THIN_STATS", "ANEMOI_AMD_LN_FOLD", "ANEMOI_AMD_EMBED_FOLD", "ANEMOI_AMD_EDGE_RAW", "ANEMOI_AMD_EDGE_FOLD",
+                  "ANEMOI_AMD_F32_LINEAR", "ANEMOI_AMD_MXFP8")
+
+
+def enc_hoist_enabled() -> bool:
+    """The encoder's call-invariant destination side is built once per parameter state on the inference path
+    (``hoisted``).  ``ANEMOI_AMD_ENC_HOIST=0``: every forward recomputes it, bit for bit the same."""
+    return os.environ.get("ANEMOI_AMD_ENC_HOIST", "1") != "0" and not torch.is_grad_enabled()
+
+
+def hoisted(cache: PackedWeights, key, sources: Sequence[Optional[Tensor]], build: Callable[[], object]):
+    """``build()`` kept in ``cache`` while none of ``sources`` changes -- an ACTIVATION that depends on parameters and the graph
+    only (the mesh rows of the encoder), keyed like a packed weight plus the route switches.  ``sources`` must name every
+    tensor that enters, parameters of earlier stages included (``static_sources`` of an operand lists them): an intermediate
+    tensor alone is no key, its address can be handed out again once it is rebuilt."""
+    switches = tuple(os.environ.get(name) for name in ROUTE_SWITCHES)
+    # the entry holds the sources themselves: while it lives none of their addresses can be handed to another tensor, so an
+    # equal (pointer, version) IS the same tensor (the model root drops and rebuilds its mesh order on request, for one)
+    return cache.get(("hoist", key, switches), sources, lambda: ([s for s in sources if s is not None], build()))[1]
+
+
+def static_sources(t) -> Optional[list]:
+    """The tensors a hoisted operand was built from (``mark_static``), or None for an ordinary, per-call operand."""
+    return getattr(t, "_anemoi_static", None)
+
+
+def mark_static(t, sources: Sequence[Optional[Tensor]]):
+    t._anemoi_static = [s for s in sources if s is not None]
+    return t
 
 
 def edge_attr_csr_cached(cache: PackedWeights, edge_attr: Tensor, trainable: Optional[Tensor], plan, *layout) -> Tensor:

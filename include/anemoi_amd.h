@@ -821,6 +821,48 @@ typedef struct anemoi_linear_route_info {
 int anemoi_linear_route(const anemoi_linear_args* args, anemoi_linear_route_info* route);
 
 /*
+ * Thin Linear (csrc/gemm_thin.hip): y[M, N] = epilogue(x[M, K] W^T + b) for bf16 x and W whose weight is small enough to stay
+ * in the four waves' registers for the whole launch, while the rows of x stream through once (global -> VGPR in the MFMA
+ * operand layout, no LDS staging).  It is NOT part of the fused Linear family above: nothing of it goes through that
+ * family's plan, and anemoi_linear_route knows nothing of it.  Shapes (N, K) taken: (256, 64), (64, 256), (256, 256),
+ * (80, 1024), (16, 1024), (16, 256), (256, 128); any M >= 1.  Every other shape, and every combination named below as not taken, returns
+ * ANEMOI_ERR_UNSUPPORTED before anything is launched -- the caller then keeps the fused Linear family's route.
+ *
+ *   batch > 1: `batch` independent problems; problem b reads x + b stride_x, w + b stride_w, residual + b stride_r,
+ *     bias + b N and writes y + b stride_y (strides in elements: column blocks of one row-major matrix, as
+ *     anemoi_linear_batched takes them).  Not with colsum / stats / stats_out, and only for the shapes with K <= 256.
+ *   colsum + stats: the LayerNorm fold of anemoi_linear_ln, acc * stats[m].x + stats[m].y * colsum[n], before the bias.
+ *   residual (bf16): added after the result was rounded to bf16 when out_dtype is bf16 (round, add, round: the persistent
+ *     kernel's order); added in f32 when out_dtype is f32.
+ *   stats_out != NULL ("statistics only"): nothing is stored to y (y may be NULL); stats_out[m] = { rstd, -mean rstd } of
+ *     row m of the result as it WOULD be stored in out_dtype, by the two-pass formula of anemoi_row_stats with `eps`.
+ *     Not with a residual.
+ * Alignment: x, w, y, residual 16 bytes; ldx, stride_x, stride_w multiples of 8; ldy, stride_y (and ldr, stride_r)
+ * multiples of 8 (bf16) or 4 (f32); bias, colsum 16 bytes.  ANEMOI_ERR_INVALID otherwise.  x is read up to row M - 1 only
+ * and y written up to row M - 1 only.  No atomics: two calls give the same bits.  `struct_bytes` must be sizeof.
+ */
+typedef struct anemoi_linear_thin_args {
+  int64_t struct_bytes;
+  int32_t out_dtype; /* ANEMOI_BF16 / ANEMOI_F32 */
+  int32_t batch;     /* 0 or 1: one problem */
+  const void* x;
+  const void* w;
+  const float* bias;
+  const float* colsum;
+  const float* stats;
+  const void* residual;
+  void* y;
+  float* stats_out;
+  int64_t ldx, ldr, ldy, M;
+  int32_t N, K;
+  int64_t stride_x, stride_w, stride_y, stride_r;
+  float eps;
+  int32_t reserved;
+} anemoi_linear_thin_args;
+
+int anemoi_linear_thin(const anemoi_linear_thin_args* args, anemoi_stream_t stream);
+
+/*
  * LayerNorm backward from the forward's row statistics (stats [rows, 2] = { rstd, -mean * rstd }, anemoi_row_stats):
  *   dx = rstd * (g - mean_c(g) - xhat * mean_c(g * xhat)), g = dy * gamma, xhat = x * rstd - mean * rstd;
  *   dgamma[c] = sum_r dy * xhat, dbeta[c] = sum_r dy (f32).  workspace: anemoi_layer_norm_backward_workspace_floats.
