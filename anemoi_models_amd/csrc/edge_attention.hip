@@ -241,7 +241,7 @@ struct EdgeFoldParams {
   int stream_hint;  // 1: q / x_r / out are nontemporal so that they do not evict gathered k|v rows from the XCD's L2
 };
 
-template <typename T, int VEC, int LPH, int UP, int U = 4>
+template <typename T, int VEC, int LPH, int UP, int U = 4, bool XR = true>
 __global__ __launch_bounds__(256) void gt_edge_attention_folded_kernel(const EdgeFoldParams p,
                                                                    const float* __restrict__ attr_,
                                                                    const int32_t* __restrict__ rowptr_,
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(256) void gt_edge_attention_folded_kernel(const Edg
       // x_r is requested here, with q, not behind the edge loop where it is consumed: one dependent HBM round trip per
       // destination less (-2 %; requesting the NEXT destination's rows ahead as well was measured and is slower, see
       // DESIGN.md section 4.2)
-      if (p.xr != nullptr) xr_raw.load(static_cast<const char*>(p.xr) + node * p.ldr * (int64_t)sizeof(T),
+      if (XR && p.xr != nullptr) xr_raw.load(static_cast<const char*>(p.xr) + node * p.ldr * (int64_t)sizeof(T),
                                        (uint32_t)(c0 * (int)sizeof(T)), p.stream_hint != 0);
 #pragma unroll
       for (int i = 0; i < APL; ++i) u[i] *= amask;
@@ -360,7 +360,7 @@ __global__ __launch_bounds__(256) void gt_edge_attention_folded_kernel(const Edg
     float o[VEC];
 #pragma unroll
     for (int i = 0; i < VEC; ++i) o[i] = acc[i >> 1][i & 1] * inv;
-    if (p.xr != nullptr) {
+    if (XR && p.xr != nullptr) {
       float r[VEC];
       xr_raw.get(r);
 #pragma unroll
@@ -395,6 +395,15 @@ static void launch_folded(const EdgeFoldParams& p, hipStream_t st) {
   // (a register-double-buffered software pipeline across destinations was measured and removed: 0.30 / 1.98 / 0.79 ms
   // against 0.19 / 1.21 / 0.60 ms of this loop on the mesh / decoder / encoder graphs of config 3 -- the second
   // register set costs a wave per SIMD, which hurts more than the overlap helps)
+  // no x_r (the decoder fold: x_r rides in the projection product): the bf16 instantiation without the
+  // operand -- no load, no add, no registers held for it.  With x_r the kernel is the one it always was.
+  if constexpr (std::is_same<T, bf16_t>::value) {
+    if (p.xr == nullptr) {
+      hipLaunchKernelGGL((gt_edge_attention_folded_kernel<T, VEC, LPH, UP, 4, false>), dim3((unsigned)(8 * bpx)),
+                         dim3(64 * WPB), 0, st, p, p.attr, p.rowptr, p.col);
+      return;
+    }
+  }
   hipLaunchKernelGGL((gt_edge_attention_folded_kernel<T, VEC, LPH, UP, 4>), dim3((unsigned)(8 * bpx)), dim3(64 * WPB), 0,
                      st, p, p.attr, p.rowptr, p.col);
 }
@@ -1043,7 +1052,7 @@ static int launch_folded_tiles(const EdgeFoldParams& p, const EdgeTileLists& tl,
 // terms of a destination are summed in canonical order (the plain kernel: CSR order): same result up to f32 rounding,
 // deterministic.  All three scores are in registers at once: exact maximum first, no online rescale.
 // ---------------------------------------------------------------------------------------------
-template <typename T, int VEC, int LPH, int UP, int MAXRUN>
+template <typename T, int VEC, int LPH, int UP, int MAXRUN, bool XR = true>
 __global__ __launch_bounds__(256) void gt_edge_attention_folded_runs_kernel(const EdgeFoldParams p,
                                                                         const float* __restrict__ attr_,
                                                                         const int32_t* __restrict__ run_ptr_,
@@ -1106,7 +1115,7 @@ __global__ __launch_bounds__(256) void gt_edge_attention_folded_runs_kernel(cons
         else VecIO<T, VEC>::load(qb + node * p.ldq, qf);
         qk[d].set(qf);
         VecIO<T, APL>::load(ub + node * p.ldu, u[d]);
-        if (p.xr != nullptr) xr_raw[d].load(static_cast<const char*>(p.xr) + node * p.ldr * (int64_t)sizeof(T),
+        if (XR && p.xr != nullptr) xr_raw[d].load(static_cast<const char*>(p.xr) + node * p.ldr * (int64_t)sizeof(T),
                                             (uint32_t)(c0 * (int)sizeof(T)), p.stream_hint != 0);
 #pragma unroll
         for (int sl = 0; sl < 3; ++sl)
@@ -1149,7 +1158,7 @@ __global__ __launch_bounds__(256) void gt_edge_attention_folded_runs_kernel(cons
         float o[VEC];
 #pragma unroll
         for (int i = 0; i < VEC; ++i) o[i] = acc[i >> 1][i & 1] * inv;
-        if (p.xr != nullptr) {
+        if (XR && p.xr != nullptr) {
           float r[VEC];
           xr_raw[d].get(r);
 #pragma unroll
@@ -1184,8 +1193,12 @@ static void launch_folded_runs(const EdgeFoldParams& p, const int32_t* run_ptr, 
   if (bpx > 32 * wgs_per_cu) bpx = 32 * wgs_per_cu;
   if (bpx < 1) bpx = 1;
   while ((bpx * WPB) % p.n_slices != 0) ++bpx;
-  hipLaunchKernelGGL((gt_edge_attention_folded_runs_kernel<T, VEC, LPH, UP, EDGE_MAX_RUN>), dim3((unsigned)(8 * bpx)),
-                     dim3(64 * WPB), 0, st, p, p.attr, run_ptr, p.col, perm, n_runs);
+  if (p.xr == nullptr)  // (the instantiation without the operand, as in launch_folded)
+    hipLaunchKernelGGL((gt_edge_attention_folded_runs_kernel<T, VEC, LPH, UP, EDGE_MAX_RUN, false>), dim3((unsigned)(8 * bpx)),
+                       dim3(64 * WPB), 0, st, p, p.attr, run_ptr, p.col, perm, n_runs);
+  else
+    hipLaunchKernelGGL((gt_edge_attention_folded_runs_kernel<T, VEC, LPH, UP, EDGE_MAX_RUN>), dim3((unsigned)(8 * bpx)),
+                       dim3(64 * WPB), 0, st, p, p.attr, run_ptr, p.col, perm, n_runs);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1202,7 +1215,7 @@ static void launch_folded_runs(const EdgeFoldParams& p, const int32_t* run_ptr, 
 // operation (canonical source order, exact maximum, no online rescale): bit-identical results.
 // ---------------------------------------------------------------------------------------------
 constexpr int EDGE_MAX_GROUP = 8;
-template <typename T, int VEC, int LPH, int UP>
+template <typename T, int VEC, int LPH, int UP, bool XR = true>
 __global__ __launch_bounds__(256) void gt_edge_attention_folded_groups3_kernel(const EdgeFoldParams p,
                                                                            const float* __restrict__ attr_,
                                                                            const int32_t* __restrict__ col_,
@@ -1262,7 +1275,7 @@ __global__ __launch_bounds__(256) void gt_edge_attention_folded_groups3_kernel(c
     r.q = __builtin_amdgcn_raw_buffer_load_b128(qrs, lane_off, (int)((uint32_t)node * q_row_bytes), 2);
     buffer_load_words<RawWords<T, APL>::W>(urs, u_off, (int)((uint32_t)node * u_row_bytes), r.u.w);
     r.xr = u32x4_t{0u, 0u, 0u, 0u};
-    if (p.xr != nullptr) r.xr = __builtin_amdgcn_raw_buffer_load_b128(xrs, lane_off, (int)((uint32_t)node * xr_row_bytes), 2);
+    if (XR && p.xr != nullptr) r.xr = __builtin_amdgcn_raw_buffer_load_b128(xrs, lane_off, (int)((uint32_t)node * xr_row_bytes), 2);
 #pragma unroll
     for (int sl = 0; sl < 3; ++sl)
       buffer_load_f32<APL>(ars, attr_off, (int)((uint32_t)(3 * node + ((pm >> (2 * sl)) & 3)) * (uint32_t)(UP * 4)), r.at[sl]);
@@ -1356,7 +1369,7 @@ __global__ __launch_bounds__(256) void gt_edge_attention_folded_groups3_kernel(c
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
           const float scaled = acc[i >> 1][i & 1] * inv;
-          o[i] = p.xr != nullptr ? scaled + r[i] : scaled;
+          o[i] = (XR && p.xr != nullptr) ? scaled + r[i] : scaled;
         }
       }
       const int out_row = (int)((uint32_t)node * o_row_bytes);
@@ -1398,8 +1411,12 @@ static void launch_folded_groups3(const EdgeFoldParams& p, const int32_t* grp_pt
   if (bpx > 32 * wgs_per_cu) bpx = 32 * wgs_per_cu;
   if (bpx < 1) bpx = 1;
   while ((bpx * WPB) % p.n_slices != 0) ++bpx;
-  hipLaunchKernelGGL((gt_edge_attention_folded_groups3_kernel<T, VEC, LPH, UP>), dim3((unsigned)(8 * bpx)), dim3(64 * WPB), 0,
-                     st, p, p.attr, p.col, grp_ptr, grp_dst, grp_perm, n_groups);
+  if (p.xr == nullptr)  // (the instantiation without the operand, as in launch_folded)
+    hipLaunchKernelGGL((gt_edge_attention_folded_groups3_kernel<T, VEC, LPH, UP, false>), dim3((unsigned)(8 * bpx)),
+                       dim3(64 * WPB), 0, st, p, p.attr, p.col, grp_ptr, grp_dst, grp_perm, n_groups);
+  else
+    hipLaunchKernelGGL((gt_edge_attention_folded_groups3_kernel<T, VEC, LPH, UP>), dim3((unsigned)(8 * bpx)), dim3(64 * WPB), 0,
+                       st, p, p.attr, p.col, grp_ptr, grp_dst, grp_perm, n_groups);
 }
 
 template <typename T, int VEC, int LPH>

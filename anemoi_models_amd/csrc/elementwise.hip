@@ -405,6 +405,31 @@ __global__ __launch_bounds__(256) void row_scale_kernel(const T* x, int64_t ldx,
   }
 }
 
+// out[r, 0:cols] = stats[r, 0] * x[r, :] (the f32 product rounded once), out[r, cols:2 cols] = x[r, :]: the raw-row blocks the
+// decoder's projection product reads behind out | t.  One 16-byte piece of x per thread, read once and
+// stored twice; the host admits only shapes that are whole 16-byte pieces.
+template <typename T>
+__global__ __launch_bounds__(256) void raw_row_tail_kernel(const T* __restrict__ x, int64_t ldx,
+                                                           const float* __restrict__ stats, T* __restrict__ out,
+                                                           int64_t ldo, int64_t rows, int cols) {
+  constexpr int VEC = 16 / sizeof(T);
+  const int64_t per_row = cols / VEC;
+  const int64_t total = rows * per_row;
+  const bool fits32 = total < ((int64_t)1 << 31);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    int64_t r, piece;
+    fast_divmod(i, per_row, fits32, r, piece);
+    const int c = (int)piece * VEC;
+    const float f = stats[2 * r];
+    float v[VEC], sv[VEC];
+    VecIO<T, VEC>::load(x + r * ldx + c, v);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) sv[k] = v[k] * f;
+    VecIO<T, VEC>::store(out + r * ldo + c, sv);
+    VecIO<T, VEC>::store(out + r * ldo + cols + c, v);
+  }
+}
+
 // out[r] = sum_c a[r, c] * (b[r, c] - shift[c])   (f32; one wave per row, 16 bytes per lane and step)
 template <typename T>
 __global__ __launch_bounds__(256) void row_dot_kernel(const T* __restrict__ a, int64_t lda, const T* __restrict__ b,
@@ -770,6 +795,26 @@ int anemoi_row_scale(int dtype, const void* x, int64_t ldx, const float* s, floa
   else
     return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_row_scale: dtype %d", dtype);
   return trail::note(check_launch("anemoi_row_scale"), "anemoi_row_scale", "out", dtype, out, ldo, rows, cols, st);
+}
+
+int anemoi_raw_row_tail(int dtype, const void* x, int64_t ldx, const float* stats, void* out, int64_t ldo, int64_t rows,
+                        int cols, anemoi_stream_t stream) {
+  ANEMOI_REQUIRE(x && stats && out && rows >= 0 && cols >= 0 && ldx >= cols && ldo >= 2 * (int64_t)cols, ANEMOI_ERR_INVALID,
+                 "anemoi_raw_row_tail: bad argument");
+  ANEMOI_REQUIRE(dtype == ANEMOI_F32 || dtype == ANEMOI_BF16, ANEMOI_ERR_UNSUPPORTED, "anemoi_raw_row_tail: dtype %d", dtype);
+  const int vec = dtype == ANEMOI_F32 ? 4 : 8;
+  ANEMOI_REQUIRE(cols % vec == 0 && ldx % vec == 0 && ldo % vec == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)out % 16 == 0,
+                 ANEMOI_ERR_UNSUPPORTED, "anemoi_raw_row_tail: rows must be whole, aligned 16-byte pieces");
+  if (rows * cols == 0) return ANEMOI_OK;
+  hipStream_t st = as_stream(stream);
+  dim3 grid(flat_grid(rows * (cols / vec))), block(256);
+  if (dtype == ANEMOI_F32)
+    hipLaunchKernelGGL((raw_row_tail_kernel<float>), grid, block, 0, st, static_cast<const float*>(x), ldx, stats,
+                       static_cast<float*>(out), ldo, rows, cols);
+  else
+    hipLaunchKernelGGL((raw_row_tail_kernel<bf16_t>), grid, block, 0, st, static_cast<const bf16_t*>(x), ldx, stats,
+                       static_cast<bf16_t*>(out), ldo, rows, cols);
+  return trail::note(check_launch("anemoi_raw_row_tail"), "anemoi_raw_row_tail", "out", dtype, out, ldo, rows, 2 * cols, st);
 }
 
 int anemoi_row_dot(int dtype, const void* a, int64_t lda, const void* b, int64_t ldb, const float* shift, float* out,

@@ -51,12 +51,12 @@ def _as_compute(x: Tensor, dtype: torch.dtype) -> Tensor:
 
 
 def folded_edge_phase(q: Tensor, k: Tensor, v: Tensor, x_r: Optional[Tensor], u: Tensor, edge_attr_csr: Tensor, plan,
-                      num_heads: int, up: int, ld_out: Optional[int] = None) -> Tensor:
+                      num_heads: int, up: int, ld_out: Optional[int] = None, out: Optional[Tensor] = None) -> Tensor:
     """The folded edge phase (``anemoi_gt_edge_attention_folded``: one fused gather -> score -> segment softmax -> weighted
-    sum -> ``+ x_r`` pass over the destination-sorted CSR)."""
+    sum -> ``+ x_r`` pass over the destination-sorted CSR).  ``out``: the caller's buffer (only ``out | t`` is written)."""
     lists = runtime.edge_lists(plan, q.dtype, q.shape[-1], num_heads, up)
-    return ops.gt_edge_attention_folded(q, k, v, x_r, u, edge_attr_csr, plan.rowptr, plan.col, num_heads, up, ld_out=ld_out,
-                                        **lists._asdict())
+    return ops.gt_edge_attention_folded(q, k, v, x_r, u, edge_attr_csr, plan.rowptr, plan.col, num_heads, up, out=out,
+                                        ld_out=ld_out, **lists._asdict())
 
 
 class EmbeddedRows:
@@ -646,6 +646,13 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
         kv_layers, sq_layers = [self.lin_key, self.lin_value], [self.lin_self, self.lin_query]
         kv_args = ("kv", lambda: self._cat_linear("kv", kv_layers, dtype), lambda: self._cat_rows(kv_layers),
                    [l.weight for l in kv_layers] + [l.bias for l in kv_layers])
+        if isinstance(x_dst, EmbeddedRows) and x_dst.h is None:
+            # destination rows handed over without their embedding (the backward mapper, when dec_fold_route holds)
+            if (isinstance(x_src, EmbeddedRows) or halo is not None
+                    or not self.dec_fold_route(dtype, x_dst.x_aug.shape[1], num_chunks)):
+                raise ValueError("destination rows without their embedding need the decoder fold (dec_fold_route)")
+            kv = self._ln_linear(self._ln_begin(self.layer_norm1, x_src), *kv_args)
+            return x_src, self._native_dec_fold(kv, x_dst, edge_attr_csr, plan, out_stats_eps)
         xs = self._ln_begin(self.layer_norm1, x_src)
         raw = None if (halo is not None or num_chunks > 1 or mx) else self._raw_source_weights(x_src, dtype)
         if raw is not None:
@@ -781,6 +788,60 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
         del g
         del sq
         y = runtime.linear(att, wp, bp, residual=h_dst, stats_eps=self._mlp_ln_eps("dst", dtype))
+        del att
+        return self._node_mlp(y, "dst", 1, out_stats_eps=out_stats_eps)
+
+    # ---- destinations given as raw rows: x_r and the embedded rows ride in the projection product
+    def dec_fold_route(self, dtype, k_pad: int, num_chunks: int = 1) -> bool:
+        """Whether this block takes destination rows as ``EmbeddedRows`` WITHOUT ``h`` (``k_pad`` raw columns): bf16 inference
+        in one chunk on the ``lin_edge`` fold, ``ANEMOI_AMD_DEC_FOLD`` not 0, the raw width one of 64 / 128 / 256 and
+        ``out | t`` a whole number of K slabs (the raw blocks start right behind them).  The caller (the backward mapper)
+        asks before it decides not to materialise the embedding.  Not with MXFP8, and not with the opt-in thin statistics site
+        (``ANEMOI_AMD_THIN_STATS=1``): without ``h`` the rows' statistics come from the side product of ``EmbeddedRows.stats``,
+        which that switch would move to the slower kernel on every grid row (and an existing launch-list test pins the
+        decoder's list under it)."""
+        if (not runtime.dec_fold_enabled() or dtype != torch.bfloat16 or num_chunks > 1 or self.update_src_nodes
+                or runtime.mxfp8_enabled(dtype) or not runtime.embed_fold_enabled(dtype) or k_pad not in (64, 128, 256)
+                or os.environ.get("ANEMOI_AMD_THIN_STATS", "0") == "1"):
+            return False
+        up = self.fold_width(dtype)
+        return up is not None and (self.num_heads * (self.out_channels_conv + up)) % ops.k_multiple(dtype) == 0
+
+    def _dec_fold_weights(self, x_dst: EmbeddedRows, dtype, up: int):
+        """Packed ``[W_p | W_t | W_p A_s | E]`` + f32 bias of ``runtime.compose_decoder_fold``, rebuilt when any parameter that
+        enters changes (pointer, in-place version, device)."""
+        ln, emb, ks = self.layer_norm2, x_dst.emb, x_dst.x_aug.shape[1]
+        params = [self.projection.weight, self.projection.bias, self.lin_edge.weight, self.lin_edge.bias, self.lin_self.weight,
+                  self.lin_self.bias, ln.weight, ln.bias, emb.weight, emb.bias]
+        return self._packed.get(
+            ("projf", "decfold", dtype, up, ks, x_dst.one_col, x_dst._tag), params,
+            lambda: runtime.compose_decoder_fold(self.projection.weight, self.projection.bias, self._projection_fold(up),
+                                                 self.lin_self.weight, self.lin_self.bias, ln.weight, ln.bias, emb.weight,
+                                                 emb.bias, ks, x_dst.one_col, dtype))
+
+    def _native_dec_fold(self, kv: Tensor, x_dst: EmbeddedRows, edge_attr_csr: Tensor, plan,
+                         out_stats_eps: Optional[float]) -> Tensor:
+        """The block on raw destination rows ``x``: ``q | u`` from the LayerNorm-folded product (no ``x_r`` rows), the folded
+        edge kernel without ``x_r``, ``rstd x | x`` written behind ``out | t``, and ONE projection product over
+        ``[out | t | rstd x | x]`` that carries ``W_p x_r`` and the residual ``emb(x)`` -- neither is ever formed.  Node MLP
+        unchanged."""
+        dtype = x_dst.dtype
+        c, h, ln = self.num_heads * self.out_channels_conv, self.num_heads, self.layer_norm2
+        up = self.fold_width(dtype)
+        xa = x_dst.x_aug
+        stats = x_dst.stats(ln.eps)
+        q_layers = [self.lin_query]
+        qu = self._ln_linear((x_dst, stats, ln), "qu", None, lambda: self._folded_rows(q_layers, up),
+                             self._fold_params(q_layers))  # [N_dst, C + H*up] = q | u
+        w, b = self._dec_fold_weights(x_dst, dtype, up)
+        width, k_att = c + h * up, c + h * up + 2 * xa.shape[1]
+        att = torch.empty((xa.shape[0], w.shape[1]), dtype=dtype, device=xa.device)
+        if w.shape[1] > k_att:
+            att[:, k_att:].zero_()
+        folded_edge_phase(qu[:, :c], kv[:, :c], kv[:, c:], None, qu[:, c:], edge_attr_csr, plan, h, up, out=att)
+        del qu, kv
+        ops.raw_row_tail(xa, stats, att[:, width:k_att])
+        y = runtime.linear(att, w, b, stats_eps=self._mlp_ln_eps("dst", dtype))
         del att
         return self._node_mlp(y, "dst", 1, out_stats_eps=out_stats_eps)
 

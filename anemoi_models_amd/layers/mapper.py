@@ -157,7 +157,7 @@ class GraphTransformerBaseMapper(GraphEdgeMixin, BaseMapper):
         self._plans = runtime.PlanCache()
 
     # ---- hooks specialised by the forward / backward mapper ------------------------------------
-    def _embed(self, x_src: Tensor, x_dst: Tensor, one_cols=(None, None), dst_static: bool = False):
+    def _embed(self, x_src: Tensor, x_dst: Tensor, one_cols=(None, None), dst_static: bool = False, dst_fold: bool = False):
         return x_src, x_dst  # the base mapper embeds nothing (reference BaseMapper.pre_process, layers/mapper.py:87-96)
 
     def _embedded(self, tag: str, lin: nn.Linear, x: Tensor, eps: Optional[float], one_col: Optional[int],
@@ -217,7 +217,8 @@ class GraphTransformerBaseMapper(GraphEdgeMixin, BaseMapper):
         ea = runtime.edge_attr_csr_cached(self._packed, self.edge_attr, self.trainable.trainable, plan,
                                           *self.proc.edge_layout(x_dst.dtype))
         num_chunks = self.proc.num_chunks if self.training else inference_num_chunks()
-        h_src, h_dst = self._embed(x_src, x_dst, one_cols, dst_static=num_chunks <= 1 and runtime.enc_hoist_enabled())
+        h_src, h_dst = self._embed(x_src, x_dst, one_cols, dst_static=num_chunks <= 1 and runtime.enc_hoist_enabled(),
+                                   dst_fold=num_chunks <= 1)
         _, h_dst = self.proc.native(h_src, h_dst, ea, plan, num_chunks, out_stats_eps=self._extract_ln_eps(h_dst.dtype))
         return self._extract(h_dst, out_dtype)
 
@@ -292,7 +293,7 @@ class GraphTransformerForwardMapper(ForwardMapperPreProcessMixin, GraphTransform
                          src_grid_size=src_grid_size, dst_grid_size=dst_grid_size)
         self.emb_nodes_src = nn.Linear(self.in_channels_src, self.hidden_dim)
 
-    def _embed(self, x_src: Tensor, x_dst: Tensor, one_cols=(None, None), dst_static: bool = False):
+    def _embed(self, x_src: Tensor, x_dst: Tensor, one_cols=(None, None), dst_static: bool = False, dst_fold: bool = False):
         eps1, eps2 = self._block_ln_eps(x_src.dtype)  # the embeddings enter the block's layer_norm1 / layer_norm2
         # source rows feed k | v only: their embedding is never written out when it can be folded away
         return (self._embedded("emb_nodes_src", self.emb_nodes_src, x_src, eps1, one_cols[0],
@@ -333,9 +334,15 @@ class GraphTransformerBackwardMapper(BackwardMapperPostProcessMixin, GraphTransf
         return (x_src, self._apply_module(self.emb_nodes_dst, x_dst), change_channels_in_shape(shapes_src, self.hidden_dim),
                 change_channels_in_shape(shapes_dst, self.hidden_dim))
 
-    def _embed(self, x_src: Tensor, x_dst: Tensor, one_cols=(None, None), dst_static: bool = False):
-        return x_src, self._embedded("emb_nodes_dst", self.emb_nodes_dst, x_dst, self._block_ln_eps(x_dst.dtype)[1],
-                                     one_cols[1], materialise=True)  # (the grid rows carry input data: never static)
+    def _embed(self, x_src: Tensor, x_dst: Tensor, one_cols=(None, None), dst_static: bool = False, dst_fold: bool = False):
+        # The embedded grid rows are only the projection's residual and the input of x_r | q | u: where the block folds both
+        # into its projection product (``dst_fold``: the one-chunk, one-rank forward; the block's ``dec_fold_route``) they
+        # are not formed.  (The grid rows carry input data: never static.)
+        lin = self.emb_nodes_dst
+        k_pad = x_dst.shape[1] if one_cols[1] is not None else ops.round_up(lin.in_features + 1, ops.k_multiple(x_dst.dtype))
+        fold = dst_fold and x_dst.is_cuda and self.proc.dec_fold_route(x_dst.dtype, k_pad)
+        return x_src, self._embedded("emb_nodes_dst", lin, x_dst, self._block_ln_eps(x_dst.dtype)[1], one_cols[1],
+                                     materialise=not fold)
 
     def _extract(self, x_dst: Tensor, out_dtype) -> Tensor:
         ln, lin = self.node_data_extractor[0], self.node_data_extractor[1]

@@ -1451,6 +1451,25 @@ def row_scale(x: Tensor, s: Tensor, alpha: float = 1.0, out: Optional[Tensor] = 
     return out
 
 
+def raw_row_tail(x: Tensor, stats: Tensor, out: Tensor) -> Tensor:
+    """``out[:, :K] = stats[:, 0, None] * x`` (f32 product, one rounding) and ``out[:, K:2K] = x`` -- the two raw-row blocks of
+    the decoder fold's projection operand (``out``: a ``[rows, 2K]`` column view of the attention buffer).  ``stats``: the
+    contiguous f32 ``[rows, 2]`` LayerNorm statistics of the rows.  Recorded as a ``row_scale`` launch."""
+    _dev(x, stats, out)
+    rows, cols = _rows(x).shape
+    if stats.dtype != torch.float32 or tuple(stats.shape) != (rows, 2) or not stats.is_contiguous():
+        raise ValueError("raw_row_tail: stats must be the contiguous [rows, 2] f32 result of row_stats")
+    if out.dtype != x.dtype or tuple(_rows(out).shape) != (rows, 2 * cols):
+        raise ValueError("raw_row_tail: out must be a [rows, 2 * cols] view in x's dtype")
+    if rows == 0:
+        return out
+    with _Timed("row_scale", bytes=3 * rows * cols * x.element_size(), raw_tail=True):
+        st = _lib.load().anemoi_raw_row_tail(dtype_code(x.dtype), x.data_ptr(), _ld(x), stats.data_ptr(), out.data_ptr(),
+                                             _ld(out), rows, cols, _stream())
+    _lib.check(st, "anemoi_raw_row_tail")
+    return out
+
+
 def _fused_epilogue_rows(dtype, m: int, n: int, k: int, ldx: int, ldp: int = 0) -> int:
     """Rows that ``linear_dual`` / ``linear_actgrad`` hand to the persistent kernel's DUAL / GMUL epilogue (``ldp``: pitch of the
     saved pre-activation, 0 where the call allocates it): the whole 256-row tiles of a bf16 product the library takes, from

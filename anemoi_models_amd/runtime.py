@@ -875,6 +875,40 @@ def fold_embedded_layer_norm(w_rows: Tensor, bias: Optional[Tensor], gamma: Tens
             torch.zeros(w.shape[0], dtype=torch.float32, device=w.device))
 
 
+def dec_fold_enabled() -> bool:
+    """The decoder's destination ``x_r`` and the embedded grid rows ride in the projection product on the inference path
+    (``compose_decoder_fold``).  ``ANEMOI_AMD_DEC_FOLD=0``: the separate launches, bit for bit."""
+    return os.environ.get("ANEMOI_AMD_DEC_FOLD", "1") != "0" and not torch.is_grad_enabled()
+
+
+def compose_decoder_fold(proj_w: Tensor, proj_b: Optional[Tensor], w_t: Tensor, self_w: Tensor, self_b: Optional[Tensor],
+                         gamma: Tensor, beta: Tensor, emb_w: Tensor, emb_b: Optional[Tensor], k_pad: int, one_col: int,
+                         dtype: torch.dtype):
+    """The mapper block's projection with ``x_r = lin_self(LN(emb(x)))`` and the residual ``emb(x)`` folded in, on destination
+    rows given as raw features ``x_aug = [x | 1 | 0-pad]`` (``k_pad`` columns, the constant 1 in ``one_col``):
+
+        W_p (S + x_r) + W_t t + b_p + emb(x) = [W_p | W_t | W_p A_s | E] [S | t | rstd x_aug | x_aug] + (b_p + W_p b_s + b_E),
+
+    with ``x_r = rstd A_s x_aug + b_s`` the operator of :func:`fold_embedded_layer_norm` (the LayerNorm's mean is gone
+    algebraically, ``rstd`` is its row statistic) and ``E`` the embedding's weight, zero in the padding columns -- its bias
+    stays in the f32 bias.  ``w_t``: the ``lin_edge`` columns of the projection (``_projection_fold``).  Returns ``(W [N, K]
+    in dtype, K = C + H up + 2 k_pad padded to the K-slab multiple, products in f64 and ONE rounding; bias [N] f32)``."""
+    wp = proj_w.detach().double()
+    a_s, b_s, _ = fold_embedded_layer_norm(self_w, self_b, gamma, beta, emb_w, emb_b, k_pad, one_col, torch.float64)
+    k_in = emb_w.shape[1]
+    e = torch.zeros((emb_w.shape[0], k_pad), dtype=torch.float64, device=wp.device)
+    e[:, :k_in] = emb_w.detach().double()
+    w = torch.cat([wp, w_t.detach().double(), wp @ a_s, e], dim=1)
+    k = w.shape[1]
+    out = torch.zeros((w.shape[0], ops.round_up(k, ops.k_multiple(dtype))), dtype=dtype, device=w.device)
+    out[:, :k] = w.to(dtype)
+    b = wp @ b_s.double()
+    for extra in (proj_b, emb_b):
+        if extra is not None:
+            b = b + extra.detach().double()
+    return out, b.float().contiguous()
+
+
 def embedding_stats_operator(emb_w: Tensor, emb_b: Optional[Tensor], k_pad: int, one_col: int, dtype: torch.dtype):
     """``T [n, k_pad]`` (n = a multiple of 256) such that ``y = T x_aug`` has, per row, mean 0 and
     ``sum(y^2) / n == |E_c x + b_c|^2 / C``: the LayerNorm variance of the embedded row ``E x + b_e`` without forming it.

@@ -726,6 +726,14 @@ int anemoi_row_dot(int dtype, const void* a, int64_t lda, const void* b, int64_t
 int anemoi_row_scale(int dtype, const void* x, int64_t ldx, const float* s, float alpha, void* out, int64_t ldo,
                      int64_t rows, int cols, anemoi_stream_t stream);
 
+/* out[r, 0:cols] = stats[r, 0] * x[r, :] (f32 product, one rounding), out[r, cols:2 cols] = x[r, :] -- stats the [rows, 2] f32
+ * LayerNorm statistics {rstd, -mean rstd} of the rows.  The two raw-row blocks the decoder's projection product reads behind
+ * out | t of the folded edge phase when x_r and the embedded grid rows are folded into it (layers/block.py::_native_dec_fold,
+ * DESIGN.md section 4.2).  Whole 16-byte pieces only (cols, ldx, ldo multiples of 16 bytes, aligned pointers), ldo >= 2 cols;
+ * anything else is ANEMOI_ERR_UNSUPPORTED before any launch.  Additive: the ABI version is unchanged. */
+int anemoi_raw_row_tail(int dtype, const void* x, int64_t ldx, const float* stats, void* out, int64_t ldo, int64_t rows,
+                        int cols, anemoi_stream_t stream);
+
 /* out = act(pre) (+ residual): the differentiable forward keeps `pre` for act' and applies the activation in one pass. */
 int anemoi_act_forward(int dtype, int act, const void* pre, int64_t ldp, const void* residual, int64_t ldr, void* out,
                        int64_t ldo, int64_t rows, int cols, anemoi_stream_t stream);
