@@ -15,6 +15,7 @@ from __future__ import annotations
 import os
 from abc import ABC
 from abc import abstractmethod
+from typing import NamedTuple
 from typing import Optional
 
 import torch
@@ -96,9 +97,40 @@ class EmbeddedRows:
         # them.  Measured slower than the persistent kernel + finalize at config 3 (0.189 against 0.132 ms: four waves share a
         # row block and meet at two barriers per block, profiles/r11_thin_hoist.md), so this site is opt-in:
         # ANEMOI_AMD_THIN_STATS=1 (under ANEMOI_AMD_THIN).
-        thin = ops.thin_enabled() and os.environ.get("ANEMOI_AMD_THIN_STATS", "0") == "1"
+        thin = ops.thin_enabled() and runtime.thin_stats_enabled()
         st = ops.linear_thin(self.x_aug, t, stats_eps=eps) if thin else None
         return st if st is not None else ops.row_stats(runtime.linear(self.x_aug, t, None, stats_eps=eps), eps)
+
+
+class Rows(NamedTuple):
+    """What the route decision (``GraphTransformerMapperBlock.route``) knows of one node set before anything is launched.
+    ``kind``: ``"tensor"`` (plain rows), ``"embedded"`` (``EmbeddedRows`` with ``h``) or ``"raw"`` (``EmbeddedRows`` that come,
+    or -- when a mapper asks before it embeds -- could come, without ``h``).  The other fields describe ``EmbeddedRows``:
+    raw width, constant-1 column, the embedding's ``in_features``."""
+
+    kind: str = "tensor"
+    k_pad: int = 0
+    one_col: int = 0
+    in_features: int = 0
+    on_gpu: bool = False
+
+    @classmethod
+    def of(cls, x) -> "Rows":
+        if not isinstance(x, EmbeddedRows):
+            return cls("tensor", on_gpu=x.is_cuda)
+        return cls("embedded" if x.h is not None else "raw", x.x_aug.shape[1], x.one_col, x.emb.in_features, x.x_aug.is_cuda)
+
+
+class Route(NamedTuple):
+    """Result of ``GraphTransformerMapperBlock.route`` (DESIGN.md section 4.2 has the table of routes)."""
+
+    name: str  # "dec_fold" | "raw_sources" | "folded" | "unfolded"
+    up: Optional[int]  # per-head width of the lin_edge fold (``fold_width``), None on the unfolded route
+    mx: bool  # the destination nodes' MLP on MXFP8
+    chunked: bool  # node MLPs in row chunks; no LayerNorm statistics on the projection's epilogue
+    block_tail: bool  # ``anemoi_gt_block_tail`` may run edge phase, projection and node MLP (``_block_tail`` can still refuse)
+    src_h: bool  # the route reads the embedded source rows ``h``
+    dst_h: bool  # ... the embedded destination rows
 
 
 class BaseBlock(nn.Module, ABC):
@@ -156,8 +188,7 @@ class GraphTransformerBaseBlock(BaseBlock, ABC):
             )
         self._packed = runtime.PackedWeights()
         self._plans = runtime.PlanCache()
-        self._dst_mlp: Optional[NativeSequential] = None
-        self._src_mlp: Optional[NativeSequential] = None
+        self._mlps: dict = {}  # "dst" / "src" -> NativeSequential (``_native_mlp``)
 
     # ---- the reference's head / sequence re-sharding helpers (layers/block.py:366-414) -----------------
     def shard_qkve_heads(self, query: Tensor, key: Tensor, value: Tensor, edges: Tensor, shapes: tuple, batch_size: int,
@@ -203,17 +234,24 @@ class GraphTransformerBaseBlock(BaseBlock, ABC):
     # ---- LayerNorm -> Linear pairs: row statistics + anemoi_linear_ln (the normalised activation is never stored)
     @staticmethod
     def _ln_begin(ln: nn.LayerNorm, x: Tensor):
-        """Handle of ``LayerNorm(x)`` for ``_ln_linear``: ``(x, stats, ln)`` when folding, else ``(LN(x), None, None)``."""
+        """Handle of ``LayerNorm(x)`` for ``_ln_product``: ``(x, stats, ln)`` when folding, else ``(LN(x), None, None)``."""
         if isinstance(x, EmbeddedRows):
             return x, x.stats(ln.eps), ln
         if runtime.ln_fold_enabled(x.dtype):
             return x, ops.row_stats(x, ln.eps), ln
         return ops.layer_norm(x, runtime.f32c(ln.weight), runtime.f32c(ln.bias), ln.eps), None, None
 
-    def _ln_linear(self, handle, tag: str, plain, rows, params, **kw) -> Tensor:
-        """``Linear(LayerNorm(x))``.  ``plain()`` -> packed ``(w, b)`` of the unfolded route; ``rows()`` -> f32
-        ``(weight rows [N, K], bias [N] or None)`` that the fold scales by the LayerNorm weight (cached per dtype)."""
+    def _ln_product(self, handle, tag: str, layers, up: Optional[int] = None, **kw) -> Tensor:
+        """``Linear(LayerNorm(x))`` for the packed ``[layers..., W_u]`` (``up`` None: the layers alone), every product in
+        front of the edge phase: ``k | v``, ``x_r | q | u``, ``q | u``, the processor's ``x_r | q | k | v | u``, the unfolded
+        ``x_r | q`` -- cached under ``tag`` as the plain packed weight, its LayerNorm fold or its embedding + LayerNorm fold."""
         xin, stats, ln = handle
+        if up is None:
+            plain, rows = (lambda: self._cat_linear(tag, layers, xin.dtype)), (lambda: self._cat_rows(layers))
+            params = [l.weight for l in layers] + [l.bias for l in layers]
+        else:
+            plain, rows = (lambda: self._folded_in(tag, layers, xin.dtype, up)), (lambda: self._folded_rows(layers, up))
+            params = self._fold_params(layers)
         if isinstance(xin, EmbeddedRows):
             # embedding -> LayerNorm -> Linear as one product on the raw features (K = padded feature count, not C)
             xa = xin.x_aug
@@ -250,9 +288,9 @@ class GraphTransformerBaseBlock(BaseBlock, ABC):
     def fold_width(self, dtype) -> Optional[int]:
         """Per-head width ``up`` of the folded edge representation (``edge_dim`` attributes + the constant 1,
         rounded up to 4), or ``None`` when this shape has to use the unfolded kernel."""
-        if os.environ.get("ANEMOI_AMD_EDGE_FOLD", "1") == "0":
+        if not runtime.edge_fold_enabled():
             return None
-        vec = 16 // torch.empty((), dtype=dtype).element_size()
+        vec = 16 // dtype.itemsize  # (asked several times per forward, by ``route`` among others: no tensor for it)
         d, h = self.out_channels_conv, self.num_heads
         if d % vec != 0 or (d // vec) not in (1, 2, 4, 8, 16):
             return None
@@ -335,9 +373,7 @@ class GraphTransformerBaseBlock(BaseBlock, ABC):
         up = self.fold_width(dtype)
         if up is None or not runtime.ln_fold_enabled(dtype):
             return None
-        if self._dst_mlp is None:
-            self._dst_mlp = NativeSequential(self.node_dst_mlp)
-        mlp = self._dst_mlp.folded_pair(dtype)
+        mlp = self._native_mlp("dst").folded_pair(dtype)
         if mlp is None:
             return None
         ln = self.layer_norm1
@@ -362,18 +398,14 @@ class GraphTransformerBaseBlock(BaseBlock, ABC):
         if (ops.PROFILE is not None or dtype != torch.bfloat16 or not q.is_cuda or plan.num_edges == 0 or q.shape[0] == 0
                 or not self.block_abi or self._mlp_ln_eps("dst", dtype) is None):
             return None
-        if self._dst_mlp is None:
-            self._dst_mlp = NativeSequential(self.node_dst_mlp)
-        mlp = self._dst_mlp.folded_pair(dtype)
+        mlp = self._native_mlp("dst").folded_pair(dtype)
         if mlp is None or not (res.dim() == 2 and res.stride(1) == 1):
             return None
         eps_mlp, act, w1, b1, cs1, w2, b2 = mlp
         wp, bp = self._folded_out(dtype, up)
         n, c, h = q.shape[0], q.shape[1], self.num_heads
         dev = q.device
-        att = torch.empty((n, wp.shape[1]), dtype=dtype, device=dev)
-        if wp.shape[1] > c + h * up:
-            att[:, c + h * up:].zero_()
+        att = self._att_buffer(n, wp.shape[1], c + h * up, dtype, dev)
         y, hid, out = (torch.empty((n, w), dtype=dtype, device=dev) for w in (c, w1.shape[0], c))
         stats = torch.empty((2 if out_stats_eps is not None else 1, n, 2), dtype=torch.float32, device=dev)
         ws = torch.empty((n * max(c // 128, 1), 2), dtype=torch.float32, device=dev)
@@ -399,29 +431,41 @@ class GraphTransformerBaseBlock(BaseBlock, ABC):
 
     block_abi = True  # False: op by op (tests compare the two routes)
 
-    def _folded_tail(self, q: Tensor, k: Tensor, v: Tensor, x_r: Tensor, u: Tensor, edge_attr_csr: Tensor, plan, res: Tensor,
-                     up: int, out_stats_eps: Optional[float]) -> Tensor:
-        """What follows the folded input products on every route: ``_block_tail``, or the same launches op by op."""
-        done = self._block_tail(q, k, v, x_r, u, edge_attr_csr, plan, res, up, out_stats_eps)
-        if done is not None:
-            return done
+    @staticmethod
+    def _att_buffer(n: int, ld: int, written: int, dtype, device) -> Tensor:
+        """The projection's operand ``[n, ld]``: the edge phase writes the first ``written`` columns, the K padding behind
+        them is zeroed here."""
+        att = torch.empty((n, ld), dtype=dtype, device=device)
+        if ld > written:
+            att[:, written:].zero_()
+        return att
+
+    def _attention(self, q: Tensor, k: Tensor, v: Tensor, x_r: Tensor, u: Optional[Tensor], edge_attr_csr: Tensor, plan,
+                   up: Optional[int]):
+        """Edge phase of the folded (``up``) or unfolded route -> ``(attention buffer, projection weight, bias)``: ``out + x_r``
+        for the plain projection, ``out + x_r | t | 0-pad`` for ``[W_p | W_t]`` (the lin_edge part via ``W_t``)."""
+        if up is None:
+            wp, bp = self._cat_linear("proj", [self.projection], q.dtype)
+            we, be = self._edge_params()
+            return self.conv.fused(q, k, v, x_r, edge_attr_csr, self.edge_dim, we, be, plan, self.num_heads), wp, bp
         wp, bp = self._folded_out(q.dtype, up)
-        att = folded_edge_phase(q, k, v, x_r, u, edge_attr_csr, plan, self.num_heads, up, ld_out=wp.shape[1])
-        # projection(out + x_r) + res, lin_edge part via W_t; the statistics of the MLP's LayerNorm ride on the epilogue,
-        # those of the LayerNorm that reads the new nodes next on the MLP's last Linear
-        y = runtime.linear(att, wp, bp, residual=res, stats_eps=self._mlp_ln_eps("dst", q.dtype))
-        return self._node_mlp(y, "dst", 1, out_stats_eps=out_stats_eps)
+        return folded_edge_phase(q, k, v, x_r, u, edge_attr_csr, plan, self.num_heads, up, ld_out=wp.shape[1]), wp, bp
+
+    def _project(self, att: Tensor, w: Tensor, b: Optional[Tensor], res: Optional[Tensor], chunked: bool = False) -> Tensor:
+        """The projection product (+ ``res``) of every route.  The statistics of the MLP's LayerNorm ride on its epilogue
+        unless the MLP runs in row chunks (those of the LayerNorm that reads the new nodes next ride on the MLP's last
+        Linear, ``_node_mlp``).  The caller drops ``att`` before it goes on to the node MLP."""
+        return runtime.linear(att, w, b, residual=res, stats_eps=None if chunked else self._mlp_ln_eps("dst", att.dtype))
+
+    def _native_mlp(self, which: str) -> NativeSequential:
+        """``node_dst_mlp`` / ``node_src_mlp`` on the kernels, built on first use."""
+        if which not in self._mlps:
+            self._mlps[which] = NativeSequential(self.node_dst_mlp if which == "dst" else self.node_src_mlp)
+        return self._mlps[which]
 
     def _node_mlp(self, y: Tensor, which: str, num_chunks: int, out_stats_eps: Optional[float] = None) -> Tensor:
         """``mlp(y) + y`` with mlp = LayerNorm, Linear, act, Linear; optionally in row chunks (bounded hidden buffer)."""
-        if which == "dst":
-            if self._dst_mlp is None:
-                self._dst_mlp = NativeSequential(self.node_dst_mlp)
-            run = self._dst_mlp
-        else:
-            if self._src_mlp is None:
-                self._src_mlp = NativeSequential(self.node_src_mlp)
-            run = self._src_mlp
+        run = self._native_mlp(which)
         if num_chunks <= 1:
             return run(y, residual=y, out_stats_eps=out_stats_eps)
         return torch.cat([run(c, residual=c) for c in y.tensor_split(num_chunks, dim=0) if c.shape[0] > 0], dim=0)
@@ -496,33 +540,25 @@ class GraphTransformerProcessorBlock(GraphTransformerBaseBlock):
             if up is None:
                 raise NotImplementedError("node-partitioned blocks need the folded edge kernel")
             n_own = x.shape[0]
-            kv_layers, sq_layers = [self.lin_key, self.lin_value], [self.lin_self, self.lin_query]
             kv = torch.empty((n_own + halo.n_recv, 2 * c), dtype=dtype, device=x.device)
-            self._ln_linear(xh, "kv", lambda: self._cat_linear("kv", kv_layers, dtype),
-                            lambda: self._cat_rows(kv_layers), [l.weight for l in kv_layers] + [l.bias for l in kv_layers],
-                            out=kv[:n_own])
+            self._ln_product(xh, "kv", [self.lin_key, self.lin_value], out=kv[:n_own])
             pending = halo.start(kv, n_own)  # xGMI transfer of the halo k|v rows ...
-            sq = self._ln_linear(xh, "squ", lambda: self._folded_in("squ", sq_layers, dtype, up),
-                                 lambda: self._folded_rows(sq_layers, up),
-                                 self._fold_params(sq_layers))  # ... overlapped with the x_r | q | u GEMM
+            sq = self._ln_product(xh, "squ", [self.lin_self, self.lin_query], up)  # ... overlapped with the x_r | q | u GEMM
             halo.finish(pending)
-            return self._folded_tail(sq[:, c:2 * c], kv[:, :c], kv[:, c:], sq[:, :c], sq[:, 2 * c:], edge_attr_csr, plan, x, up,
-                                     self._next_ln_eps(dtype))
-        all4 = [self.lin_self, self.lin_query, self.lin_key, self.lin_value]
-        if up is not None:
-            sq = self._ln_linear(xh, "sqkvu", lambda: self._folded_in("sqkvu", all4, dtype, up),
-                                 lambda: self._folded_rows(all4, up),
-                                 self._fold_params(all4))  # [N, 4C + H*up] = x_r | q | k | v | u
-            return self._folded_tail(sq[:, c:2 * c], sq[:, 2 * c:3 * c], sq[:, 3 * c:4 * c], sq[:, :c], sq[:, 4 * c:],
-                                     edge_attr_csr, plan, x, up, self._next_ln_eps(dtype))
-        wp, bp = self._cat_linear("proj", [self.projection], dtype)
-        we, be = self._edge_params()
-        sqkv = self._ln_linear(xh, "sqkv", lambda: self._cat_linear("sqkv", all4, dtype), lambda: self._cat_rows(all4),
-                               [l.weight for l in all4] + [l.bias for l in all4])  # [N, 4C] = x_r | q | k | v
-        att = self.conv.fused(sqkv[:, c:2 * c], sqkv[:, 2 * c:3 * c], sqkv[:, 3 * c:], sqkv[:, :c], edge_attr_csr,
-                              self.edge_dim, we, be, plan, self.num_heads)
-        y = runtime.linear(att, wp, bp, residual=x, stats_eps=self._mlp_ln_eps("dst", dtype))  # projection(out + x_r) + x
-        return self._node_mlp(y, "dst", 1, out_stats_eps=self._next_ln_eps(dtype))
+            k, v, u = kv[:, :c], kv[:, c:], sq[:, 2 * c:]
+        else:
+            # [N, 4C (+ H*up)] = x_r | q | k | v (| u)
+            sq = self._ln_product(xh, "sqkvu" if up is not None else "sqkv",
+                                  [self.lin_self, self.lin_query, self.lin_key, self.lin_value], up)
+            k, v, u = sq[:, 2 * c:3 * c], sq[:, 3 * c:4 * c], sq[:, 4 * c:]
+        q, x_r, next_eps = sq[:, c:2 * c], sq[:, :c], self._next_ln_eps(dtype)
+        done = None if up is None else self._block_tail(q, k, v, x_r, u, edge_attr_csr, plan, x, up, next_eps)
+        if done is not None:
+            return done
+        att, wp, bp = self._attention(q, k, v, x_r, u, edge_attr_csr, plan, up)
+        y = self._project(att, wp, bp, x)  # projection(out + x_r) + x
+        del att
+        return self._node_mlp(y, "dst", 1, out_stats_eps=next_eps)
 
     # ANEMOI_AMD_MXFP8=1 runs the x_r | q | k | v | u product on MXFP8 only when this is set; off by default, it costs the
     # most accuracy of the covered products (profiles/r07_mxfp8.md section 5); off, the product keeps the bf16 LayerNorm fold
@@ -550,11 +586,11 @@ class GraphTransformerProcessorBlock(GraphTransformerBaseBlock):
             xq = ops.mx_quantize(x, ln=(runtime.f32c(ln.weight), runtime.f32c(ln.bias), ln.eps))
             sq = ops.linear_mx(xq, w_in[0], w_in[1])  # [N, 4C + H*up] = x_r | q | k | v | u
         else:
-            sq = self._ln_linear(self._ln_begin(ln, x), "sqkvu", lambda: self._folded_in("sqkvu", all4, x.dtype, up),
-                                 lambda: self._folded_rows(all4, up), self._fold_params(all4))
-        att = folded_edge_phase(sq[:, c:2 * c], sq[:, 2 * c:3 * c], sq[:, 3 * c:4 * c], sq[:, :c], sq[:, 4 * c:],
-                                edge_attr_csr, plan, self.num_heads, up,
-                                ld_out=ops.round_up(c + self.num_heads * up, ops.k_multiple(x.dtype)))
+            sq = self._ln_product(self._ln_begin(ln, x), "sqkvu", all4, up)
+        width = c + self.num_heads * up
+        att = self._att_buffer(x.shape[0], ops.round_up(width, ops.k_multiple(x.dtype)), width, x.dtype, x.device)
+        folded_edge_phase(sq[:, c:2 * c], sq[:, 2 * c:3 * c], sq[:, 3 * c:4 * c], sq[:, :c], sq[:, 4 * c:], edge_attr_csr, plan,
+                          self.num_heads, up, out=att)
         y = ops.linear_mx(ops.mx_quantize(att[:, :c + self.num_heads * up]), w_out[0], w_out[1], residual=x)
         return self._mx_node_mlp(y, "dst")
 
@@ -628,102 +664,156 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
 
     mx_node_mlp = True  # ANEMOI_AMD_MXFP8=1 runs node_dst_mlp on MXFP8 (the decoder's mapper turns it off)
 
-    def native(self, x_src: Tensor, x_dst: Tensor, edge_attr_csr: Tensor, plan: EdgePlan, num_chunks: int = 1,
-               halo=None, out_stats_eps: Optional[float] = None):
-        """``out_stats_eps``: epsilon of the LayerNorm the new destination nodes enter next (its statistics then come
-        out of the node MLP's last GEMM).  ``halo``: node-partitioned run -- ``x_src`` holds this rank's source rows, the k|v rows of the other
-        sources of the plan are appended by one all-to-all-v."""
+    # ---- the route: decided here and nowhere else (DESIGN.md section 4.2 has the table of routes)
+    def route(self, dtype, src: Rows, dst: Rows, num_chunks: int = 1, halo: bool = False) -> Route:
+        """Which launch sequence ``native`` runs for these rows, from what is known before anything is launched; the switches
+        are read now.  In precedence order: ``dec_fold`` (raw destination rows ride in the projection product),
+        ``raw_sources`` (attention over raw source rows, no ``k | v``), ``folded`` (``lin_edge`` folded into the neighbouring
+        products), ``unfolded``.  ``native`` takes its route from here; the mappers ask with rows of kind ``"raw"`` before
+        they embed and form ``h`` only where ``src_h`` / ``dst_h`` say the route reads it."""
+        mxfp8 = runtime.mxfp8_enabled(dtype)
+        mx = mxfp8 and self.mx_node_mlp  # the destination nodes' MLP on MXFP8 (DESIGN.md 4.6)
+        if mx:
+            fc1 = self.node_dst_mlp[1]
+            self._mx_check(fc1.in_features if isinstance(fc1, nn.Linear) else 0, True if halo else None)
+        up = self.fold_width(dtype)
+        h, d = self.num_heads, self.out_channels_conv
+        plain = dtype == torch.bfloat16 and num_chunks <= 1 and not halo and not self.update_src_nodes and up is not None
+        if (plain and dst.kind == "raw" and src.kind == "tensor" and dst.on_gpu and runtime.dec_fold_enabled()
+                and not mxfp8 and runtime.embed_fold_enabled(dtype) and dst.k_pad in (64, 128, 256)
+                # the rows' statistics come from the side product of ``EmbeddedRows.stats``, which the opt-in thin statistics
+                # site would move to the slower kernel on every grid row (and a launch-list test pins the decoder's list
+                # under it); ``out | t`` a whole number of K slabs: the raw blocks start right behind them
+                and not runtime.thin_stats_enabled() and (h * (d + up)) % ops.k_multiple(dtype) == 0):
+            name = "dec_fold"
+        elif (plain and src.kind == "raw" and not mx and src.on_gpu and runtime.edge_raw_enabled() and h == 16
+              and src.k_pad in (64, 128, 256) and self._sum_col(src.k_pad, src.one_col) >= src.in_features):
+            name = "raw_sources"
+        elif up is not None:
+            name = "folded"
+        elif halo:
+            raise NotImplementedError("node-partitioned blocks need the folded edge kernel")
+        else:
+            name = "unfolded"
+        return Route(name, up, mx, num_chunks > 1,
+                     block_tail=name == "folded" and num_chunks <= 1 and not self.update_src_nodes and not mx,
+                     src_h=self.update_src_nodes, dst_h=name != "dec_fold")
+
+    def dec_fold_route(self, dtype, k_pad: int, num_chunks: int = 1) -> bool:
+        """``route`` for plain source rows and raw destination rows of ``k_pad`` columns on the GPU: is it ``dec_fold``?"""
+        return self.route(dtype, Rows(), Rows("raw", k_pad, on_gpu=True), num_chunks).name == "dec_fold"
+
+    def native(self, x_src, x_dst, edge_attr_csr: Tensor, plan: EdgePlan, num_chunks: int = 1, halo=None,
+               out_stats_eps: Optional[float] = None):
+        """``(source rows, new destination rows)``.  The first element: the updated source rows under ``update_src_nodes``,
+        else the embedded source rows as they came (``h`` of ``EmbeddedRows``, or the plain tensor) -- ``None`` where the rows
+        came without ``h``.  ``out_stats_eps``: epsilon of the LayerNorm the new destination nodes enter next (its
+        statistics then come out of the node MLP's last GEMM).  ``halo``: node-partitioned run -- ``x_src`` holds this rank's
+        source rows, the k|v rows of the other sources of the plan are appended by one all-to-all-v.
+
+        Four stages, each selected by ``route``: source side, destination product, edge phase into the attention buffer,
+        tail.  Large intermediates are dropped before the next stage allocates."""
         dtype = x_dst.dtype
         self._check_channels(dtype)
-        mx = runtime.mxfp8_enabled(dtype) and self.mx_node_mlp  # the destination nodes' MLP on MXFP8 (DESIGN.md 4.6)
-        if mx:
-            self._mx_check(self.node_dst_mlp[1].in_features if isinstance(self.node_dst_mlp[1], nn.Linear) else 0, halo)
-        c = self.num_heads * self.out_channels_conv
-        # EmbeddedRows (mappers): the rows arrive as the raw features they are embedded from; ``h_dst`` is materialised
-        h_dst = x_dst.h if isinstance(x_dst, EmbeddedRows) else x_dst
-        if isinstance(x_src, EmbeddedRows) and x_src.h is None and self.update_src_nodes:
+        src, dst = Rows.of(x_src), Rows.of(x_dst)
+        r = self.route(dtype, src, dst, num_chunks, halo is not None)
+        # the hand-over: a mapper that asked ``route`` formed every ``h`` the route reads; other callers may not have
+        if r.src_h and src.kind == "raw":
             raise ValueError("update_src_nodes needs the embedded source rows")
-        kv_layers, sq_layers = [self.lin_key, self.lin_value], [self.lin_self, self.lin_query]
-        kv_args = ("kv", lambda: self._cat_linear("kv", kv_layers, dtype), lambda: self._cat_rows(kv_layers),
-                   [l.weight for l in kv_layers] + [l.bias for l in kv_layers])
-        if isinstance(x_dst, EmbeddedRows) and x_dst.h is None:
-            # destination rows handed over without their embedding (the backward mapper, when dec_fold_route holds)
-            if (isinstance(x_src, EmbeddedRows) or halo is not None
-                    or not self.dec_fold_route(dtype, x_dst.x_aug.shape[1], num_chunks)):
-                raise ValueError("destination rows without their embedding need the decoder fold (dec_fold_route)")
-            kv = self._ln_linear(self._ln_begin(self.layer_norm1, x_src), *kv_args)
-            return x_src, self._native_dec_fold(kv, x_dst, edge_attr_csr, plan, out_stats_eps)
+        if r.dst_h and dst.kind == "raw":
+            raise ValueError("destination rows without their embedding need the decoder fold (dec_fold_route)")
+        c, h, up = self.num_heads * self.out_channels_conv, self.num_heads, r.up
+        # EmbeddedRows (mappers): the rows arrive as the raw features they are embedded from
+        h_src = x_src.h if isinstance(x_src, EmbeddedRows) else x_src
+        h_dst = x_dst.h if isinstance(x_dst, EmbeddedRows) else x_dst
+
+        # 1. source side: k | v from the LayerNorm-folded product (into the halo buffer, then the all-to-all), or nothing
         xs = self._ln_begin(self.layer_norm1, x_src)
-        raw = None if (halo is not None or num_chunks > 1 or mx) else self._raw_source_weights(x_src, dtype)
-        if raw is not None:
-            return x_src.h, self._native_raw_sources(x_src, xs[1], x_dst, h_dst, edge_attr_csr, plan, raw, out_stats_eps)
-        if halo is None:
-            kv = self._ln_linear(xs, *kv_args)  # [N_src, 2C] = k | v
+        kv = pending = None
+        if r.name == "raw_sources":
+            src_stats = xs[1]
+        elif halo is None:
+            kv = self._ln_product(xs, "kv", [self.lin_key, self.lin_value])  # [N_src, 2C] = k | v
         else:
             n_own = x_src.shape[0]
             kv = torch.empty((n_own + halo.n_recv, 2 * c), dtype=dtype, device=x_src.device)
-            self._ln_linear(xs, *kv_args, out=kv[:n_own])
+            self._ln_product(xs, "kv", [self.lin_key, self.lin_value], out=kv[:n_own])
             pending = halo.start(kv, n_own)  # overlapped with the destination-side LayerNorm + GEMM below
         del xs
-        xd = self._ln_begin(self.layer_norm2, x_dst)
-        up = self.fold_width(dtype)
-        if up is not None:
-            wp, bp = self._folded_out(dtype, up)
-            sq = self._ln_linear(xd, "squ", lambda: self._folded_in("squ", sq_layers, dtype, up),
-                                 lambda: self._folded_rows(sq_layers, up),
-                                 self._fold_params(sq_layers))  # [N_dst, 2C + H*up] = x_r | q | u
-            del xd
-            if halo is not None:
-                halo.finish(pending)
-            if num_chunks <= 1 and not self.update_src_nodes and not mx:
-                new_dst = self._folded_tail(sq[:, c:2 * c], kv[:, :c], kv[:, c:], sq[:, :c], sq[:, 2 * c:], edge_attr_csr, plan,
-                                            h_dst, up, out_stats_eps)
-                return (x_src.h if isinstance(x_src, EmbeddedRows) else x_src), new_dst
-            att = folded_edge_phase(sq[:, c:2 * c], kv[:, :c], kv[:, c:], sq[:, :c], sq[:, 2 * c:], edge_attr_csr, plan,
-                                    self.num_heads, up, ld_out=wp.shape[1])
+
+        # 2. destination product: x_r | q | u, q | u (decoder fold), x_r | q (unfolded); x_r | q | u and qt on raw sources
+        qt = None
+        if r.name == "raw_sources":
+            raw = self._raw_source_weights(x_src, dtype)
+            sq, qt = self._raw_dst_side(x_src, x_dst, h_dst, up, raw[0])
         else:
-            if halo is not None:
-                raise NotImplementedError("node-partitioned blocks need the folded edge kernel")
-            wp, bp = self._cat_linear("proj", [self.projection], dtype)
-            we, be = self._edge_params()
-            sq = self._ln_linear(xd, "sq", lambda: self._cat_linear("sq", sq_layers, dtype),
-                                 lambda: self._cat_rows(sq_layers),
-                                 [l.weight for l in sq_layers] + [l.bias for l in sq_layers])  # [N_dst, 2C] = x_r | q
+            xd = self._ln_begin(self.layer_norm2, x_dst)
+            dst_stats = xd[1]
+            if r.name == "dec_fold":
+                sq = self._ln_product(xd, "qu", [self.lin_query], up)  # [N_dst, C + H*up] = q | u (no x_r rows)
+            else:  # [N_dst, 2C (+ H*up)] = x_r | q (| u)
+                sq = self._ln_product(xd, "sq" if up is None else "squ", [self.lin_self, self.lin_query], up)
             del xd
-            att = self.conv.fused(sq[:, c:], kv[:, :c], kv[:, c:], sq[:, :c], edge_attr_csr, self.edge_dim, we, be,
-                                  plan, self.num_heads)
+        if pending is not None:
+            halo.finish(pending)
+
+        # 3. edge phase into the attention buffer, the projection's operand
+        res = h_dst
+        if r.name == "dec_fold":
+            # rstd x | x written behind out | t: ONE projection product over [out | t | rstd x | x] carries W_p x_r and the
+            # residual emb(x) -- neither is ever formed
+            xa, res = x_dst.x_aug, None
+            wp, bp = self._dec_fold_weights(x_dst, dtype, up)
+            width, k_att = c + h * up, c + h * up + 2 * xa.shape[1]
+            att = self._att_buffer(xa.shape[0], wp.shape[1], k_att, dtype, xa.device)
+            folded_edge_phase(sq[:, :c], kv[:, :c], kv[:, c:], None, sq[:, c:], edge_attr_csr, plan, h, up, out=att)
+            ops.raw_row_tail(xa, dst_stats, att[:, width:k_att])
+        elif r.name == "raw_sources":
+            # the raw-row edge kernel, then g -> sum alpha v (one launch over the heads) + x_r
+            w_qt, w_g, sum_col = raw
+            wp, bp = self._folded_out(dtype, up)
+            att = self._att_buffer(sq.shape[0], wp.shape[1], c + h * up, dtype, sq.device)
+            g = ops.gt_edge_attention_raw(qt, x_src.x_aug, src_stats, sq[:, 2 * c:2 * c + h * up], edge_attr_csr, plan.rowptr,
+                                          plan.col, h, self.out_channels_conv, up, sum_col, att[:, c:c + h * up])
+            del qt
+            if w_g.dim() == 3:
+                ops.linear_heads(g, w_g, out=att[:, :c], residual=sq[:, :c])
+            else:
+                runtime.linear(g, w_g, residual=sq[:, :c], out=att[:, :c])
+            del g
+        else:
+            q, k, v, x_r, u = sq[:, c:2 * c], kv[:, :c], kv[:, c:], sq[:, :c], sq[:, 2 * c:]
+            done = self._block_tail(q, k, v, x_r, u, edge_attr_csr, plan, res, up, out_stats_eps) if r.block_tail else None
+            if done is not None:
+                return h_src, done
+            att, wp, bp = self._attention(q, k, v, x_r, u, edge_attr_csr, plan, up)
+            del q, k, v, x_r, u
         del sq, kv
-        y = runtime.linear(att, wp, bp, residual=h_dst,
-                       stats_eps=self._mlp_ln_eps("dst", dtype) if num_chunks <= 1 else None)
+
+        # 4. tail: projection (+ residual) and the node MLPs
+        y = self._project(att, wp, bp, res, r.chunked)
         del att
-        if mx:
+        if r.mx:
             new_dst = self._mx_node_mlp(y, "dst", num_chunks)
         else:
             new_dst = self._node_mlp(y, "dst", num_chunks, out_stats_eps=out_stats_eps)
-        if isinstance(x_src, EmbeddedRows):
-            x_src = x_src.h
-        new_src = self._node_mlp(x_src, "src", num_chunks) if self.update_src_nodes else x_src
-        return new_src, new_dst
+        return (self._node_mlp(h_src, "src", num_chunks) if self.update_src_nodes else h_src), new_dst
 
     # ---- sources given as raw rows: k | v are never formed (DESIGN.md section 4.2, "raw-row encoder")
-    RAW_ROWS_DEFAULT = "1"  # ANEMOI_AMD_EDGE_RAW=0: the k | v product on every source row + the folded edge kernel (A/B)
+    @staticmethod
+    def _sum_col(ks: int, one_col: int) -> int:
+        """The last column of the raw rows that is not the constant-1 column; the route needs it inside the K padding."""
+        return ks - 1 if one_col != ks - 1 else ks - 2
 
-    def _raw_source_weights(self, x_src, dtype):
-        """``(W_qt [H, Ks, D], W_g [H, D, Ks], sum_col)`` when this block can attend over the raw source rows, else ``None``.
+    def _raw_source_weights(self, x_src: EmbeddedRows, dtype):
+        """``(W_qt [H, Ks, D], W_g [H, D, Ks], sum_col)`` of the ``raw_sources`` route (``route`` says when it is taken).
 
         With ``F = [F_k; F_v]`` and ``b' = [b_k; b_v]`` the embedding- and LayerNorm-folded k | v operator of
         ``runtime.fold_embedded_layer_norm`` (``k_j = rstd_j F_k x_j + b_k``): ``W_qt[h] = F_k[h]^T`` carries a query to
         the raw space, ``W_g[h] = F_v[h]`` brings the aggregate back, with ``b_v[h]`` in column ``sum_col`` -- a zero
         column of the raw rows where the edge kernel leaves ``sum_j alpha_ij``.  They depend on parameters only."""
-        h, d = self.num_heads, self.out_channels_conv
-        if (not isinstance(x_src, EmbeddedRows) or x_src.h is not None or self.update_src_nodes
-                or dtype != torch.bfloat16 or not x_src.x_aug.is_cuda
-                or os.environ.get("ANEMOI_AMD_EDGE_RAW", self.RAW_ROWS_DEFAULT) == "0"):
-            return None
-        ks, k_in = x_src.x_aug.shape[1], x_src.emb.in_features
-        sum_col = ks - 1 if x_src.one_col != ks - 1 else ks - 2
-        if self.fold_width(dtype) is None or h != 16 or ks not in (64, 128, 256) or sum_col < k_in:
-            return None
+        h, d, ks = self.num_heads, self.out_channels_conv, x_src.x_aug.shape[1]
+        sum_col = self._sum_col(ks, x_src.one_col)
         kv_layers = [self.lin_key, self.lin_value]
         ln, emb = self.layer_norm1, x_src.emb
 
@@ -744,69 +834,29 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
                                 [l.weight for l in kv_layers] + [l.bias for l in kv_layers]
                                 + [ln.weight, ln.bias, emb.weight, emb.bias], build)
 
-    def _native_raw_sources(self, x_src, src_stats: Tensor, x_dst, h_dst: Tensor, edge_attr_csr: Tensor, plan, raw,
-                            out_stats_eps: Optional[float]) -> Tensor:
-        """The block on raw source rows: ``x_r | q | u`` as before, ``q -> qt`` (one launch over the heads), the raw-row
-        edge kernel, ``g -> sum alpha v`` (one launch over the heads) ``+ x_r``, then projection and node MLP unchanged."""
-        dtype = x_dst.dtype
-        c, h = self.num_heads * self.out_channels_conv, self.num_heads
-        w_qt, w_g, sum_col = raw
-        up = self.fold_width(dtype)
+    def _raw_dst_side(self, x_src: EmbeddedRows, x_dst, h_dst: Tensor, up: int, w_qt: Tensor):
+        """``(x_r | q | u, qt)`` of the ``raw_sources`` route: the destination product and ``q -> qt`` (one launch over the
+        heads).  For hoisted destination rows (the encoder's mesh rows on the inference path) both depend on parameters only
+        and are kept -- both are read, never written, downstream.  Sources: the rows' own, this block's destination-side
+        parameters, and the source-side ones that form A_k in ``w_qt``."""
+        dtype, c = x_dst.dtype, self.num_heads * self.out_channels_conv
         sq_layers = [self.lin_self, self.lin_query]
-        wp, bp = self._folded_out(dtype, up)
-        per_head = w_qt.dim() == 3
 
         def dst_side():
-            sq = self._ln_linear(self._ln_begin(self.layer_norm2, x_dst), "squ",
-                                 lambda: self._folded_in("squ", sq_layers, dtype, up),
-                                 lambda: self._folded_rows(sq_layers, up), self._fold_params(sq_layers))  # x_r | q | u
-            return sq, (ops.linear_heads(sq[:, c:2 * c], w_qt) if per_head else runtime.linear(sq[:, c:2 * c], w_qt))
+            sq = self._ln_product(self._ln_begin(self.layer_norm2, x_dst), "squ", sq_layers, up)  # x_r | q | u
+            return sq, (ops.linear_heads(sq[:, c:2 * c], w_qt) if w_qt.dim() == 3 else runtime.linear(sq[:, c:2 * c], w_qt))
 
-        # hoisted destination rows (the encoder's mesh rows on the inference path): x_r | q | u and qt depend on parameters
-        # only -- both are read, never written, below.  Sources: the rows' own, this block's destination-side parameters, and
-        # the source-side ones that form A_k in w_qt.
         sources = runtime.static_sources(x_dst) if runtime.enc_hoist_enabled() else None
-        if sources is not None:
-            ln1, ln2, emb = self.layer_norm1, self.layer_norm2, x_src.emb
-            sources = (sources + [h_dst, ln2.weight, ln2.bias] + self._fold_params(sq_layers)
-                       + [self.lin_key.weight, self.lin_key.bias, self.lin_value.weight, self.lin_value.bias, ln1.weight,
-                          ln1.bias, emb.weight, emb.bias])
-            sq, qt = runtime.hoisted(self._packed, ("squ|qt", dtype, tuple(h_dst.shape), up, x_src.x_aug.shape[1], x_src.one_col),
-                                     sources, dst_side)
-        else:
-            sq, qt = dst_side()
-        att = torch.empty((sq.shape[0], wp.shape[1]), dtype=dtype, device=sq.device)
-        if wp.shape[1] > c + h * up:
-            att[:, c + h * up:].zero_()
-        g = ops.gt_edge_attention_raw(qt, x_src.x_aug, src_stats, sq[:, 2 * c:2 * c + h * up], edge_attr_csr, plan.rowptr,
-                                      plan.col, h, self.out_channels_conv, up, sum_col, att[:, c:c + h * up])
-        del qt
-        if per_head:
-            ops.linear_heads(g, w_g, out=att[:, :c], residual=sq[:, :c])
-        else:
-            runtime.linear(g, w_g, residual=sq[:, :c], out=att[:, :c])
-        del g
-        del sq
-        y = runtime.linear(att, wp, bp, residual=h_dst, stats_eps=self._mlp_ln_eps("dst", dtype))
-        del att
-        return self._node_mlp(y, "dst", 1, out_stats_eps=out_stats_eps)
+        if sources is None:
+            return dst_side()
+        ln1, ln2, emb = self.layer_norm1, self.layer_norm2, x_src.emb
+        sources = (sources + [h_dst, ln2.weight, ln2.bias] + self._fold_params(sq_layers)
+                   + [self.lin_key.weight, self.lin_key.bias, self.lin_value.weight, self.lin_value.bias, ln1.weight,
+                      ln1.bias, emb.weight, emb.bias])
+        return runtime.hoisted(self._packed, ("squ|qt", dtype, tuple(h_dst.shape), up, x_src.x_aug.shape[1], x_src.one_col),
+                               sources, dst_side)
 
     # ---- destinations given as raw rows: x_r and the embedded rows ride in the projection product (DESIGN.md section 4.2)
-    def dec_fold_route(self, dtype, k_pad: int, num_chunks: int = 1) -> bool:
-        """Whether this block takes destination rows as ``EmbeddedRows`` WITHOUT ``h`` (``k_pad`` raw columns): bf16 inference
-        in one chunk on the ``lin_edge`` fold, ``ANEMOI_AMD_DEC_FOLD`` not 0, the raw width one of 64 / 128 / 256 and
-        ``out | t`` a whole number of K slabs (the raw blocks start right behind them).  The caller (the backward mapper)
-        asks before it decides not to materialise the embedding.  Not with MXFP8, and not with the opt-in thin statistics site
-        (``ANEMOI_AMD_THIN_STATS=1``): without ``h`` the rows' statistics come from the side product of ``EmbeddedRows.stats``,
-        which that switch would move to the slower kernel on every grid row (and an existing launch-list test pins the
-        decoder's list under it)."""
-        if (not runtime.dec_fold_enabled() or dtype != torch.bfloat16 or num_chunks > 1 or self.update_src_nodes
-                or runtime.mxfp8_enabled(dtype) or not runtime.embed_fold_enabled(dtype) or k_pad not in (64, 128, 256)
-                or os.environ.get("ANEMOI_AMD_THIN_STATS", "0") == "1"):
-            return False
-        up = self.fold_width(dtype)
-        return up is not None and (self.num_heads * (self.out_channels_conv + up)) % ops.k_multiple(dtype) == 0
-
     def _dec_fold_weights(self, x_dst: EmbeddedRows, dtype, up: int):
         """Packed ``[W_p | W_t | W_p A_s | E]`` + f32 bias of ``runtime.compose_decoder_fold``, rebuilt when any parameter that
         enters changes (pointer, in-place version, device)."""
@@ -818,32 +868,6 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
             lambda: runtime.compose_decoder_fold(self.projection.weight, self.projection.bias, self._projection_fold(up),
                                                  self.lin_self.weight, self.lin_self.bias, ln.weight, ln.bias, emb.weight,
                                                  emb.bias, ks, x_dst.one_col, dtype))
-
-    def _native_dec_fold(self, kv: Tensor, x_dst: EmbeddedRows, edge_attr_csr: Tensor, plan,
-                         out_stats_eps: Optional[float]) -> Tensor:
-        """The block on raw destination rows ``x``: ``q | u`` from the LayerNorm-folded product (no ``x_r`` rows), the folded
-        edge kernel without ``x_r``, ``rstd x | x`` written behind ``out | t``, and ONE projection product over
-        ``[out | t | rstd x | x]`` that carries ``W_p x_r`` and the residual ``emb(x)`` -- neither is ever formed.  Node MLP
-        unchanged."""
-        dtype = x_dst.dtype
-        c, h, ln = self.num_heads * self.out_channels_conv, self.num_heads, self.layer_norm2
-        up = self.fold_width(dtype)
-        xa = x_dst.x_aug
-        stats = x_dst.stats(ln.eps)
-        q_layers = [self.lin_query]
-        qu = self._ln_linear((x_dst, stats, ln), "qu", None, lambda: self._folded_rows(q_layers, up),
-                             self._fold_params(q_layers))  # [N_dst, C + H*up] = q | u
-        w, b = self._dec_fold_weights(x_dst, dtype, up)
-        width, k_att = c + h * up, c + h * up + 2 * xa.shape[1]
-        att = torch.empty((xa.shape[0], w.shape[1]), dtype=dtype, device=xa.device)
-        if w.shape[1] > k_att:
-            att[:, k_att:].zero_()
-        folded_edge_phase(qu[:, :c], kv[:, :c], kv[:, c:], None, qu[:, c:], edge_attr_csr, plan, h, up, out=att)
-        del qu, kv
-        ops.raw_row_tail(xa, stats, att[:, width:k_att])
-        y = runtime.linear(att, w, b, stats_eps=self._mlp_ln_eps("dst", dtype))
-        del att
-        return self._node_mlp(y, "dst", 1, out_stats_eps=out_stats_eps)
 
     def _sharded(self, x, edge_attr: Tensor, edge_index: Tensor, shapes: tuple, batch_size: int, model_comm_group, size=None):
         """The reference's module-level protocol across a model group (layers/block.py:479-550): row shards of the source

@@ -22,6 +22,7 @@ from .. import training
 from .block import EmbeddedRows
 from .block import GraphConvMapperBlock
 from .block import GraphTransformerMapperBlock
+from .block import Rows
 from .block import inference_num_chunks
 from .graph import TrainableTensor
 from .mlp import MLP
@@ -157,8 +158,23 @@ class GraphTransformerBaseMapper(GraphEdgeMixin, BaseMapper):
         self._plans = runtime.PlanCache()
 
     # ---- hooks specialised by the forward / backward mapper ------------------------------------
-    def _embed(self, x_src: Tensor, x_dst: Tensor, one_cols=(None, None), dst_static: bool = False, dst_fold: bool = False):
+    def _embed(self, x_src: Tensor, x_dst: Tensor, one_cols=(None, None), num_chunks: int = 1, halo: bool = False,
+               dst_static: bool = False):
         return x_src, x_dst  # the base mapper embeds nothing (reference BaseMapper.pre_process, layers/mapper.py:87-96)
+
+    @staticmethod
+    def _folds(lin: nn.Linear, x: Tensor, eps: Optional[float]) -> bool:
+        """Whether ``lin(x)`` goes to the block as ``EmbeddedRows``: few input features, bf16 LayerNorm-fold path."""
+        return eps is not None and runtime.embed_fold_enabled(x.dtype) and 2 * (lin.in_features + 1) <= lin.out_features
+
+    def _rows(self, lin: nn.Linear, x: Tensor, eps: Optional[float], one_col: Optional[int]) -> Rows:
+        """What ``_embedded`` would hand to the block for ``lin(x)`` without ``h``, for the block's ``route``: the mapper
+        asks before it embeds and forms ``h`` only where the route reads it."""
+        if not self._folds(lin, x, eps):
+            return Rows(on_gpu=x.is_cuda)
+        k_in = lin.in_features
+        k_pad = x.shape[1] if one_col is not None else ops.round_up(k_in + 1, ops.k_multiple(x.dtype))
+        return Rows("raw", k_pad, k_in if one_col is None else one_col, k_in, x.is_cuda)
 
     def _embedded(self, tag: str, lin: nn.Linear, x: Tensor, eps: Optional[float], one_col: Optional[int],
                   materialise: bool, static: bool = False):
@@ -174,7 +190,7 @@ class GraphTransformerBaseMapper(GraphEdgeMixin, BaseMapper):
             return runtime.hoisted(self._packed, (tag, x.dtype, tuple(x.shape), one_col, eps, materialise), sources,
                                    lambda: runtime.mark_static(self._embedded(tag, lin, x, eps, one_col, materialise), sources))
         k_in = lin.in_features
-        if eps is None or not runtime.embed_fold_enabled(x.dtype) or 2 * (k_in + 1) > lin.out_features:
+        if not self._folds(lin, x, eps):
             return linear_native(self._packed, tag, lin, x, stats_eps=eps)
         if one_col is None:
             kp = ops.round_up(k_in + 1, ops.k_multiple(x.dtype))
@@ -217,8 +233,8 @@ class GraphTransformerBaseMapper(GraphEdgeMixin, BaseMapper):
         ea = runtime.edge_attr_csr_cached(self._packed, self.edge_attr, self.trainable.trainable, plan,
                                           *self.proc.edge_layout(x_dst.dtype))
         num_chunks = self.proc.num_chunks if self.training else inference_num_chunks()
-        h_src, h_dst = self._embed(x_src, x_dst, one_cols, dst_static=num_chunks <= 1 and runtime.enc_hoist_enabled(),
-                                   dst_fold=num_chunks <= 1)
+        h_src, h_dst = self._embed(x_src, x_dst, one_cols, num_chunks,
+                                   dst_static=num_chunks <= 1 and runtime.enc_hoist_enabled())
         _, h_dst = self.proc.native(h_src, h_dst, ea, plan, num_chunks, out_stats_eps=self._extract_ln_eps(h_dst.dtype))
         return self._extract(h_dst, out_dtype)
 
@@ -229,8 +245,8 @@ class GraphTransformerBaseMapper(GraphEdgeMixin, BaseMapper):
         plan = local_graph.plan
         ea = runtime.edge_attr_csr_cached(self._packed, self.edge_attr, self.trainable.trainable, plan,
                                           *self.proc.edge_layout(x_dst.dtype))
-        h_src, h_dst = self._embed(x_src, x_dst, one_cols)
         num_chunks = self.proc.num_chunks if self.training else inference_num_chunks()
+        h_src, h_dst = self._embed(x_src, x_dst, one_cols, num_chunks, local_graph.halo is not None)
         _, h_dst = self.proc.native(h_src, h_dst, ea, plan, num_chunks, local_graph.halo,
                                     out_stats_eps=self._extract_ln_eps(h_dst.dtype))
         return self._extract(h_dst, out_dtype)
@@ -293,11 +309,15 @@ class GraphTransformerForwardMapper(ForwardMapperPreProcessMixin, GraphTransform
                          src_grid_size=src_grid_size, dst_grid_size=dst_grid_size)
         self.emb_nodes_src = nn.Linear(self.in_channels_src, self.hidden_dim)
 
-    def _embed(self, x_src: Tensor, x_dst: Tensor, one_cols=(None, None), dst_static: bool = False, dst_fold: bool = False):
+    def _embed(self, x_src: Tensor, x_dst: Tensor, one_cols=(None, None), num_chunks: int = 1, halo: bool = False,
+               dst_static: bool = False):
         eps1, eps2 = self._block_ln_eps(x_src.dtype)  # the embeddings enter the block's layer_norm1 / layer_norm2
-        # source rows feed k | v only: their embedding is never written out when it can be folded away
-        return (self._embedded("emb_nodes_src", self.emb_nodes_src, x_src, eps1, one_cols[0],
-                               materialise=self.proc.update_src_nodes),
+        # source rows feed k | v only: their embedding is written out only where the block's route reads it
+        # (``update_src_nodes``); the destination embedding always is -- it is the residual of the projection
+        dst = self._rows(self.emb_nodes_dst, x_dst, eps2, one_cols[1])
+        route = self.proc.route(x_dst.dtype, self._rows(self.emb_nodes_src, x_src, eps1, one_cols[0]),
+                                dst._replace(kind="embedded") if dst.kind == "raw" else dst, num_chunks, halo)
+        return (self._embedded("emb_nodes_src", self.emb_nodes_src, x_src, eps1, one_cols[0], materialise=route.src_h),
                 self._embedded("emb_nodes_dst", self.emb_nodes_dst, x_dst, eps2, one_cols[1], materialise=True,
                                static=dst_static))
 
@@ -334,15 +354,15 @@ class GraphTransformerBackwardMapper(BackwardMapperPostProcessMixin, GraphTransf
         return (x_src, self._apply_module(self.emb_nodes_dst, x_dst), change_channels_in_shape(shapes_src, self.hidden_dim),
                 change_channels_in_shape(shapes_dst, self.hidden_dim))
 
-    def _embed(self, x_src: Tensor, x_dst: Tensor, one_cols=(None, None), dst_static: bool = False, dst_fold: bool = False):
-        # The embedded grid rows are only the projection's residual and the input of x_r | q | u: where the block folds both
-        # into its projection product (``dst_fold``: the one-chunk, one-rank forward; the block's ``dec_fold_route``) they
-        # are not formed.  (The grid rows carry input data: never static.)
-        lin = self.emb_nodes_dst
-        k_pad = x_dst.shape[1] if one_cols[1] is not None else ops.round_up(lin.in_features + 1, ops.k_multiple(x_dst.dtype))
-        fold = dst_fold and x_dst.is_cuda and self.proc.dec_fold_route(x_dst.dtype, k_pad)
-        return x_src, self._embedded("emb_nodes_dst", lin, x_dst, self._block_ln_eps(x_dst.dtype)[1], one_cols[1],
-                                     materialise=not fold)
+    def _embed(self, x_src: Tensor, x_dst: Tensor, one_cols=(None, None), num_chunks: int = 1, halo: bool = False,
+               dst_static: bool = False):
+        # The embedded grid rows are only the projection's residual and the input of x_r | q | u: where the block's route
+        # folds both into its projection product (``dec_fold``) they are not formed.  (The grid rows carry input data: never
+        # static.)
+        lin, eps = self.emb_nodes_dst, self._block_ln_eps(x_dst.dtype)[1]
+        route = self.proc.route(x_dst.dtype, Rows(on_gpu=x_src.is_cuda), self._rows(lin, x_dst, eps, one_cols[1]), num_chunks,
+                                halo)
+        return x_src, self._embedded("emb_nodes_dst", lin, x_dst, eps, one_cols[1], materialise=route.dst_h)
 
     def _extract(self, x_dst: Tensor, out_dtype) -> Tensor:
         ln, lin = self.node_data_extractor[0], self.node_data_extractor[1]

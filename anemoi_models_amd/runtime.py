@@ -697,6 +697,27 @@ def ln_fold_enabled(dtype: torch.dtype) -> bool:
     return dtype == torch.bfloat16 and os.environ.get("ANEMOI_AMD_LN_FOLD", "1") != "0"
 
 
+def edge_fold_enabled() -> bool:
+    """``lin_edge`` rides in the neighbouring GEMMs and the folded edge kernel runs (``ANEMOI_AMD_EDGE_FOLD=0``: the unfolded
+    kernel, A/B).  The shape conditions are the block's (``GraphTransformerBaseBlock.fold_width``)."""
+    return os.environ.get("ANEMOI_AMD_EDGE_FOLD", "1") != "0"
+
+
+RAW_ROWS_DEFAULT = "1"  # ANEMOI_AMD_EDGE_RAW=0: the k | v product on every source row + the folded edge kernel (A/B)
+
+
+def edge_raw_enabled() -> bool:
+    """The encoder attends over the raw source rows ("raw-row encoder"; ``ANEMOI_AMD_EDGE_RAW=0``
+    disables)."""
+    return os.environ.get("ANEMOI_AMD_EDGE_RAW", RAW_ROWS_DEFAULT) != "0"
+
+
+def thin_stats_enabled() -> bool:
+    """``ANEMOI_AMD_THIN_STATS=1`` (opt-in, under ``ANEMOI_AMD_THIN``): the statistics side product of ``EmbeddedRows.stats`` on
+    the thin kernel.  Measured slower than the persistent kernel + finalize at config 3 (profiles/r11_thin_hoist.md)."""
+    return os.environ.get("ANEMOI_AMD_THIN_STATS", "0") == "1"
+
+
 def fold_layer_norm(w_rows: Tensor, bias: Optional[Tensor], gamma: Tensor, beta: Tensor, dtype: torch.dtype):
     """Fold ``LayerNorm(gamma, beta)`` into the Linear ``(w_rows [N, K] f32, bias [N] f32 or None)`` that consumes it.
 

@@ -100,6 +100,43 @@ def test_launch_coverage(monkeypatch):
     assert edge(recs_on) == edge(recs_off)
 
 
+@pytest.fixture(scope="module")
+def shared_model():
+    """One model for the tests below, which change switches only (never a parameter)."""
+    model, x, _, _ = _build()
+    return model.to(DEV), x.to(DEV)
+
+
+def _refused_route_is_the_switch_off_route(monkeypatch, shared_model, switch, name, value):
+    """Under ``name=value`` the route behind ``switch`` is refused: ``switch=1`` and ``switch=0`` then run the same launches
+    and give the same bits (and the forward runs -- no rows are handed over without an embedding their route reads)."""
+    model, x = shared_model
+    monkeypatch.setenv("ANEMOI_AMD_DTYPE", "bf16")
+    monkeypatch.setenv(name, value)
+    got = {}
+    for flag in ("1", "0"):
+        monkeypatch.setenv(switch, flag)
+        _forward(model, x)  # packs and hoists what this setting needs: the recorded forward is a steady-state one
+        got[flag] = _forward(model, x, record=True)
+    (y_on, recs_on), (y_off, recs_off) = got["1"], got["0"]
+    print(f"{name}={value}: {len(recs_on)} launches with {switch}=1, {len(recs_off)} with {switch}=0")
+    assert recs_on and recs_on == recs_off
+    assert torch.equal(y_on, y_off)
+
+
+@pytest.mark.parametrize("name,value", [("ANEMOI_AMD_THIN_STATS", "1"), ("ANEMOI_AMD_MXFP8", "1"), ("ANEMOI_AMD_EDGE_FOLD", "0"),
+                                        ("ANEMOI_AMD_EMBED_FOLD", "0"), ("ANEMOI_AMD_LN_FOLD", "0"),
+                                        ("ANEMOI_INFERENCE_NUM_CHUNKS", "2")])
+def test_a_setting_that_refuses_the_decoder_fold_gives_the_switch_off_route(monkeypatch, shared_model, name, value):
+    _refused_route_is_the_switch_off_route(monkeypatch, shared_model, "ANEMOI_AMD_DEC_FOLD", name, value)
+
+
+@pytest.mark.parametrize("name,value", [("ANEMOI_AMD_EDGE_FOLD", "0"), ("ANEMOI_INFERENCE_NUM_CHUNKS", "2"),
+                                        ("ANEMOI_AMD_MXFP8", "1")])
+def test_a_setting_that_refuses_the_raw_row_encoder_gives_the_switch_off_route(monkeypatch, shared_model, name, value):
+    _refused_route_is_the_switch_off_route(monkeypatch, shared_model, "ANEMOI_AMD_EDGE_RAW", name, value)
+
+
 @pytest.mark.parametrize("what", ["emb_nodes_dst", "lin_self", "projection", "load_state_dict"])
 def test_a_changed_parameter_rebuilds_the_composed_weight(monkeypatch, what):
     """After an in-place update of a parameter that enters the composed weight (or ``load_state_dict``) the output changes and
