@@ -236,14 +236,42 @@ static int row_stats_launch(const void* x, int64_t ldx, float* stats, int64_t ro
 // One thread per output element; consecutive threads write consecutive columns (coalesced store),
 // reads of x are contiguous runs of V floats.
 // ---------------------------------------------------------------------------------------------
-template <typename T>
+// NaN imputation folded into the I/O glue (anemoi_*_imputed): IMPUTE is a compile-time flag of the kernels below, the plain
+// entry points launch the IMPUTE = false instantiations, whose extra argument is an empty struct and whose code is unchanged.
+// A state column v of grid node g is imputed when fill_src[v] >= 0 and, with a static map, nan_map[g * W + fill_src[v]] is
+// set (whatever the value loaded), without one (dynamic imputer) when the value loaded is NaN.
+struct ImputeArgs {
+  const float* fill_val;        // [V] value written at an imputed point, already in the space the model sees
+  const int32_t* fill_src;      // [V] column of the NaN map per input column, -1: not imputed
+  const uint8_t* nan_map;       // [G, W] row-major, nullptr: dynamic
+  int W;
+  const int32_t* out_nan_src;   // [V_out] (finalize_output only) map column whose points get their NaN back, -1: none
+};
+struct BoundImputeArgs {
+  int64_t G;
+  const uint8_t* nan_map;       // [G, W], never nullptr in an IMPUTE = true launch
+  int W;
+  const int32_t* fin_nan_src;   // [n_fin] map column per fin column, -1: none
+};
+struct NoImpute {};
+template <bool IMPUTE, typename A = ImputeArgs>
+using impute_arg_t = typename std::conditional<IMPUTE, A, NoImpute>::type;
+
+__device__ __forceinline__ bool imputed_point(const ImputeArgs& imp, int v, int64_t g, float raw) {
+  const int s = imp.fill_src[v];
+  if (s < 0) return false;
+  return imp.nan_map != nullptr ? imp.nan_map[g * imp.W + s] != 0 : raw != raw;
+}
+
+template <typename T, bool IMPUTE>
 __global__ __launch_bounds__(256) void assemble_nodes_kernel(const float* __restrict__ x, int B, int T_, int Ens,
                                                              int64_t G, int V, const float* __restrict__ latlons,
                                                              int n_ll, const float* __restrict__ trainable, int n_tr,
                                                              T* __restrict__ out, int64_t ldo,
                                                              const float* __restrict__ in_mul,
                                                              const float* __restrict__ in_add,
-                                                             const int64_t* __restrict__ rows, int64_t n_rows) {
+                                                             const int64_t* __restrict__ rows, int64_t n_rows,
+                                                             const impute_arg_t<IMPUTE> imp) {
   const int64_t total = (rows != nullptr ? n_rows : (int64_t)B * Ens * G) * ldo;
   const int tv = T_ * V;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
@@ -258,7 +286,11 @@ __global__ __launch_bounds__(256) void assemble_nodes_kernel(const float* __rest
       const int64_t b = be / Ens;
       const int t = c / V, v = c - t * V;
       val = x[((((b * T_ + t) * Ens + e) * G) + g) * V + v];
+      [[maybe_unused]] const float raw = val;
       if (in_mul != nullptr) val = val * in_mul[v] + in_add[v];  // InputNormalizer.transform folded into the read
+      if constexpr (IMPUTE) {
+        if (imputed_point(imp, v, g, raw)) val = imp.fill_val[v];
+      }
     } else if (c < tv + n_ll) {
       val = latlons[g * n_ll + (c - tv)];
     } else if (c < tv + n_ll + n_tr) {
@@ -273,14 +305,15 @@ __global__ __launch_bounds__(256) void assemble_nodes_kernel(const float* __rest
 // on the 542 080 x 256 data-grid matrix of config 3, this one is bound by the reads of x).
 // IDX32: every flat index fits 31 bits -- 32-bit divisions (a 64-bit division is ~200 instructions on this ISA; with three
 // of them per thread the kernel was bound by integer ALU work, not by memory: 2.3 TB/s on the data-grid matrix).
-template <typename T, bool IDX32>
+template <typename T, bool IDX32, bool IMPUTE>
 __global__ __launch_bounds__(256) void assemble_nodes8_kernel(const float* __restrict__ x, int B, int T_, int Ens,
                                                               int64_t G, int V, const float* __restrict__ latlons,
                                                               int n_ll, const float* __restrict__ trainable, int n_tr,
                                                               T* __restrict__ out, int ldo8,
                                                               const float* __restrict__ in_mul,
                                                               const float* __restrict__ in_add,
-                                                              const int64_t* __restrict__ rows, int64_t n_rows) {
+                                                              const int64_t* __restrict__ rows, int64_t n_rows,
+                                                              const impute_arg_t<IMPUTE> imp) {
   // rows != nullptr (anemoi_assemble_node_rows, B = Ens = 1): output row i is grid node rows[i]
   const int64_t total = (rows != nullptr ? n_rows : (int64_t)B * Ens * G) * ldo8;
   const int tv = T_ * V;
@@ -314,6 +347,10 @@ __global__ __launch_bounds__(256) void assemble_nodes8_kernel(const float* __res
           val[i] = val[i] * in_mul[v] + in_add[v];
           val[i + 1] = val[i + 1] * in_mul[v + 1] + in_add[v + 1];
         }
+        if constexpr (IMPUTE) {  // the select reads the RAW pair: a dynamic imputer tests the value it has just loaded
+          if (imputed_point(imp, v, g, p.x)) val[i] = imp.fill_val[v];
+          if (imputed_point(imp, v + 1, g, p.y)) val[i + 1] = imp.fill_val[v + 1];
+        }
         v += 2;
         if (v == V) {
           v = 0;
@@ -329,7 +366,11 @@ __global__ __launch_bounds__(256) void assemble_nodes8_kernel(const float* __res
       float r = 0.f;
       if (c < tv) {
         r = x[((((b * T_ + t) * Ens + e) * G) + g) * V + v];
+        [[maybe_unused]] const float raw = r;
         if (in_mul != nullptr) r = r * in_mul[v] + in_add[v];  // InputNormalizer.transform folded into the read
+        if constexpr (IMPUTE) {
+          if (imputed_point(imp, v, g, raw)) r = imp.fill_val[v];
+        }
         if (++v == V) {
           v = 0;
           ++t;
@@ -529,7 +570,9 @@ __global__ __launch_bounds__(256) void advance_input_kernel(float* __restrict__ 
 
 // y[row, c] <- ((y[row, c] + [c prognostic] normalised x[b, T-1, ens, g, src[c]]) - out_add[c]) / out_mul[c]: prognostic
 // residual and InputNormalizer.inverse_transform in one pass over the output
-template <bool IDX32>
+// IMPUTE (anemoi_finalize_output_imputed): the residual adds the IMPUTED value of the last time slice, and after the
+// de-normalisation the points of the static map get their NaN back (out_nan_src; a dynamic imputer restores nothing)
+template <bool IDX32, bool IMPUTE>
 __global__ __launch_bounds__(256) void finalize_output_kernel(float* __restrict__ y, int V_out,
                                                               const float* __restrict__ x, int B, int T_, int Ens,
                                                               int64_t G, int V_in, const int32_t* __restrict__ src,
@@ -537,7 +580,8 @@ __global__ __launch_bounds__(256) void finalize_output_kernel(float* __restrict_
                                                               const float* __restrict__ in_add,
                                                               const float* __restrict__ out_mul,
                                                               const float* __restrict__ out_add,
-                                                              const int64_t* __restrict__ rows, int64_t n_rows) {
+                                                              const int64_t* __restrict__ rows, int64_t n_rows,
+                                                              const impute_arg_t<IMPUTE> imp) {
   // rows != nullptr (anemoi_finalize_output_rows, B = Ens = 1): y holds n_rows rows, row i is grid node rows[i]
   const int64_t total = (rows != nullptr ? n_rows : (int64_t)B * Ens * G) * V_out;
   using I = typename std::conditional<IDX32, unsigned, int64_t>::type;  // (see assemble_nodes8_kernel)
@@ -559,10 +603,23 @@ __global__ __launch_bounds__(256) void finalize_output_kernel(float* __restrict_
         b = (int64_t)(be / (I)Ens);
       }
       float xv = x[((((b * T_ + (T_ - 1)) * Ens + e) * G) + g) * V_in + sv];
+      [[maybe_unused]] const float raw = xv;
       if (in_mul != nullptr) xv = xv * in_mul[sv] + in_add[sv];
+      if constexpr (IMPUTE) {
+        if (imputed_point(imp, sv, g, raw)) xv = imp.fill_val[sv];
+      }
       val += xv;
     }
     if (out_mul != nullptr) val = (val - out_add[c]) / out_mul[c];
+    if constexpr (IMPUTE) {  // (rows == nullptr in every IMPUTE launch)
+      if (imp.nan_map != nullptr && imp.out_nan_src != nullptr) {
+        const int s = imp.out_nan_src[c];
+        if (s >= 0) {
+          const int64_t g = one_be ? (int64_t)row : (int64_t)(row % (I)G);
+          if (imp.nan_map[g * imp.W + s] != 0) val = __builtin_nanf("");
+        }
+      }
+    }
     y[idx] = val;
   }
 }
@@ -572,6 +629,9 @@ __global__ __launch_bounds__(256) void finalize_output_kernel(float* __restrict_
 // reference's chained in-place index assignments define; then the columns listed in fin_* are de-normalised
 // ((y - add) / mul: they were left normalised by anemoi_finalize_output so that the boundings see normalised values).
 // Comparisons (not fminf / fmaxf) keep a NaN a NaN, like torch's relu / hardtanh.
+// IMPUTE (anemoi_bound_output_imputed): a fin column gets the NaNs of its map column back AFTER its de-normalisation -- the
+// kernel that de-normalises a column restores it, so every bounding op above has seen finite values.
+template <bool IMPUTE>
 __global__ __launch_bounds__(256) void bound_output_kernel(float* __restrict__ y, int V_out, int64_t rows, int n_ops,
                                                            const int32_t* __restrict__ op_col,
                                                            const float* __restrict__ op_lo,
@@ -579,7 +639,8 @@ __global__ __launch_bounds__(256) void bound_output_kernel(float* __restrict__ y
                                                            const int32_t* __restrict__ op_mul, int n_fin,
                                                            const int32_t* __restrict__ fin_col,
                                                            const float* __restrict__ fin_mul,
-                                                           const float* __restrict__ fin_add) {
+                                                           const float* __restrict__ fin_add,
+                                                           const impute_arg_t<IMPUTE, BoundImputeArgs> imp) {
   for (int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; row < rows;
        row += (int64_t)gridDim.x * blockDim.x) {
     float* yr = y + row * V_out;
@@ -594,7 +655,12 @@ __global__ __launch_bounds__(256) void bound_output_kernel(float* __restrict__ y
     }
     for (int j = 0; j < n_fin; ++j) {
       const int c = fin_col[j];
-      yr[c] = (yr[c] - fin_add[j]) / fin_mul[j];
+      float v = (yr[c] - fin_add[j]) / fin_mul[j];
+      if constexpr (IMPUTE) {
+        const int s = imp.fin_nan_src[j];
+        if (s >= 0 && imp.nan_map[(row % imp.G) * imp.W + s] != 0) v = __builtin_nanf("");
+      }
+      yr[c] = v;
     }
   }
 }
@@ -686,11 +752,27 @@ int anemoi_row_stats(int dtype, const void* x, int64_t ldx, float* stats, int64_
   return trail::note(rc, "anemoi_row_stats", "stats", ANEMOI_F32, stats, 2, rows, 2, as_stream(stream));
 }
 
+// Argument checks shared by the *_imputed entry points: fill_val / fill_src come together, a map needs them and a width
+static int check_impute(const char* who, const ImputeArgs& imp) {
+  ANEMOI_REQUIRE((imp.fill_val == nullptr) == (imp.fill_src == nullptr), ANEMOI_ERR_INVALID,
+                 "%s: fill_val and fill_src come together", who);
+  ANEMOI_REQUIRE(imp.nan_map == nullptr || imp.fill_src != nullptr, ANEMOI_ERR_INVALID,
+                 "%s: nan_map without fill_val / fill_src", who);
+  ANEMOI_REQUIRE(imp.nan_map == nullptr || imp.W > 0, ANEMOI_ERR_INVALID, "%s: nan_map needs W > 0, got %d", who, imp.W);
+  return ANEMOI_OK;
+}
+
 static int assemble_nodes_impl(const char* who, int dtype, const float* x, int B, int T, int Ens, int64_t G, int V, const float* latlons,
                                int n_ll, const float* trainable, int n_tr, void* out, int64_t ldo, const float* in_mul,
-                               const float* in_add, const int64_t* rows, int64_t n_rows, anemoi_stream_t stream) {
+                               const float* in_add, const int64_t* rows, int64_t n_rows, anemoi_stream_t stream,
+                               const ImputeArgs* imp = nullptr) {
   ANEMOI_REQUIRE((in_mul == nullptr) == (in_add == nullptr), ANEMOI_ERR_INVALID,
                  "anemoi_assemble_nodes: in_mul and in_add come together");
+  if (imp != nullptr) {
+    const int rc = check_impute(who, *imp);
+    if (rc != ANEMOI_OK) return rc;
+    if (imp->fill_src == nullptr) imp = nullptr;  // nothing is imputed: the plain instantiations
+  }
   ANEMOI_REQUIRE(out && B > 0 && Ens > 0 && G >= 0 && T >= 0 && V >= 0 && n_ll >= 0 && n_tr >= 0, ANEMOI_ERR_INVALID,
                  "anemoi_assemble_nodes: bad argument");
   ANEMOI_REQUIRE((x != nullptr) || T * V == 0, ANEMOI_ERR_INVALID, "anemoi_assemble_nodes: x is null");
@@ -702,9 +784,14 @@ static int assemble_nodes_impl(const char* who, int dtype, const float* x, int B
   hipStream_t st = as_stream(stream);
   if (ldo % 8 == 0 && ldo < ((int64_t)1 << 31) && (uintptr_t)out % 16 == 0 && (dtype == ANEMOI_F32 || dtype == ANEMOI_BF16)) {
     const int ldo8 = (int)(ldo / 8);
-#define ANEMOI_ASM8(TT, I32)                                                                                          \
-  hipLaunchKernelGGL((assemble_nodes8_kernel<TT, I32>), dim3(flat_grid(total / 8)), dim3(256), 0, st, x, B, T, Ens, G, V, \
-                     latlons, n_ll, trainable, n_tr, static_cast<TT*>(out), ldo8, in_mul, in_add, rows, n_rows)
+#define ANEMOI_ASM8_(TT, I32, IMP, ARG)                                                                                    \
+  hipLaunchKernelGGL((assemble_nodes8_kernel<TT, I32, IMP>), dim3(flat_grid(total / 8)), dim3(256), 0, st, x, B, T, Ens, G, \
+                     V, latlons, n_ll, trainable, n_tr, static_cast<TT*>(out), ldo8, in_mul, in_add, rows, n_rows, ARG)
+#define ANEMOI_ASM8(TT, I32)                                 \
+  do {                                                       \
+    if (imp != nullptr) ANEMOI_ASM8_(TT, I32, true, *imp);   \
+    else ANEMOI_ASM8_(TT, I32, false, NoImpute{});           \
+  } while (0)
     const bool idx32 = !force_idx64() && total / 8 < ((int64_t)1 << 31) - ((int64_t)1 << 24);  // (+ one grid stride stays below 2^31)
     if (dtype == ANEMOI_F32) {
       if (idx32) ANEMOI_ASM8(float, true);
@@ -714,16 +801,22 @@ static int assemble_nodes_impl(const char* who, int dtype, const float* x, int B
       else ANEMOI_ASM8(bf16_t, false);
     }
 #undef ANEMOI_ASM8
+#undef ANEMOI_ASM8_
     return trail::note(check_launch("anemoi_assemble_nodes"), who, "out", dtype, out, ldo, total / ldo, ldo, st);
   }
-  if (dtype == ANEMOI_F32)
-    hipLaunchKernelGGL((assemble_nodes_kernel<float>), dim3(flat_grid(total)), dim3(256), 0, st, x, B, T, Ens, G, V,
-                       latlons, n_ll, trainable, n_tr, static_cast<float*>(out), ldo, in_mul, in_add, rows, n_rows);
-  else if (dtype == ANEMOI_BF16)
-    hipLaunchKernelGGL((assemble_nodes_kernel<bf16_t>), dim3(flat_grid(total)), dim3(256), 0, st, x, B, T, Ens, G, V,
-                       latlons, n_ll, trainable, n_tr, static_cast<bf16_t*>(out), ldo, in_mul, in_add, rows, n_rows);
-  else
+#define ANEMOI_ASM1(TT, IMP, ARG)                                                                                        \
+  hipLaunchKernelGGL((assemble_nodes_kernel<TT, IMP>), dim3(flat_grid(total)), dim3(256), 0, st, x, B, T, Ens, G, V, latlons, \
+                     n_ll, trainable, n_tr, static_cast<TT*>(out), ldo, in_mul, in_add, rows, n_rows, ARG)
+  if (dtype == ANEMOI_F32) {
+    if (imp != nullptr) ANEMOI_ASM1(float, true, *imp);
+    else ANEMOI_ASM1(float, false, NoImpute{});
+  } else if (dtype == ANEMOI_BF16) {
+    if (imp != nullptr) ANEMOI_ASM1(bf16_t, true, *imp);
+    else ANEMOI_ASM1(bf16_t, false, NoImpute{});
+  } else {
     return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_assemble_nodes: dtype %d", dtype);
+  }
+#undef ANEMOI_ASM1
   return trail::note(check_launch("anemoi_assemble_nodes"), who, "out", dtype, out, ldo, total / ldo, ldo, st);
 }
 
@@ -732,6 +825,15 @@ int anemoi_assemble_nodes(int dtype, const float* x, int B, int T, int Ens, int6
                           const float* in_add, anemoi_stream_t stream) {
   return assemble_nodes_impl("anemoi_assemble_nodes", dtype, x, B, T, Ens, G, V, latlons, n_ll, trainable, n_tr, out, ldo, in_mul, in_add, nullptr, 0,
                              stream);
+}
+
+int anemoi_assemble_nodes_imputed(int dtype, const float* x, int B, int T, int Ens, int64_t G, int V, const float* latlons,
+                                  int n_ll, const float* trainable, int n_tr, void* out, int64_t ldo, const float* in_mul,
+                                  const float* in_add, const float* fill_val, const int32_t* fill_src,
+                                  const uint8_t* nan_map, int W, anemoi_stream_t stream) {
+  const ImputeArgs imp{fill_val, fill_src, nan_map, W, nullptr};
+  return assemble_nodes_impl("anemoi_assemble_nodes_imputed", dtype, x, B, T, Ens, G, V, latlons, n_ll, trainable, n_tr, out, ldo,
+                             in_mul, in_add, nullptr, 0, stream, &imp);
 }
 
 int anemoi_assemble_node_rows(int dtype, const float* x, int T, int64_t G, int V, const float* latlons, int n_ll,
@@ -881,19 +983,30 @@ int anemoi_advance_input(float* x, int B, int T, int Ens, int64_t G, int V_in, c
 
 static int finalize_output_impl(const char* who, float* y, int V_out, const float* x, int B, int T, int Ens, int64_t G, int V_in,
                                 const int32_t* src, const float* in_mul, const float* in_add, const float* out_mul,
-                                const float* out_add, const int64_t* rows, int64_t n_rows, anemoi_stream_t stream) {
+                                const float* out_add, const int64_t* rows, int64_t n_rows, anemoi_stream_t stream,
+                                const ImputeArgs* imp = nullptr) {
   ANEMOI_REQUIRE(y && x && src && B > 0 && T > 0 && Ens > 0 && G >= 0 && V_in > 0 && V_out > 0, ANEMOI_ERR_INVALID,
                  "anemoi_finalize_output: bad argument");
+  if (imp != nullptr) {
+    const int rc = check_impute(who, *imp);
+    if (rc != ANEMOI_OK) return rc;
+    if (imp->fill_src == nullptr) imp = nullptr;  // nothing is imputed, nothing to restore: the plain instantiations
+  }
   ANEMOI_REQUIRE((in_mul == nullptr) == (in_add == nullptr) && (out_mul == nullptr) == (out_add == nullptr),
                  ANEMOI_ERR_INVALID, "anemoi_finalize_output: mul and add come together");
   const int64_t total = (rows != nullptr ? n_rows : (int64_t)B * Ens * G) * V_out;
   if (total == 0) return ANEMOI_OK;
-  if (!force_idx64() && total < ((int64_t)1 << 31) - ((int64_t)1 << 24))
-    hipLaunchKernelGGL(finalize_output_kernel<true>, dim3(flat_grid(total)), dim3(256), 0, as_stream(stream), y, V_out, x, B,
-                       T, Ens, G, V_in, src, in_mul, in_add, out_mul, out_add, rows, n_rows);
-  else
-    hipLaunchKernelGGL(finalize_output_kernel<false>, dim3(flat_grid(total)), dim3(256), 0, as_stream(stream), y, V_out, x, B,
-                       T, Ens, G, V_in, src, in_mul, in_add, out_mul, out_add, rows, n_rows);
+#define ANEMOI_FIN(I32, IMP, ARG)                                                                                        \
+  hipLaunchKernelGGL((finalize_output_kernel<I32, IMP>), dim3(flat_grid(total)), dim3(256), 0, as_stream(stream), y, V_out, \
+                     x, B, T, Ens, G, V_in, src, in_mul, in_add, out_mul, out_add, rows, n_rows, ARG)
+  if (!force_idx64() && total < ((int64_t)1 << 31) - ((int64_t)1 << 24)) {
+    if (imp != nullptr) ANEMOI_FIN(true, true, *imp);
+    else ANEMOI_FIN(true, false, NoImpute{});
+  } else {
+    if (imp != nullptr) ANEMOI_FIN(false, true, *imp);
+    else ANEMOI_FIN(false, false, NoImpute{});
+  }
+#undef ANEMOI_FIN
   return trail::note(check_launch("anemoi_finalize_output"), who, "out", ANEMOI_F32, y, V_out, total / V_out, V_out,
                      as_stream(stream));
 }
@@ -902,6 +1015,15 @@ int anemoi_finalize_output(float* y, int V_out, const float* x, int B, int T, in
                            const int32_t* src, const float* in_mul, const float* in_add, const float* out_mul,
                            const float* out_add, anemoi_stream_t stream) {
   return finalize_output_impl("anemoi_finalize_output", y, V_out, x, B, T, Ens, G, V_in, src, in_mul, in_add, out_mul, out_add, nullptr, 0, stream);
+}
+
+int anemoi_finalize_output_imputed(float* y, int V_out, const float* x, int B, int T, int Ens, int64_t G, int V_in,
+                                   const int32_t* src, const float* in_mul, const float* in_add, const float* out_mul,
+                                   const float* out_add, const float* fill_val, const int32_t* fill_src,
+                                   const uint8_t* nan_map, int W, const int32_t* out_nan_src, anemoi_stream_t stream) {
+  const ImputeArgs imp{fill_val, fill_src, nan_map, W, nan_map != nullptr ? out_nan_src : nullptr};
+  return finalize_output_impl("anemoi_finalize_output_imputed", y, V_out, x, B, T, Ens, G, V_in, src, in_mul, in_add, out_mul,
+                              out_add, nullptr, 0, stream, &imp);
 }
 
 int anemoi_finalize_output_rows(float* y, int V_out, const float* x, int T, int64_t G, int V_in, const int32_t* src,
@@ -913,20 +1035,48 @@ int anemoi_finalize_output_rows(float* y, int V_out, const float* x, int T, int6
   return finalize_output_impl("anemoi_finalize_output_rows", y, V_out, x, 1, T, 1, G, V_in, src, in_mul, in_add, out_mul, out_add, rows, n_rows, stream);
 }
 
-int anemoi_bound_output(float* y, int V_out, int64_t rows, int n_ops, const int32_t* op_col, const float* op_lo,
-                        const float* op_hi, const int32_t* op_mul, int n_fin, const int32_t* fin_col,
-                        const float* fin_mul, const float* fin_add, anemoi_stream_t stream) {
+static int bound_output_impl(const char* who, float* y, int V_out, int64_t rows, int n_ops, const int32_t* op_col,
+                             const float* op_lo, const float* op_hi, const int32_t* op_mul, int n_fin,
+                             const int32_t* fin_col, const float* fin_mul, const float* fin_add, anemoi_stream_t stream,
+                             const BoundImputeArgs* imp = nullptr) {
   ANEMOI_REQUIRE(y && V_out > 0 && rows >= 0 && n_ops >= 0 && n_fin >= 0, ANEMOI_ERR_INVALID,
                  "anemoi_bound_output: bad argument");
   ANEMOI_REQUIRE(n_ops == 0 || (op_col && op_lo && op_hi && op_mul), ANEMOI_ERR_INVALID,
                  "anemoi_bound_output: null op list");
   ANEMOI_REQUIRE(n_fin == 0 || (fin_col && fin_mul && fin_add), ANEMOI_ERR_INVALID,
                  "anemoi_bound_output: null de-normalisation list");
+  if (imp != nullptr) {
+    ANEMOI_REQUIRE(imp->nan_map == nullptr || imp->W > 0, ANEMOI_ERR_INVALID, "%s: nan_map needs W > 0, got %d", who, imp->W);
+    ANEMOI_REQUIRE(imp->nan_map == nullptr || n_fin == 0 || imp->fin_nan_src != nullptr, ANEMOI_ERR_INVALID,
+                   "%s: nan_map and fin_nan_src come together", who);
+    ANEMOI_REQUIRE(imp->nan_map == nullptr || (imp->G > 0 && rows % imp->G == 0), ANEMOI_ERR_INVALID,
+                   "%s: rows %lld is not a multiple of the grid size G = %lld", who, (long long)rows, (long long)imp->G);
+    if (imp->nan_map == nullptr || n_fin == 0) imp = nullptr;  // dynamic imputer / no column to restore: the plain instantiation
+  }
   if (rows == 0 || (n_ops == 0 && n_fin == 0)) return ANEMOI_OK;
-  hipLaunchKernelGGL(bound_output_kernel, dim3(flat_grid(rows)), dim3(256), 0, as_stream(stream), y, V_out, rows, n_ops,
-                     op_col, op_lo, op_hi, op_mul, n_fin, fin_col, fin_mul, fin_add);
-  return trail::note(check_launch("anemoi_bound_output"), "anemoi_bound_output", "out", ANEMOI_F32, y, V_out, rows, V_out,
-                     as_stream(stream));
+  if (imp != nullptr)
+    hipLaunchKernelGGL(bound_output_kernel<true>, dim3(flat_grid(rows)), dim3(256), 0, as_stream(stream), y, V_out, rows,
+                       n_ops, op_col, op_lo, op_hi, op_mul, n_fin, fin_col, fin_mul, fin_add, *imp);
+  else
+    hipLaunchKernelGGL(bound_output_kernel<false>, dim3(flat_grid(rows)), dim3(256), 0, as_stream(stream), y, V_out, rows,
+                       n_ops, op_col, op_lo, op_hi, op_mul, n_fin, fin_col, fin_mul, fin_add, NoImpute{});
+  return trail::note(check_launch("anemoi_bound_output"), who, "out", ANEMOI_F32, y, V_out, rows, V_out, as_stream(stream));
+}
+
+int anemoi_bound_output(float* y, int V_out, int64_t rows, int n_ops, const int32_t* op_col, const float* op_lo,
+                        const float* op_hi, const int32_t* op_mul, int n_fin, const int32_t* fin_col,
+                        const float* fin_mul, const float* fin_add, anemoi_stream_t stream) {
+  return bound_output_impl("anemoi_bound_output", y, V_out, rows, n_ops, op_col, op_lo, op_hi, op_mul, n_fin, fin_col, fin_mul,
+                           fin_add, stream);
+}
+
+int anemoi_bound_output_imputed(float* y, int V_out, int64_t rows, int n_ops, const int32_t* op_col, const float* op_lo,
+                                const float* op_hi, const int32_t* op_mul, int n_fin, const int32_t* fin_col,
+                                const float* fin_mul, const float* fin_add, int64_t G, const uint8_t* nan_map, int W,
+                                const int32_t* fin_nan_src, anemoi_stream_t stream) {
+  const BoundImputeArgs imp{G, nan_map, W, fin_nan_src};
+  return bound_output_impl("anemoi_bound_output_imputed", y, V_out, rows, n_ops, op_col, op_lo, op_hi, op_mul, n_fin, fin_col,
+                           fin_mul, fin_add, stream, &imp);
 }
 
 int anemoi_abi_version(void) { return 55; }

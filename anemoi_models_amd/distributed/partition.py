@@ -381,6 +381,8 @@ def sharded_forward(model, x: Tensor, group, input_affine=None, output_affine=No
     skipped and ``(y_local [rows, V_out] f32 WITHOUT the prognostic residual, shard plan)`` is returned; of ``x`` only
     the grid rows this rank's encoder and decoder read (``enc_src_ids``, ``dec_dst_ids``) need to be valid."""
     _refuse_truncation(model)
+    if getattr(input_affine, "impute", None) is not None:
+        raise NotImplementedError("the node-partitioned forward takes no imputation (predict_step takes its generic route)")
     if torch.is_grad_enabled() and any(p.requires_grad for p in model.parameters()):
         if input_affine is not None or output_affine is not None:
             raise NotImplementedError("input_affine / output_affine belong to the inference interface (predict_step)")

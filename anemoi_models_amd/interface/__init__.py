@@ -45,11 +45,12 @@ class AnemoiModelInterface(torch.nn.Module):
     def predict_step(self, batch: torch.Tensor) -> torch.Tensor:
         """``[batch, time, grid, variables]`` (physical values, input variables) -> de-normalised prediction
         ``[batch, ensemble = 1, grid, output variables]`` (reference interface/__init__.py:97-123)."""
-        fused = self._normalizer_affines(batch)
+        fused = self._fused_route(batch)
         if fused is not None:
-            # the only processor is an InputNormalizer: its per-variable affine maps ride on the first and the last
-            # kernel of the forward (anemoi_assemble_nodes / anemoi_finalize_output) -- two passes over the grid state
-            # and two over the prediction less, same arithmetic
+            # the processors are an InputNormalizer, alone or with one NaN imputer: the per-variable affine maps, the
+            # imputer's select and its NaN restore ride on the first and the last kernel of the forward (anemoi_assemble_nodes /
+            # anemoi_finalize_output / anemoi_bound_output and their _imputed forms) -- no pass of its own over the grid
+            # state or the prediction, same arithmetic
             with torch.no_grad():
                 assert len(batch.shape) == 4, (
                     f"The input tensor has an incorrect shape: expected a 4-dimensional tensor, got {batch.shape}!")
@@ -67,26 +68,81 @@ class AnemoiModelInterface(torch.nn.Module):
         """``((mul_in, add_in), (mul_out, add_out))`` when pre / post-processing is exactly one ``InputNormalizer``
         acting on the model's input / output variable lists and the model accepts them; else ``None``.
         ``ANEMOI_AMD_FUSE_NORMALIZER=0`` turns the fusion off (A/B)."""
+        from ..preprocessing.normalizer import InputNormalizer
+
+        procs = list(self.pre_processors.processors.values())
+        if len(procs) != 1 or type(procs[0]) is not InputNormalizer:
+            return None
+        return self._affines_of(procs[0], batch)
+
+    def _affines_of(self, norm, batch: torch.Tensor):
+        """The conditions every fused route shares, then the affine maps of ``norm`` on the model's variable lists."""
         import inspect
         import os
-
-        from ..preprocessing.normalizer import InputNormalizer
 
         mode = os.environ.get("ANEMOI_AMD_FUSE_NORMALIZER", "1")
         if mode == "0" or batch.dim() != 4 or not (batch.is_cuda or mode == "force"):
             return None
-        procs = list(self.pre_processors.processors.values())
-        if len(procs) != 1 or type(procs[0]) is not InputNormalizer:
-            return None
         if "input_affine" not in inspect.signature(self.model.forward).parameters:
             return None
-        norm = procs[0]
         if batch.shape[-1] != norm._input_idx.numel():  # the full-variable layout is left to the generic route
             return None
         if self.pre_processors.first_run:  # keep the reference's one-off NaN check of the first processed batch
             return None
         i_in, i_out = norm._input_idx.long(), norm._output_idx.long()
         return ((norm._norm_mul[i_in], norm._norm_add[i_in]), (norm._norm_mul[i_out], norm._norm_add[i_out]))
+
+    def _fused_route(self, batch: torch.Tensor):
+        """Route query of :meth:`predict_step`: ``(input_affine, output_affine)`` for ``model(x, input_affine=...,
+        output_affine=...)`` when pre / post-processing rides on the forward's I/O kernels, ``None`` for the generic route.
+
+        Fused: exactly one ``InputNormalizer`` (:meth:`_normalizer_affines`), or one ``InputNormalizer`` and one NaN imputer of
+        ``preprocessing.imputer`` in either order -- then ``input_affine`` is an ``ImputedAffine`` carrying the imputer's
+        ``Imputation``.  With an imputer the model must have the plain residual and a bounding list that compiles, and a
+        static imputer its ``nan_locations`` on a grid of the batch's size with every map column inside the map.  The first
+        call is always generic: it fixes ``nan_locations`` / ``loss_mask_training``, which this route never touches."""
+        from ..layers.bounding import compile_boundings
+        from ..preprocessing import imputer as imp_mod
+        from ..preprocessing.normalizer import InputNormalizer
+
+        procs = list(self.pre_processors.processors.values())
+        if len(procs) == 1:
+            return self._normalizer_affines(batch)
+        # (exact types: a subclass may redefine transform / inverse_transform; BaseImputer itself imputes nothing)
+        kinds = (imp_mod.InputImputer, imp_mod.ConstantImputer, imp_mod.DynamicInputImputer, imp_mod.DynamicConstantImputer)
+        if len(procs) != 2 or sorted(type(p) is InputNormalizer for p in procs) != [False, True]:
+            return None
+        imputer_first = type(procs[1]) is InputNormalizer
+        imputer, norm = (procs[0], procs[1]) if imputer_first else (procs[1], procs[0])
+        if not any(type(imputer) is k for k in kinds):
+            return None
+        affines = self._affines_of(norm, batch)
+        if affines is None:
+            return None
+        if getattr(self.model, "_truncation", None) is not None:
+            return None
+        if len(getattr(self.model, "boundings", ())) > 0 and compile_boundings(self.model.boundings) is None:
+            return None
+        dynamic = isinstance(imputer, imp_mod.DynamicMixin)
+        if not dynamic:
+            nan_map = imputer.nan_locations
+            if nan_map is None or nan_map.dim() != 2 or nan_map.shape[0] != batch.shape[-2]:
+                return None
+            if any(src >= nan_map.shape[1] for src in imputer.index_training_input):
+                return None  # the generic route fails on it exactly as the reference does
+        (mul_in, add_in), out_affine = affines
+        key = (id(imputer), str(batch.device), imputer_first, self._version_of(norm),
+               None if dynamic else (imputer.nan_locations.data_ptr(), tuple(imputer.nan_locations.shape)))
+        cache = self.__dict__.setdefault("_imputation_cache", {})
+        hit = cache.get("imputation")
+        if hit is None or hit[0] != key:  # built once per (imputer, device), rebuilt when its sources change
+            hit = (key, imputer.imputation(batch.device, (mul_in, add_in) if imputer_first else None))
+            cache["imputation"] = hit
+        return imp_mod.ImputedAffine(mul_in, add_in, hit[1]), out_affine
+
+    @staticmethod
+    def _version_of(norm) -> tuple:
+        return (norm._norm_mul.data_ptr(), norm._norm_mul._version, norm._norm_add.data_ptr(), norm._norm_add._version)
 
     # ------------------------------------------------------------------ autoregressive rollout (BASELINE config 4)
     def _advance_map(self, device) -> torch.Tensor:

@@ -210,6 +210,12 @@ class AnemoiModelEncProcDec(nn.Module):
         key = ("residual_src", str(y.device))
         out_dtype = x.dtype
         truncation = getattr(self, "_truncation", None)
+        # NaN imputation riding on the input affine (preprocessing.imputer.ImputedAffine, from predict_step): the residual
+        # adds the imputed state, and each output column gets its NaNs back from the kernel that de-normalises it
+        impute = getattr(input_affine, "impute", None)
+        if impute is not None and (truncation is not None or rows is not None or output_affine is None):
+            raise NotImplementedError("an imputation runs with the plain residual, the whole grid and an output affine "
+                                      "(AnemoiModelInterface.predict_step takes its generic route otherwise)")
         if truncation is not None:
             # truncated skip connection: y += A_up (A_down x') on the raw x (input affine on load), two launches straight out
             # of x and into y; the rest of this function then runs with a column map that adds nothing
@@ -231,9 +237,21 @@ class AnemoiModelEncProcDec(nn.Module):
             src[torch.as_tensor(self._internal_output_idx).long()] = torch.as_tensor(self._internal_input_idx).to(torch.int32)
             self._idx_cache[key] = src.to(y.device)
         if len(self.boundings) == 0:
-            ops.finalize_output(y, x, self._idx_cache[key], input_affine, output_affine, rows=rows)
+            if impute is not None:
+                ops.finalize_output(y, x, self._idx_cache[key], input_affine, output_affine, impute=impute)
+            else:
+                ops.finalize_output(y, x, self._idx_cache[key], input_affine, output_affine, rows=rows)
             return y if y.dtype == out_dtype else y.to(out_dtype)
         plan = self._bounding_plan(y.device, output_affine)
+        if plan is not None and impute is not None:
+            # bounded columns stay finite (and normalised) through finalize_output; bound_output restores them at its end
+            op_lists, masked_affine, fin = plan
+            imp_fin, imp_bound = self._imputation_split(impute, fin[0])
+            ops.finalize_output(y, x, self._idx_cache[key], input_affine, masked_affine, impute=imp_fin)
+            ops.bound_output(y, *op_lists, fin=fin, impute=imp_bound)
+            return y if y.dtype == out_dtype else y.to(out_dtype)
+        if impute is not None:
+            raise NotImplementedError("an imputation needs a bounding list that layers.bounding.compile_boundings knows")
         if plan is None:  # a bounding class this package does not know: call the modules, as the reference does
             ops.finalize_output(y, x, self._idx_cache[key], input_affine, None, rows=rows)
             if y.dtype != out_dtype:
@@ -279,6 +297,21 @@ class AnemoiModelEncProcDec(nn.Module):
             self._idx_cache[key] = (lists, masked, fin)
         return self._idx_cache[key]
 
+    def _imputation_split(self, impute, fin_cols: Tensor):
+        """``impute`` for ``finalize_output`` (restores the columns it de-normalises: all but ``fin_cols``) and for
+        ``bound_output`` (one entry per ``fin`` column); cached per imputation and bounding plan."""
+        key = ("imputation_split", id(impute), fin_cols.data_ptr())
+        hit = self._idx_cache.get(key)
+        if hit is None or hit[0] is not impute:  # (the entry holds the object, so its id cannot be re-used while cached)
+            if impute.out_nan_src is None:
+                hit = (impute, impute, impute)
+            else:
+                kept = impute.out_nan_src.clone()
+                kept[fin_cols.long()] = -1
+                hit = (impute, impute.restoring(kept), impute.restoring(impute.out_nan_src[fin_cols.long()].contiguous()))
+            self._idx_cache[key] = hit
+        return hit[1], hit[2]
+
     def _training_forward(self, x: Tensor, input_affine=None, output_affine=None) -> Tensor:
         """Forward WITH an autograd graph (anemoi-training calls ``.backward()`` on a loss of the result): the reference's
         own composition -- encoder, processor, skip, decoder, residual, boundings -- through the sub-modules' ``forward``
@@ -286,6 +319,8 @@ class AnemoiModelEncProcDec(nn.Module):
         kernels, mappers and processor chunks checkpointed as in the reference).  SURVEY section 8f-1."""
         from .. import training
 
+        if getattr(input_affine, "impute", None) is not None:
+            raise NotImplementedError("an imputation belongs to the inference interface (predict_step), not to the training forward")
         if input_affine is not None or output_affine is not None:
             raise NotImplementedError("input_affine / output_affine belong to the inference interface (predict_step)")
         return training.model_forward(self, x)
@@ -317,8 +352,13 @@ class AnemoiModelEncProcDec(nn.Module):
         width = self.multi_step * self.num_input_channels + na.attr_ndims[data]
         fold = self._embed_fold(dtype)
         tr_data = na.trainable_tensors[data].trainable
+        impute = getattr(input_affine, "impute", None)
+        if impute is not None and (getattr(self, "_truncation", None) is not None or output_affine is None):
+            raise NotImplementedError("an imputation runs with the plain residual and an output affine "
+                                      "(AnemoiModelInterface.predict_step takes its generic route otherwise)")
         x_data = ops.assemble_nodes(x, na.latlons(data), self._with_ones(tr_data, grid, fold), batch_size, dtype,
-                                    ld_out=self._feature_ld(width + int(fold), dtype, fold), in_affine=input_affine)
+                                    ld_out=self._feature_ld(width + int(fold), dtype, fold), in_affine=input_affine,
+                                    **({} if impute is None else {"impute": impute}))
         # mesh rows live in an internal Morton order (gather locality of the edge kernels); only the tiny
         # per-node attribute tables are permuted, the mesh never leaves the model
         order, inv = self._mesh_order(x.device)

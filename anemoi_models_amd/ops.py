@@ -848,12 +848,39 @@ def mhsa_backward(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, batch_siz
     return dqkv
 
 
+def _impute_args(who: str, impute, x: Tensor, n_out: Optional[int] = None):
+    """``(fill_val, fill_src, nan_map | None, W, out_nan_src | None)`` of an imputation (``preprocessing.imputer.Imputation``:
+    device tensors ``fill_val`` f32 ``[V]``, ``fill_src`` int32 ``[V]``, ``nan_map`` bool / uint8 ``[G, W]`` or ``None`` for a
+    dynamic imputer, ``out_nan_src`` int32 or ``None``, and ``W``) checked against the state ``x`` ``[B, T, Ens, G, V]``."""
+    v, g = x.shape[-1], x.shape[-2]
+    fv, fs, nm, ons = impute.fill_val, impute.fill_src, impute.nan_map, impute.out_nan_src
+    _dev(fv, fs, nm, ons)
+    if fv.dtype != torch.float32 or fs.dtype != torch.int32 or fv.shape != (v,) or fs.shape != (v,) or \
+            not fv.is_contiguous() or not fs.is_contiguous():
+        raise ValueError(f"{who}: impute needs f32 fill_val and int32 fill_src with one entry per input variable ({v})")
+    w = int(impute.W)
+    if nm is not None:
+        if nm.dtype not in (torch.bool, torch.uint8) or not nm.is_contiguous() or tuple(nm.shape) != (g, w) or w <= 0:
+            raise ValueError(f"{who}: impute.nan_map must be a contiguous bool / uint8 [{g}, W = {w}] tensor, got "
+                             f"{nm.dtype} {tuple(nm.shape)}")
+    if ons is not None and n_out is not None:
+        if ons.dtype != torch.int32 or ons.shape != (n_out,) or not ons.is_contiguous():
+            raise ValueError(f"{who}: impute.out_nan_src must be int32 with {n_out} entries")
+    return fv, fs, nm, w, ons
+
+
 def assemble_nodes(x: Optional[Tensor], latlons: Tensor, trainable: Optional[Tensor], batch_size: int,
                    dtype: torch.dtype, ld_out: Optional[int] = None, ensemble: int = 1, in_affine=None,
-                   rows: Optional[Tensor] = None) -> Tensor:
+                   rows: Optional[Tensor] = None, impute=None) -> Tensor:
     """Rows ``(b, ens, g)`` of ``[x (time-major) | latlons | trainable | 0-pad]`` in ``dtype``.  ``in_affine`` =
     ``(mul, add)`` f32 ``[V]``: ``x`` is the raw state, normalised as ``x * mul + add`` while it is read.
-    ``rows`` (int64 node ids; batch 1, ensemble 1): only those nodes' rows, in that order (``anemoi_assemble_node_rows``)."""
+    ``rows`` (int64 node ids; batch 1, ensemble 1): only those nodes' rows, in that order (``anemoi_assemble_node_rows``).
+    ``impute`` (``preprocessing.imputer.Imputation``): NaN imputation as a select on the read
+    (``anemoi_assemble_nodes_imputed``); not with ``rows``."""
+    if impute is not None and rows is not None:
+        raise ValueError("assemble_nodes: the row-list kernel takes no imputation (rows= with impute=)")
+    if impute is not None and x is None:
+        raise ValueError("assemble_nodes: impute= needs a state x")
     _dev(x, latlons, trainable, rows)
     mul = add = None
     if in_affine is not None and x is not None:
@@ -886,6 +913,13 @@ def assemble_nodes(x: Optional[Tensor], latlons: Tensor, trainable: Optional[Ten
         _lib.check(st, "anemoi_assemble_node_rows")
         return out
     out = torch.empty((b * ens * g, ld), dtype=dtype, device=latlons.device)
+    if impute is not None:
+        fv, fs, nm, w, _ = _impute_args("assemble_nodes", impute, x)
+        st = _lib.load().anemoi_assemble_nodes_imputed(dtype_code(dtype), _ptr(x), b, t, ens, g, v, latlons.data_ptr(), n_ll,
+                                                       _ptr(trainable), n_tr, out.data_ptr(), ld, _ptr(mul), _ptr(add),
+                                                       fv.data_ptr(), fs.data_ptr(), _ptr(nm), w, _stream())
+        _lib.check(st, "anemoi_assemble_nodes_imputed")
+        return out
     st = _lib.load().anemoi_assemble_nodes(dtype_code(dtype), _ptr(x), b, t, ens, g, v, latlons.data_ptr(), n_ll,
                                            _ptr(trainable), n_tr, out.data_ptr(), ld, _ptr(mul), _ptr(add), _stream())
     _lib.check(st, "anemoi_assemble_nodes")
@@ -893,11 +927,16 @@ def assemble_nodes(x: Optional[Tensor], latlons: Tensor, trainable: Optional[Ten
 
 
 def finalize_output(y: Tensor, x: Tensor, src: Tensor, in_affine=None, out_affine=None,
-                    rows: Optional[Tensor] = None) -> Tensor:
+                    rows: Optional[Tensor] = None, impute=None) -> Tensor:
     """In place on the f32 output ``y`` ``[B, Ens, G, V_out]``: prognostic residual from the last time slice of ``x``
     (``src`` int32 ``[V_out]``: input column per output column, -1 = none; ``in_affine`` normalises a raw ``x`` on the
     fly) and, with ``out_affine = (mul, add)``, the de-normalisation ``(y - add) / mul``.  ``rows`` (int64 node ids; batch
-    1, ensemble 1): ``y`` holds only those nodes' rows ``[..., len(rows), V_out]`` (``anemoi_finalize_output_rows``)."""
+    1, ensemble 1): ``y`` holds only those nodes' rows ``[..., len(rows), V_out]`` (``anemoi_finalize_output_rows``).
+    ``impute`` (``preprocessing.imputer.Imputation``): the residual adds the imputed value of the raw state, and after the
+    de-normalisation the columns of ``impute.out_nan_src`` (int32 ``[V_out]``, -1 = none) get the NaNs of the static map back
+    (``anemoi_finalize_output_imputed``); not with ``rows``."""
+    if impute is not None and rows is not None:
+        raise ValueError("finalize_output: the row-list kernel takes no imputation (rows= with impute=)")
     _dev(y, x, src, rows)
     if y.dtype != torch.float32 or not y.is_contiguous():
         raise ValueError("finalize_output: y must be contiguous float32")
@@ -920,6 +959,15 @@ def finalize_output(y: Tensor, x: Tensor, src: Tensor, in_affine=None, out_affin
                                                      _stream())
         _lib.check(st, "anemoi_finalize_output_rows")
         return y
+    if impute is not None:
+        fv, fs, nm, w, ons = _impute_args("finalize_output", impute, x, y.shape[-1])
+        if y.numel() != b * ens * g * y.shape[-1]:
+            raise ValueError("finalize_output: y does not hold one row per (batch, member, grid node) of x")
+        st = _lib.load().anemoi_finalize_output_imputed(y.data_ptr(), y.shape[-1], x.data_ptr(), b, t, ens, g, v_in,
+                                                        src.data_ptr(), _ptr(im), _ptr(ia), _ptr(om), _ptr(oa),
+                                                        fv.data_ptr(), fs.data_ptr(), _ptr(nm), w, _ptr(ons), _stream())
+        _lib.check(st, "anemoi_finalize_output_imputed")
+        return y
     st = _lib.load().anemoi_finalize_output(y.data_ptr(), y.shape[-1], x.data_ptr(), b, t, ens, g, v_in, src.data_ptr(),
                                             _ptr(im), _ptr(ia), _ptr(om), _ptr(oa), _stream())
     _lib.check(st, "anemoi_finalize_output")
@@ -927,9 +975,12 @@ def finalize_output(y: Tensor, x: Tensor, src: Tensor, in_affine=None, out_affin
 
 
 def bound_output(y: Tensor, op_col: Tensor, op_lo: Tensor, op_hi: Tensor, op_mul: Tensor,
-                 fin: Optional[tuple] = None) -> Tensor:
+                 fin: Optional[tuple] = None, impute=None) -> Tensor:
     """In place on the f32 output ``y`` ``[..., V_out]``: the ordered bounding ops (see ``layers.bounding.compile_boundings``)
-    and, with ``fin = (cols int32, mul f32, add f32)``, the de-normalisation of those columns afterwards."""
+    and, with ``fin = (cols int32, mul f32, add f32)``, the de-normalisation of those columns afterwards.
+    ``impute`` (``preprocessing.imputer.Imputation`` whose ``out_nan_src`` holds ONE ENTRY PER ``fin`` COLUMN, -1 = none; ``y``
+    is ``[..., G, V_out]`` with the map's ``G``): those columns get the NaNs of the static map back after their
+    de-normalisation (``anemoi_bound_output_imputed``)."""
     _dev(y, op_col, op_lo, op_hi, op_mul)
     if y.dtype != torch.float32 or not y.is_contiguous():
         raise ValueError("bound_output: y must be contiguous float32")
@@ -945,6 +996,20 @@ def bound_output(y: Tensor, op_col: Tensor, op_lo: Tensor, op_hi: Tensor, op_mul
                 fm.numel() != fc.numel() or fa.numel() != fc.numel():
             raise ValueError("bound_output: fin = (int32 columns, f32 mul, f32 add) of one length")
     v_out = y.shape[-1]
+    if impute is not None and impute.nan_map is not None:
+        nm, ons, n_fin = impute.nan_map, impute.out_nan_src, 0 if fc is None else fc.numel()
+        _dev(nm, ons)
+        if y.dim() < 2 or nm.dtype not in (torch.bool, torch.uint8) or not nm.is_contiguous() or \
+                tuple(nm.shape) != (y.shape[-2], int(impute.W)) or int(impute.W) <= 0:
+            raise ValueError(f"bound_output: impute.nan_map must be a contiguous bool / uint8 [G = {y.shape[-2]}, W] tensor")
+        if n_fin and (ons is None or ons.dtype != torch.int32 or ons.shape != (n_fin,) or not ons.is_contiguous()):
+            raise ValueError(f"bound_output: impute.out_nan_src must be int32 with one entry per fin column ({n_fin})")
+        st = _lib.load().anemoi_bound_output_imputed(y.data_ptr(), v_out, y.numel() // max(v_out, 1), n_ops, _ptr(op_col),
+                                                     _ptr(op_lo), _ptr(op_hi), _ptr(op_mul), n_fin, _ptr(fc), _ptr(fm),
+                                                     _ptr(fa), y.shape[-2], nm.data_ptr(), int(impute.W),
+                                                     _ptr(ons) if n_fin else None, _stream())
+        _lib.check(st, "anemoi_bound_output_imputed")
+        return y
     st = _lib.load().anemoi_bound_output(y.data_ptr(), v_out, y.numel() // max(v_out, 1), n_ops, _ptr(op_col),
                                          _ptr(op_lo), _ptr(op_hi), _ptr(op_mul), 0 if fc is None else fc.numel(),
                                          _ptr(fc), _ptr(fm), _ptr(fa), _stream())

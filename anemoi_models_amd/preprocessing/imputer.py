@@ -22,6 +22,59 @@ from torch import Tensor
 from . import BasePreprocessor
 
 
+class Imputation:
+    """What the I/O kernels need to impute while they read the raw state and to put the NaNs back while they write the
+    prediction (``ops.assemble_nodes`` / ``finalize_output`` / ``bound_output``, keyword ``impute``), on one device:
+
+    * ``fill_val`` f32 ``[V_in]``: the value written at an imputed point, in the space the model sees;
+    * ``fill_src`` int32 ``[V_in]``: column of the NaN map per input column, -1 = not imputed;
+    * ``nan_map`` bool ``[G, W]`` (the imputer's own ``nan_locations``, not a copy) or ``None`` for a dynamic imputer;
+    * ``out_nan_src`` int32 ``[V_out]``: map column whose NaNs an output column gets back, -1 = none (``None``: dynamic);
+    * ``W``: width of the map.
+
+    The constructor takes the three index lists as Python lists and refuses a map column outside ``[0, W)`` before anything
+    reaches a kernel."""
+
+    __slots__ = ("fill_val", "fill_src", "nan_map", "out_nan_src", "W")
+
+    def __init__(self, fill_val: Tensor, fill_src, nan_map: Optional[Tensor], out_nan_src=None, W: Optional[int] = None) -> None:
+        device = fill_val.device
+        if nan_map is not None:
+            if nan_map.dim() != 2 or nan_map.dtype not in (torch.bool, torch.uint8) or not nan_map.is_contiguous():
+                raise ValueError("Imputation: nan_map must be a contiguous bool / uint8 [grid, W] tensor")
+            W = nan_map.shape[1]
+        self.W = int(W or 0)
+        fill_src = [int(s) for s in fill_src]
+        out_src = None if (out_nan_src is None or nan_map is None) else [int(s) for s in out_nan_src]
+        if nan_map is not None and any(s >= self.W for s in fill_src + (out_src or [])):
+            raise ValueError(f"Imputation: a map column index is outside the NaN map of width {self.W}")
+        if len(fill_src) != fill_val.numel():
+            raise ValueError("Imputation: one fill_src entry per fill_val entry")
+        self.fill_val = fill_val.detach().to(torch.float32).contiguous()
+        self.fill_src = torch.tensor([max(s, -1) for s in fill_src], dtype=torch.int32, device=device)
+        self.nan_map = None if nan_map is None else nan_map.to(device)
+        self.out_nan_src = None if out_src is None else torch.tensor([max(s, -1) for s in out_src], dtype=torch.int32,
+                                                                    device=device)
+
+    def restoring(self, out_nan_src: Optional[Tensor]) -> "Imputation":
+        """The same imputation with another list of columns to restore (``_bounding_plan`` splits the list between
+        ``finalize_output`` and ``bound_output``); shares every other tensor."""
+        other = object.__new__(Imputation)
+        other.fill_val, other.fill_src, other.nan_map, other.W = self.fill_val, self.fill_src, self.nan_map, self.W
+        other.out_nan_src = out_nan_src
+        return other
+
+
+class ImputedAffine(tuple):
+    """``(mul, add)`` of the input normaliser, as ``model.forward(x, input_affine=...)`` takes it, that also carries the
+    :class:`Imputation` of the state (``.impute``): a caller that knows nothing of imputers still sees the pair."""
+
+    def __new__(cls, mul: Tensor, add: Tensor, impute: Imputation):
+        self = super().__new__(cls, (mul, add))
+        self.impute = impute
+        return self
+
+
 class BaseImputer(BasePreprocessor):
     """Shared bookkeeping: which dataset variable is imputed, with what, and where it sits in the four layouts
     (training / inference x input / output)."""
@@ -87,6 +140,35 @@ class BaseImputer(BasePreprocessor):
         dst = torch.tensor([layout[i] for i in keep], dtype=torch.long, device=device)
         val = torch.tensor([float(self.replacement[i]) for i in keep], dtype=torch.float32, device=device)
         return src, dst, val
+
+    def imputation(self, device, in_affine=None) -> Imputation:
+        """The :class:`Imputation` of this imputer on the inference layouts (input columns ``index_inference_input``, output
+        columns ``index_inference_output``, map columns ``index_training_input``).  ``in_affine = (mul, add)`` per input
+        column: the imputer runs BEFORE the normaliser, so the replacement is normalised (in f32, on the device) as the
+        processor chain would; ``None``: the imputer sees normalised values and writes ``replacement`` itself.  A static imputer
+        needs its ``nan_locations`` (the first call has run); ``ValueError`` for a map column outside the map."""
+        dynamic = isinstance(self, DynamicMixin)
+        n_in, n_out = self.num_inference_input_vars, self.num_inference_output_vars
+        fill_src, out_src = [-1] * n_in, [-1] * n_out
+        fill = torch.zeros(n_in, dtype=torch.float32)
+        for i, src in enumerate(self.index_training_input):
+            dst = self.index_inference_input[i]
+            if dst is not None:
+                fill_src[dst] = 0 if dynamic else src  # (a dynamic imputer reads no map: any index >= 0 marks the column)
+                fill[dst] = float(self.replacement[i])
+            dst = self.index_inference_output[i]
+            if dst is not None:
+                out_src[dst] = src
+        fill = fill.to(device)
+        if in_affine is not None:
+            picked = torch.tensor([s >= 0 for s in fill_src], device=device)
+            mul, add = (t.detach().to(device=device, dtype=torch.float32) for t in in_affine)
+            fill = torch.where(picked, fill * mul + add, fill)
+        if dynamic:
+            return Imputation(fill, fill_src, None)
+        if self.nan_locations is None:
+            raise ValueError("a static imputer has no NaN map before its first call")
+        return Imputation(fill, fill_src, self.nan_locations.to(device), out_src)
 
     def get_nans(self, x: Tensor) -> Tensor:
         """``[grid, variables]`` NaN map of the first element of every leading dimension."""

@@ -360,6 +360,58 @@ int anemoi_bound_output(float* y, int V_out, int64_t rows, int n_ops, const int3
                         const float* fin_mul, const float* fin_add, anemoi_stream_t stream);
 
 /*
+ * NaN imputation folded into the three I/O kernels above (preprocessing/imputer.py: InputImputer / ConstantImputer and
+ * their Dynamic forms between AnemoiModelInterface.predict_step and the model).  The kernels are the same templates with
+ * a compile-time flag; the plain entry points above keep launching the instantiations without it.  Additive: no existing
+ * signature changes and the ABI version is unchanged.
+ *
+ * anemoi_assemble_nodes_imputed: the arguments of anemoi_assemble_nodes plus
+ *   fill_val  f32   [V]       value written when a point is imputed, ALREADY in the space the model sees (imputer before
+ *                             normaliser: replacement * in_mul + in_add; normaliser before imputer: replacement)
+ *   fill_src  int32 [V]       column of the NaN map for this input column, -1: the column is not imputed
+ *   nan_map   uint8 [G, W]    row-major static NaN map (the imputer's nan_locations), or NULL: dynamic imputer
+ *   W         int             width of the NaN map
+ * For the state column c = t * V + v of row (b, ens, g):
+ *   raw  = x[b, t, ens, g, v]
+ *   pick = fill_src[v] >= 0 && (nan_map ? nan_map[g * W + fill_src[v]] != 0 : isnan(raw))
+ *   val  = pick ? fill_val[v] : (in_mul ? raw * in_mul[v] + in_add[v] : raw)
+ * The same map row serves every b, t, ens (_expand_subset_mask, preprocessing/imputer.py:106-108).  A static imputer
+ * overwrites a mapped point whether or not it is NaN today and leaves a NaN outside the map alone; a dynamic one tests the
+ * value it has just loaded.  Checks: fill_val / fill_src both NULL (nothing imputed: the call is anemoi_assemble_nodes) or
+ * both given; nan_map needs them and W > 0; fill_src[v] < W and the G rows of the map are the caller's to guarantee.
+ */
+int anemoi_assemble_nodes_imputed(int dtype, const float* x, int B, int T, int Ens, int64_t G, int V, const float* latlons,
+                                  int n_ll, const float* trainable, int n_tr, void* out, int64_t ldo, const float* in_mul,
+                                  const float* in_add, const float* fill_val, const int32_t* fill_src,
+                                  const uint8_t* nan_map, int W, anemoi_stream_t stream);
+
+/*
+ * anemoi_finalize_output_imputed: the arguments of anemoi_finalize_output plus fill_val / fill_src / nan_map / W as above --
+ * the prognostic residual reads the last time slice of the RAW state and adds the imputed value there, not a NaN -- and
+ *   out_nan_src int32 [V_out]  map column whose NaNs output column c gets back, -1: none (NULL: none at all)
+ * After the residual and the de-normalisation: y[b, ens, g, c] = NaN where nan_map[g * W + out_nan_src[c]] != 0 (the
+ * imputer's inverse_transform).  A dynamic imputer restores nothing: with nan_map == NULL out_nan_src is ignored.
+ */
+int anemoi_finalize_output_imputed(float* y, int V_out, const float* x, int B, int T, int Ens, int64_t G, int V_in,
+                                   const int32_t* src, const float* in_mul, const float* in_add, const float* out_mul,
+                                   const float* out_add, const float* fill_val, const int32_t* fill_src,
+                                   const uint8_t* nan_map, int W, const int32_t* out_nan_src, anemoi_stream_t stream);
+
+/*
+ * anemoi_bound_output_imputed: the arguments of anemoi_bound_output plus the grid size G (rows % G == 0), nan_map, W and
+ *   fin_nan_src int32 [n_fin]  map column whose NaNs column fin_col[j] gets back, -1: none
+ * After the op list and the de-normalisation of fin_col[j]: y[row, fin_col[j]] = NaN where
+ * nan_map[(row % G) * W + fin_nan_src[j]] != 0.  The rule between the two kernels: A COLUMN'S NaNs ARE RESTORED BY THE
+ * KERNEL THAT DE-NORMALISES IT, AFTER IT HAS DONE SO -- the columns the boundings read or write stay finite until every
+ * bounding op has run, as in the reference, where the boundings run inside the model and the imputer's inverse runs last.
+ * nan_map == NULL (dynamic imputer): the call is anemoi_bound_output.
+ */
+int anemoi_bound_output_imputed(float* y, int V_out, int64_t rows, int n_ops, const int32_t* op_col, const float* op_lo,
+                                const float* op_hi, const int32_t* op_mul, int n_fin, const int32_t* fin_col,
+                                const float* fin_mul, const float* fin_add, int64_t G, const uint8_t* nan_map, int W,
+                                const int32_t* fin_nan_src, anemoi_stream_t stream);
+
+/*
  * Prognostic residual (models/encoder_processor_decoder.py:227), in place on the f32 output:
  *   y[b, ens, g, out_idx[p]] += x[b, T-1, ens, g, in_idx[p]]   for p < n_prog.
  */
