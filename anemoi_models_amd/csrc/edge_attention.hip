@@ -341,7 +341,7 @@ __global__ __launch_bounds__(256) void gt_edge_attention_folded_kernel(const Edg
 #pragma unroll
       for (int uu = 0; uu < U; ++uu) {
         if (e + uu < e_end) {
-          const float pe = __expf(s[uu] - mb);
+          const float pe = __expf(exponent_of(s[uu], mb));
           l += pe;
           float vv[VEC];
           unpack<T, VEC>(vr[uu], vv);
@@ -612,7 +612,7 @@ __global__ __launch_bounds__(256) void gt_edge_attention_folded_sched_kernel(con
 #pragma unroll
       for (int uu = 0; uu < U; ++uu) {
         if (e + uu < e_end) {
-          const float pe = __expf(s[uu] - mb);
+          const float pe = __expf(exponent_of(s[uu], mb));
           l += pe;
           float vv[VEC];
           unpack<T, VEC>(vr[uu], vv);
@@ -973,7 +973,7 @@ __global__ __launch_bounds__(256) void gt_edge_attention_folded_tiles_kernel(con
 #pragma unroll
         for (int uu = 0; uu < U; ++uu) {
           if (uu < rem) {
-            const float pe = __expf(s[uu] - mb);
+            const float pe = __expf(exponent_of(s[uu], mb));
             l += pe;
             float vv[VEC];
             unpack<T, VEC>(vr[uu], vv);
@@ -1144,7 +1144,7 @@ __global__ __launch_bounds__(256) void gt_edge_attention_folded_runs_kernel(cons
         for (int a = 0; a < APL; ++a) tacc[a] = 0.f;
 #pragma unroll
         for (int sl = 0; sl < 3; ++sl) {
-          const float pe = __expf(sc[sl] - m);
+          const float pe = __expf(exponent_of(sc[sl], m));
           l += pe;
           float vv[VEC];
           unpack<T, VEC>(vr[sl], vv);
@@ -1347,7 +1347,7 @@ __global__ __launch_bounds__(256) void gt_edge_attention_folded_groups3_kernel(c
       for (int a = 0; a < APL; ++a) tacc[a] = 0.f;
 #pragma unroll
       for (int sl = 0; sl < 3; ++sl) {
-        const float pe = __expf(sc[sl] - m);
+        const float pe = __expf(exponent_of(sc[sl], m));
         l += pe;
         float vv[VEC];
         unpack<T, VEC>(vr[sl], vv);

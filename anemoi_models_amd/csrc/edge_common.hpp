@@ -113,6 +113,17 @@ struct QK<bf16_t, VEC> {
   }
 };
 
+// The exponent of a softmax weight, s - m, with s = scale * (q . k + u . a) ALREADY ROUNDED to f32: every folded kernel hands
+// __expf the same number, bit for bit, and all five form it here.  Left to the compiler, `sum * scale - m` stayed v_mul + v_sub
+// where the product and the difference sit in different basic blocks (plain, sched, tiles) and became ONE v_fma_f32 -- a single
+// rounding -- where a destination's three scores live in one block (groups, runs): with a scale that is no power of two
+// (D = 32) the group and run kernels' lse differed from the plain kernel's in the last bit (tests/test_gpu_edge_attn.py).  The
+// subtraction below carries no contract flag, so it cannot be fused, whatever the blocks look like to a later compiler.
+__device__ __forceinline__ float exponent_of(float s, float m) {
+#pragma clang fp contract(off)
+  return s - m;
+}
+
 // 16-byte streaming accesses: data that is touched exactly once per launch
 template <typename T, int VEC>
 __device__ __forceinline__ void load_stream(const T* p, float (&r)[VEC]) {
