@@ -336,6 +336,14 @@ SIGNATURES = {
                                                c_void_p, c_void_p]),
     "anemoi_bound_output_imputed": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                             c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
+    "anemoi_assemble_nodes_remapped": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_int,
+                                               c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "anemoi_residual_remapped": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_int, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p]),
+    "anemoi_unmap_output": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "anemoi_prognostic_residual": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p,
                                            c_void_p, c_int, c_void_p]),
     "anemoi_advance_input": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_int, c_void_p, c_int,

@@ -50,7 +50,8 @@ class AnemoiModelInterface(torch.nn.Module):
             # the processors are an InputNormalizer, alone or with one NaN imputer: the per-variable affine maps, the
             # imputer's select and its NaN restore ride on the first and the last kernel of the forward (anemoi_assemble_nodes /
             # anemoi_finalize_output / anemoi_bound_output and their _imputed forms) -- no pass of its own over the grid
-            # state or the prediction, same arithmetic
+            # state or the prediction, same arithmetic.  With a remapper next to the normaliser its converters ride on
+            # anemoi_assemble_nodes_remapped / anemoi_residual_remapped / anemoi_unmap_output in the same way
             with torch.no_grad():
                 assert len(batch.shape) == 4, (
                     f"The input tensor has an incorrect shape: expected a 4-dimensional tensor, got {batch.shape}!")
@@ -100,9 +101,12 @@ class AnemoiModelInterface(torch.nn.Module):
         ``preprocessing.imputer`` in either order -- then ``input_affine`` is an ``ImputedAffine`` carrying the imputer's
         ``Imputation``.  With an imputer the model must have the plain residual and a bounding list that compiles, and a
         static imputer its ``nan_locations`` on a grid of the batch's size with every map column inside the map.  The first
-        call is always generic: it fixes ``nan_locations`` / ``loss_mask_training``, which this route never touches."""
+        call is always generic: it fixes ``nan_locations`` / ``loss_mask_training``, which this route never touches.
+        One ``InputNormalizer`` and one ``Monomapper`` / ``Multimapper``: :meth:`_remapped_route`."""
         from ..layers.bounding import compile_boundings
         from ..preprocessing import imputer as imp_mod
+        from ..preprocessing.monomapper import Monomapper
+        from ..preprocessing.multimapper import Multimapper
         from ..preprocessing.normalizer import InputNormalizer
 
         procs = list(self.pre_processors.processors.values())
@@ -114,6 +118,8 @@ class AnemoiModelInterface(torch.nn.Module):
             return None
         imputer_first = type(procs[1]) is InputNormalizer
         imputer, norm = (procs[0], procs[1]) if imputer_first else (procs[1], procs[0])
+        if type(imputer) in (Monomapper, Multimapper):
+            return self._remapped_route(batch, imputer, norm, mapper_first=imputer_first)
         if not any(type(imputer) is k for k in kinds):
             return None
         affines = self._affines_of(norm, batch)
@@ -139,6 +145,34 @@ class AnemoiModelInterface(torch.nn.Module):
             hit = (key, imputer.imputation(batch.device, (mul_in, add_in) if imputer_first else None))
             cache["imputation"] = hit
         return imp_mod.ImputedAffine(mul_in, add_in, hit[1]), out_affine
+
+    def _remapped_route(self, batch: torch.Tensor, mapper, norm, mapper_first: bool):
+        """The case of :meth:`_fused_route` with one remapper next to the normaliser: a ``Monomapper`` on either side of it, a
+        ``Multimapper`` after it (before it the reference normaliser refuses the internal width, and so does the generic route).
+        The model must be the flat ``AnemoiModelEncProcDec`` with the plain residual and a bounding list that compiles.
+        ``input_affine`` is a ``RemappedAffine``: its ``ops.Remapping`` holds the remapper's and the normaliser's column tables
+        for the assemble, residual and unmap kernels, built once per (remapper, normaliser version, device)."""
+        from ..layers.bounding import compile_boundings
+        from ..models.encoder_processor_decoder import AnemoiModelEncProcDec
+        from ..preprocessing import remapper as rm_mod
+
+        if mapper_first and type(mapper) is rm_mod.Multimapper:
+            return None
+        if type(self.model) is not AnemoiModelEncProcDec or getattr(self.model, "_truncation", None) is not None:
+            return None
+        if len(self.model.boundings) > 0 and compile_boundings(self.model.boundings) is None:
+            return None
+        affines = self._affines_of(norm, batch)
+        if affines is None:
+            return None
+        (mul_in, add_in), out_affine = affines
+        key = (id(mapper), str(batch.device), mapper_first, self._version_of(norm))
+        cache = self.__dict__.setdefault("_remapping_cache", {})
+        hit = cache.get("remapping")
+        if hit is None or hit[0] != key:
+            hit = (key, rm_mod.remapping(mapper, (mul_in, add_in), out_affine, mapper_first, batch.device))
+            cache["remapping"] = hit
+        return rm_mod.RemappedAffine(mul_in, add_in, hit[1]), out_affine
 
     @staticmethod
     def _version_of(norm) -> tuple:
@@ -171,6 +205,12 @@ class AnemoiModelInterface(torch.nn.Module):
         if gather not in ("all", "last"):
             raise ValueError(f"rollout: gather must be 'all' or 'last', got {gather!r}")
         keep_sharded = gather == "last" and model_comm_group is not None and model_comm_group.size() > 1
+        from ..preprocessing.multimapper import Multimapper
+
+        if any(isinstance(p, Multimapper) for p in self.pre_processors.processors.values()):
+            # the forcing write-back below pre-processes slices of the INTERNAL width, which a Multimapper does not take
+            raise NotImplementedError("rollout: a Multimapper in config.data.processors changes the width of the state; "
+                                      "use predict_step")
         idx = self.data_indices.internal_model
         x = self.pre_processors(batch, in_place=False)
         assert len(x.shape) == 4, f"The input tensor has an incorrect shape: expected 4 dimensions, got {x.shape}!"

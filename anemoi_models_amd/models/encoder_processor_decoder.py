@@ -216,6 +216,22 @@ class AnemoiModelEncProcDec(nn.Module):
         if impute is not None and (truncation is not None or rows is not None or output_affine is None):
             raise NotImplementedError("an imputation runs with the plain residual, the whole grid and an output affine "
                                       "(AnemoiModelInterface.predict_step takes its generic route otherwise)")
+        remap = getattr(input_affine, "remap", None)
+        if remap is not None:
+            # a remapper riding on the input affine (preprocessing.remapper.RemappedAffine, from predict_step): the residual adds
+            # the remapped, normalised last state, the boundings see the internal normalised output as in the reference, and one
+            # pass maps it back to the raw output layout with the normaliser's inverse folded in
+            if truncation is not None or rows is not None or output_affine is None:
+                raise NotImplementedError("a remapping runs with the plain residual, the whole grid and an output affine "
+                                          "(AnemoiModelInterface.predict_step takes its generic route otherwise)")
+            ops.residual_remapped(y, x, remap)
+            if len(self.boundings) > 0:
+                plan = self._bounding_plan(y.device, None)
+                if plan is None:
+                    raise NotImplementedError("a remapping needs a bounding list that layers.bounding.compile_boundings knows")
+                ops.bound_output(y, *plan[0])
+            out = ops.unmap_output(y, remap)
+            return out if out.dtype == out_dtype else out.to(out_dtype)
         if truncation is not None:
             # truncated skip connection: y += A_up (A_down x') on the raw x (input affine on load), two launches straight out
             # of x and into y; the rest of this function then runs with a column map that adds nothing
@@ -329,6 +345,11 @@ class AnemoiModelEncProcDec(nn.Module):
         """``input_affine`` / ``output_affine`` (keyword-only extension, ``(mul, add)`` per input / output variable): ``x``
         is the RAW state and the result is de-normalised -- ``InputNormalizer`` folded into the first and the last
         kernel of the forward (``AnemoiModelInterface.predict_step`` uses it); default: the reference's contract."""
+        remap = getattr(input_affine, "remap", None)
+        if remap is not None and (getattr(self, "_truncation", None) is not None or output_affine is None or
+                                  (model_comm_group is not None and model_comm_group.size() > 1)):
+            raise NotImplementedError("a remapping runs on one device with the plain residual and an output affine "
+                                      "(AnemoiModelInterface.predict_step takes its generic route otherwise)")
         if model_comm_group is not None and model_comm_group.size() > 1:
             from ..distributed.partition import sharded_forward
 
@@ -356,9 +377,10 @@ class AnemoiModelEncProcDec(nn.Module):
         if impute is not None and (getattr(self, "_truncation", None) is not None or output_affine is None):
             raise NotImplementedError("an imputation runs with the plain residual and an output affine "
                                       "(AnemoiModelInterface.predict_step takes its generic route otherwise)")
+        # (a remapping's tables hold the normaliser: the raw state is read through them instead of the affine pair)
+        how = {"remap": remap} if remap is not None else {"in_affine": input_affine, **({} if impute is None else {"impute": impute})}
         x_data = ops.assemble_nodes(x, na.latlons(data), self._with_ones(tr_data, grid, fold), batch_size, dtype,
-                                    ld_out=self._feature_ld(width + int(fold), dtype, fold), in_affine=input_affine,
-                                    **({} if impute is None else {"impute": impute}))
+                                    ld_out=self._feature_ld(width + int(fold), dtype, fold), **how)
         # mesh rows live in an internal Morton order (gather locality of the edge kernels); only the tiny
         # per-node attribute tables are permuted, the mesh never leaves the model
         order, inv = self._mesh_order(x.device)

@@ -869,14 +869,143 @@ def _impute_args(who: str, impute, x: Tensor, n_out: Optional[int] = None):
     return fv, fs, nm, w, ons
 
 
+REMAP_OPS = {"copy": 0, "log1p": 1, "sqrt": 2, "boxcox": 3, "cos": 4, "sin": 5, "expm1": 6, "square": 7, "inv_boxcox": 8,
+             "atan2deg": 9}  # ANEMOI_REMAP_* of include/anemoi_amd.h
+REMAP_FORWARD_OPS = ("copy", "log1p", "sqrt", "boxcox", "cos", "sin")
+REMAP_INVERSE_OPS = ("copy", "expm1", "square", "inv_boxcox", "atan2deg")
+
+
+class Remapping:
+    """The column tables of a remapper (and the normaliser next to it) for ``assemble_nodes(remap=)``, ``residual_remapped``
+    and ``unmap_output``, on one device (include/anemoi_amd.h "Remappers folded into predict_step's I/O kernels").
+
+    Forward, one entry per internal input column ``j``: ``src`` (raw input column), ``op`` (name in ``REMAP_FORWARD_OPS``),
+    ``pre`` / ``post`` = ``(mul, add)`` f32 ``[V_int]`` or ``None`` (identity):  ``f_j(x) = post_mul * op(pre_mul * x + pre_add) +
+    post_add``.  ``res``: internal input column whose ``f_j`` of the last state is added to internal output column ``c``, -1
+    = none.  Inverse, one entry per raw output column ``c``: ``s0`` / ``s1`` (internal output columns; ``s1`` is the sine
+    column of ``atan2deg``, else -1), ``inv_op`` (name in ``REMAP_INVERSE_OPS``), ``inv_post`` ``[V_int_out]`` / ``inv_pre``
+    ``[V_out]``:  ``z = (inv((y - post_add) / post_mul) - pre_add) / pre_mul``.
+
+    The integer tables are kept twice, on the device for the kernels and on the host for the entry points' range checks; the
+    constructor makes the same checks and raises ``ValueError``."""
+
+    __slots__ = ("v_raw", "v_int", "v_int_out", "v_out", "src", "op", "res", "s0", "s1", "inv_op", "h_src", "h_op", "h_res",
+                 "h_s0", "h_s1", "h_inv_op", "pre", "post", "inv_pre", "inv_post")
+
+    def __init__(self, device, v_raw: int, src, op, res, s0, s1, inv_op, pre=None, post=None, inv_pre=None,
+                 inv_post=None) -> None:
+        src, res, s0, s1 = ([int(i) for i in t] for t in (src, res, s0, s1))
+        self.v_raw, self.v_int, self.v_int_out, self.v_out = int(v_raw), len(src), len(res), len(s0)
+        if len(op) != self.v_int or len(s1) != self.v_out or len(inv_op) != self.v_out:
+            raise ValueError("Remapping: one op per src entry, one s1 and one inverse op per s0 entry")
+        if any(o not in REMAP_FORWARD_OPS for o in op) or any(o not in REMAP_INVERSE_OPS for o in inv_op):
+            raise ValueError(f"Remapping: forward ops are {REMAP_FORWARD_OPS}, inverse ops {REMAP_INVERSE_OPS}")
+        if any(not 0 <= i < self.v_raw for i in src) or any(not -1 <= i < self.v_int for i in res):
+            raise ValueError("Remapping: src outside the raw input columns or res outside the internal input columns")
+        if any(not 0 <= i < self.v_int_out for i in s0) or \
+                any(o == "atan2deg" and not 0 <= i < self.v_int_out for o, i in zip(inv_op, s1)):
+            raise ValueError("Remapping: s0 / s1 outside the internal output columns")
+
+        def table(values):
+            host = torch.tensor(values, dtype=torch.int32)
+            return host, host.to(device)
+
+        self.h_src, self.src = table(src)
+        self.h_op, self.op = table([REMAP_OPS[o] for o in op])
+        self.h_res, self.res = table(res)
+        self.h_s0, self.s0 = table(s0)
+        self.h_s1, self.s1 = table(s1)
+        self.h_inv_op, self.inv_op = table([REMAP_OPS[o] for o in inv_op])
+
+        def pair(p, n, name):
+            if p is None:
+                return None
+            mul, add = (t.detach().to(device=device, dtype=torch.float32).contiguous() for t in p)
+            if mul.shape != (n,) or add.shape != (n,):
+                raise ValueError(f"Remapping: {name} needs (mul, add) with {n} entries each")
+            return mul, add
+
+        self.pre, self.post = pair(pre, self.v_int, "pre"), pair(post, self.v_int, "post")
+        self.inv_pre, self.inv_post = pair(inv_pre, self.v_out, "inv_pre"), pair(inv_post, self.v_int_out, "inv_post")
+
+
+def _remap_forward_args(who: str, remap: Remapping, x: Tensor):
+    """Table arguments shared by ``anemoi_assemble_nodes_remapped`` and ``anemoi_residual_remapped``, checked against ``x``."""
+    _dev(remap.src, remap.op, *(remap.pre or ()), *(remap.post or ()))
+    if x.shape[-1] != remap.v_raw:
+        raise ValueError(f"{who}: the state has {x.shape[-1]} variables, the remapping reads {remap.v_raw}")
+    pre, post = remap.pre or (None, None), remap.post or (None, None)
+    return (remap.src.data_ptr(), remap.op.data_ptr(), _ptr(pre[0]), _ptr(pre[1]), _ptr(post[0]), _ptr(post[1]))
+
+
+def residual_remapped(y: Tensor, x: Tensor, remap: Remapping) -> Tensor:
+    """In place on the f32 internal output ``y`` ``[B, Ens, G, V_int_out]``: ``y[..., c] += f_j(x[b, T - 1, ens, g, src[j]])``
+    for ``j = remap.res[c] >= 0`` -- the prognostic residual on the remapped, normalised last state of the RAW ``x``
+    ``[B, T, Ens, G, V_raw]``.  Nothing is de-normalised."""
+    _dev(y, x, remap.res)
+    if y.dtype != torch.float32 or not y.is_contiguous():
+        raise ValueError("residual_remapped: y must be contiguous float32")
+    x = x.contiguous().float()
+    b, t, ens, g, v_raw = x.shape
+    if y.shape[-1] != remap.v_int_out or y.numel() != b * ens * g * remap.v_int_out:
+        raise ValueError(f"residual_remapped: y {tuple(y.shape)} does not hold [B, Ens, G, {remap.v_int_out}] of x {tuple(x.shape)}")
+    tables = _remap_forward_args("residual_remapped", remap, x)
+    st = _lib.load().anemoi_residual_remapped(y.data_ptr(), remap.v_int_out, x.data_ptr(), b, t, ens, g, v_raw, remap.v_int,
+                                              remap.res.data_ptr(), *tables, remap.h_res.data_ptr(), remap.h_src.data_ptr(),
+                                              remap.h_op.data_ptr(), _stream())
+    _lib.check(st, "anemoi_residual_remapped")
+    return y
+
+
+def unmap_output(y: Tensor, remap: Remapping) -> Tensor:
+    """The f32 internal output ``y`` ``[..., V_int_out]`` -> a new ``[..., V_out]`` in the raw output layout: kept columns, the
+    mono inverses and ``atan2`` in degrees of a (cos, sin) column pair, the normaliser's inverse folded in (see
+    :class:`Remapping`)."""
+    _dev(y, remap.s0, remap.s1, remap.inv_op, *(remap.inv_pre or ()), *(remap.inv_post or ()))
+    if y.dtype != torch.float32 or not y.is_contiguous() or y.shape[-1] != remap.v_int_out:
+        raise ValueError(f"unmap_output: y must be contiguous float32 [..., {remap.v_int_out}]")
+    out = torch.empty(tuple(y.shape[:-1]) + (remap.v_out,), dtype=torch.float32, device=y.device)
+    pre, post = remap.inv_pre or (None, None), remap.inv_post or (None, None)
+    st = _lib.load().anemoi_unmap_output(y.data_ptr(), remap.v_int_out, out.data_ptr(), remap.v_out,
+                                         y.numel() // remap.v_int_out, remap.s0.data_ptr(), remap.s1.data_ptr(),
+                                         remap.inv_op.data_ptr(), _ptr(pre[0]), _ptr(pre[1]), _ptr(post[0]), _ptr(post[1]),
+                                         remap.h_s0.data_ptr(), remap.h_s1.data_ptr(), remap.h_inv_op.data_ptr(), _stream())
+    _lib.check(st, "anemoi_unmap_output")
+    return out
+
+
 def assemble_nodes(x: Optional[Tensor], latlons: Tensor, trainable: Optional[Tensor], batch_size: int,
                    dtype: torch.dtype, ld_out: Optional[int] = None, ensemble: int = 1, in_affine=None,
-                   rows: Optional[Tensor] = None, impute=None) -> Tensor:
+                   rows: Optional[Tensor] = None, impute=None, remap: Optional[Remapping] = None) -> Tensor:
     """Rows ``(b, ens, g)`` of ``[x (time-major) | latlons | trainable | 0-pad]`` in ``dtype``.  ``in_affine`` =
     ``(mul, add)`` f32 ``[V]``: ``x`` is the raw state, normalised as ``x * mul + add`` while it is read.
     ``rows`` (int64 node ids; batch 1, ensemble 1): only those nodes' rows, in that order (``anemoi_assemble_node_rows``).
     ``impute`` (``preprocessing.imputer.Imputation``): NaN imputation as a select on the read
-    (``anemoi_assemble_nodes_imputed``); not with ``rows``."""
+    (``anemoi_assemble_nodes_imputed``); not with ``rows``.
+    ``remap`` (:class:`Remapping`): ``x`` holds the RAW variables and the feature columns are the internal ones, ``f_j`` of the
+    raw column ``remap.src[j]`` (``anemoi_assemble_nodes_remapped``); its tables hold the normaliser, so not with
+    ``in_affine``, ``impute`` or ``rows``."""
+    if remap is not None:
+        if x is None or in_affine is not None or impute is not None or rows is not None:
+            raise ValueError("assemble_nodes: remap= needs a state x and takes no in_affine, impute or rows")
+        _dev(x, latlons, trainable)
+        b, t, ens, gx, v_raw = x.shape
+        g, n_ll = latlons.shape
+        n_tr = 0 if trainable is None else trainable.shape[1]
+        if gx != g or b != batch_size:
+            raise ValueError(f"assemble_nodes: x has shape {tuple(x.shape)} but the graph has {g} nodes")
+        x = x.contiguous().float()
+        tables = _remap_forward_args("assemble_nodes", remap, x)
+        width = t * remap.v_int + n_ll + n_tr
+        ld = width if ld_out is None else ld_out
+        latlons = latlons.contiguous().float()
+        trainable = None if trainable is None else trainable.contiguous().float()
+        out = torch.empty((b * ens * g, ld), dtype=dtype, device=latlons.device)
+        st = _lib.load().anemoi_assemble_nodes_remapped(dtype_code(dtype), x.data_ptr(), b, t, ens, g, v_raw, remap.v_int,
+                                                        latlons.data_ptr(), n_ll, _ptr(trainable), n_tr, out.data_ptr(), ld,
+                                                        *tables, remap.h_src.data_ptr(), remap.h_op.data_ptr(), _stream())
+        _lib.check(st, "anemoi_assemble_nodes_remapped")
+        return out
     if impute is not None and rows is not None:
         raise ValueError("assemble_nodes: the row-list kernel takes no imputation (rows= with impute=)")
     if impute is not None and x is None:

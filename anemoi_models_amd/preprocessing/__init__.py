@@ -1,7 +1,7 @@
 """Pre- / post-processors mirroring reference preprocessing/__init__.py:20-194 (same class names, config schema,
-``forward(x, in_place, inverse)`` contract).  Only the pieces on the inference path are provided: the base class, the
-``Processors`` container, ``normalizer.InputNormalizer`` and the NaN imputers of ``imputer``; the remappers are not
-part of this build."""
+``forward(x, in_place, inverse)`` contract): the base class, the ``Processors`` container, ``normalizer.InputNormalizer``,
+the NaN imputers of ``imputer`` and the remappers (``remapper.Remapper`` -> ``monomapper.Monomapper`` /
+``multimapper.Multimapper``, converters in ``mappings``)."""
 
 from __future__ import annotations
 

@@ -48,9 +48,12 @@ class _DataIndex:
 
 class SimpleDataIndices:
     """Dataset layout ``[prognostic..., forcing..., diagnostic...]``; input = all but diagnostic, output = all but
-    forcing (reference data_indices/collection.py:24-103 without remapping: ``internal_*`` == the plain views)."""
+    forcing (reference data_indices/collection.py:24-103).  ``remapped = {name: [new names]}`` (``config.data.remapped``, the
+    variables a ``preprocessing.multimapper.Multimapper`` replaces): ``internal_data`` / ``internal_model`` drop those
+    variables and append the new ones at the end, a remapped forcing hands its new names to ``forcing``; without it
+    ``internal_*`` are the plain views."""
 
-    def __init__(self, n_prognostic: int, n_forcing: int = 0, n_diagnostic: int = 0, names=None) -> None:
+    def __init__(self, n_prognostic: int, n_forcing: int = 0, n_diagnostic: int = 0, names=None, remapped=None) -> None:
         prog = [f"prog_{i}" for i in range(n_prognostic)]
         forc = [f"forc_{i}" for i in range(n_forcing)]
         diag = [f"diag_{i}" for i in range(n_diagnostic)]
@@ -74,6 +77,44 @@ class SimpleDataIndices:
         self.internal_data = self.data
         self.num_input = len(inp)
         self.num_output = len(out)
+        self.remapped = {k: list(v) for k, v in (remapped or {}).items()}
+        if self.remapped:
+            self._remap(prog + forc, prog + diag, forc, diag)
+
+    def _remap(self, model_in, model_out, forcing, diagnostic) -> None:
+        """The two internal views with ``self.remapped`` applied (reference data_indices/collection.py:40-103)."""
+        assert set(self.remapped).isdisjoint(diagnostic), "Remapped variable overlap with diagnostic variables. Not implemented."
+        assert set(self.remapped).issubset(self.name_to_index), (
+            "Remapping a variable that does not exist in the dataset. Check for typos: "
+            f"{set(self.remapped).difference(self.name_to_index)}")
+        data_names = [n for n in self.name_to_index if n not in self.remapped]
+        in_names = [n for n in model_in if n not in self.remapped]
+        out_names = [n for n in model_out if n not in self.remapped]
+        forcing = list(forcing)
+        for key, new in self.remapped.items():
+            in_names += new
+            data_names += new
+            if key in forcing:  # a forcing stays out of the output; its new names are forcings
+                forcing += new
+                forcing.remove(key)
+            else:
+                out_names += new
+
+        def pick(names, chosen):
+            return sorted(i for i, n in enumerate(names) if n in chosen)
+
+        def without(names, *dropped):
+            return sorted(i for i, n in enumerate(names) if not any(n in d for d in dropped))
+
+        inp = _ModelIndex(in_names, without(in_names, forcing), forcing=pick(in_names, forcing))
+        out = _ModelIndex(out_names, without(out_names, diagnostic), diagnostic=pick(out_names, diagnostic))
+        self.internal_model = _Internal(inp, out)
+        name_to_index = {n: i for i, n in enumerate(data_names)}
+        d_in = _DataIndex(name_to_index, without(data_names, diagnostic), without(data_names, diagnostic, forcing),
+                          diagnostic=pick(data_names, diagnostic), forcing=pick(data_names, forcing))
+        d_out = _DataIndex(name_to_index, without(data_names, forcing), without(data_names, diagnostic, forcing),
+                           diagnostic=pick(data_names, diagnostic), forcing=pick(data_names, forcing))
+        self.internal_data = _Internal(d_in, d_out)
 
 
 def advance_colmap(data_indices) -> torch.Tensor:

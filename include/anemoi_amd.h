@@ -412,6 +412,58 @@ int anemoi_bound_output_imputed(float* y, int V_out, int64_t rows, int n_ops, co
                                 const int32_t* fin_nan_src, anemoi_stream_t stream);
 
 /*
+ * Remappers folded into predict_step's I/O kernels (csrc/remap.hip; preprocessing/monomapper.py, multimapper.py: log1p,
+ * sqrt, boxcox with lambda 1/2, cos_sin).  A remapper is a per-column function of the raw state whose internal layout
+ * may be wider than the raw one (V_int != V_raw).  Additive: no existing signature changes and the ABI version is unchanged.
+ *
+ * One op code per column, one device function for the three kernels:
+ *   ANEMOI_REMAP_COPY u | _LOG1P log1p(u) | _SQRT sqrt(u) | _BOXCOX (sqrt(u) - 1) / 0.5 | _COS cos(u pi / 180) |
+ *   _SIN sin(u pi / 180) | _EXPM1 expm1(u) | _SQUARE u u | _INV_BOXCOX (0.5 u + 1)^2 |
+ *   _ATAN2DEG remainder(atan2(u1, u) 180 / pi, 360), in [0, 360], of TWO source columns (u the cosine, u1 the sine)
+ * Forward, internal input column j < V_int, from raw column src[j]:
+ *   f_j(x) = post_mul[j] * op_j(pre_mul[j] * x + pre_add[j]) + post_add[j]                    op_j in COPY .. SIN
+ * Inverse, raw output column c < V_out, from internal output column(s) s0[c] (and s1[c] for ATAN2DEG):
+ *   u = (y[s0[c]] - post_add[s0[c]]) / post_mul[s0[c]],  u1 likewise from s1[c]
+ *   z = (op_c(u, u1) - pre_add[c]) / pre_mul[c]                      op_c in COPY, EXPM1, SQUARE, INV_BOXCOX, ATAN2DEG
+ * The InputNormalizer is the pre pair when it runs before the remapper and the post pair when it runs after; a pair given as
+ * NULL / NULL is the identity and costs nothing.  NaN and values outside a converter's domain follow the C library (log1p of
+ * a value below -1 and sqrt of a negative one are NaN, NaN stays NaN).
+ *
+ * All tables are device arrays.  h_* are HOST copies of the integer tables of the same name: the entry point checks them --
+ * src / s0 / s1 / res inside their range, op codes inside the list above -- and returns ANEMOI_ERR_INVALID before anything is
+ * launched; it reads no device memory and is capturable.  Every output element is written by one thread, no atomics.
+ *
+ * anemoi_assemble_nodes_remapped: anemoi_assemble_nodes whose feature column c = t * V_int + j holds
+ * f_j(x[b, t, ens, g, src[j]]), x being f32 [B, T, Ens, G, V_raw]; same row layout [x | latlons | trainable | 0-pad], dtypes
+ * and ldo rule (ldo >= T * V_int + n_ll + n_tr; eight columns per thread when ldo % 8 == 0 and out is 16-byte aligned).
+ *
+ * anemoi_residual_remapped: in place on the f32 internal output y [B, Ens, G, V_int_out],
+ *   y[.., c] += f_j(x[b, T-1, ens, g, src[j]])   for j = res[c] >= 0     (res int32 [V_int_out], -1: none)
+ * -- the prognostic residual on the remapped, normalised input; nothing is de-normalised here.
+ *
+ * anemoi_unmap_output: y f32 [rows, V_int_out] -> out f32 [rows, V_out] (another buffer), one thread per output element,
+ * the inverse above; pre tables have V_out entries, post tables V_int_out.
+ */
+enum {
+  ANEMOI_REMAP_COPY = 0, ANEMOI_REMAP_LOG1P = 1, ANEMOI_REMAP_SQRT = 2, ANEMOI_REMAP_BOXCOX = 3, ANEMOI_REMAP_COS = 4,
+  ANEMOI_REMAP_SIN = 5, ANEMOI_REMAP_EXPM1 = 6, ANEMOI_REMAP_SQUARE = 7, ANEMOI_REMAP_INV_BOXCOX = 8,
+  ANEMOI_REMAP_ATAN2DEG = 9
+};
+int anemoi_assemble_nodes_remapped(int dtype, const float* x, int B, int T, int Ens, int64_t G, int V_raw, int V_int,
+                                   const float* latlons, int n_ll, const float* trainable, int n_tr, void* out, int64_t ldo,
+                                   const int32_t* src, const int32_t* op, const float* pre_mul, const float* pre_add,
+                                   const float* post_mul, const float* post_add, const int32_t* h_src, const int32_t* h_op,
+                                   anemoi_stream_t stream);
+int anemoi_residual_remapped(float* y, int V_int_out, const float* x, int B, int T, int Ens, int64_t G, int V_raw, int V_int,
+                             const int32_t* res, const int32_t* src, const int32_t* op, const float* pre_mul,
+                             const float* pre_add, const float* post_mul, const float* post_add, const int32_t* h_res,
+                             const int32_t* h_src, const int32_t* h_op, anemoi_stream_t stream);
+int anemoi_unmap_output(const float* y, int V_int_out, float* out, int V_out, int64_t rows, const int32_t* s0,
+                        const int32_t* s1, const int32_t* op, const float* pre_mul, const float* pre_add,
+                        const float* post_mul, const float* post_add, const int32_t* h_s0, const int32_t* h_s1,
+                        const int32_t* h_op, anemoi_stream_t stream);
+
+/*
  * Prognostic residual (models/encoder_processor_decoder.py:227), in place on the f32 output:
  *   y[b, ens, g, out_idx[p]] += x[b, T-1, ens, g, in_idx[p]]   for p < n_prog.
  */
