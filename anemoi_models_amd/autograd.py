@@ -1424,6 +1424,36 @@ def truncated_residual(out: Tensor, x: Tensor, plan, out_idx: Tensor, in_idx: Te
     return _TruncatedResidual.apply(out, x, plan.on(x.device, cache), out_idx, in_idx, tuple(shape))
 
 
+class _BoundOutput(torch.autograd.Function):
+    """The whole bounding list IN PLACE on the fresh f32 output of the residual (``anemoi_bound_output_train``: one launch, which
+    also writes the tape -- what every op read) and its gradient from the tape alone (``anemoi_bound_output_backward``: one
+    launch, every element owned by one thread) -- where the module loop runs a gather, an activation and an index_put per
+    module and torch's index accumulation per module in the backward."""
+
+    @staticmethod
+    def forward(ctx, y: Tensor, lists, slope: Tensor, n_tape: int):
+        ctx.save_for_backward(ops.bound_output_train(y, *lists, slope, n_tape))
+        ctx.lists, ctx.slope = lists, slope
+        ctx.mark_dirty(y)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g: Tensor):
+        (tape,) = ctx.saved_tensors
+        return ops.bound_output_backward(g.float().contiguous(), tape, *ctx.lists, ctx.slope), None, None, None
+
+
+def bound_output(y: Tensor, lists, slope: Tensor, n_tape: int) -> Tensor:
+    """The bounding ops ``lists = (col int32, lo f32, hi f32, mul int32)`` with their ``slope`` (f32, zeros for the hard classes;
+    ``layers.bounding``) applied in place to ``y`` f32 ``[..., V_out]`` -- a fresh, contiguous tensor that requires a gradient and
+    is no leaf, such as the output of the residual -- and differentiable.  ``n_tape``: ops plus ops with a multiplier.
+    The derivative of an op is 1 strictly inside its bounds and its slope elsewhere, the bounds included."""
+    if y.dtype != torch.float32 or not y.is_contiguous():
+        raise ValueError("bound_output: y must be contiguous float32")
+    return _BoundOutput.apply(y, tuple(lists), slope, int(n_tape))
+
+
 def _f32c(t: Optional[Tensor]) -> Optional[Tensor]:
     """A constant operand of a loss (no gradient) as contiguous float32."""
     return None if t is None else t.detach().float().contiguous()

@@ -5,6 +5,7 @@
 // layout allows, one wave64 per row (LayerNorm) or a flat grid-stride mapping.
 #include <cstdlib>
 
+#include "bound_op.hpp"
 #include "common.hpp"
 #include "trail.hpp"
 
@@ -631,7 +632,9 @@ __global__ __launch_bounds__(256) void finalize_output_kernel(float* __restrict_
 // Comparisons (not fminf / fmaxf) keep a NaN a NaN, like torch's relu / hardtanh.
 // IMPUTE (anemoi_bound_output_imputed): a fin column gets the NaNs of its map column back AFTER its de-normalisation -- the
 // kernel that de-normalises a column restores it, so every bounding op above has seen finite values.
-template <bool IMPUTE>
+// LEAKY (anemoi_bound_output_leaky): op i has a slope s = op_slope[i] and maps v < lo to lo + s (v - lo), v > hi to
+// hi + s (v - hi) (bound_op, bound_op.hpp); the instantiations without the flag are the code they were.
+template <bool IMPUTE, bool LEAKY>
 __global__ __launch_bounds__(256) void bound_output_kernel(float* __restrict__ y, int V_out, int64_t rows, int n_ops,
                                                            const int32_t* __restrict__ op_col,
                                                            const float* __restrict__ op_lo,
@@ -640,7 +643,8 @@ __global__ __launch_bounds__(256) void bound_output_kernel(float* __restrict__ y
                                                            const int32_t* __restrict__ fin_col,
                                                            const float* __restrict__ fin_mul,
                                                            const float* __restrict__ fin_add,
-                                                           const impute_arg_t<IMPUTE, BoundImputeArgs> imp) {
+                                                           const impute_arg_t<IMPUTE, BoundImputeArgs> imp,
+                                                           [[maybe_unused]] const float* __restrict__ op_slope) {
   for (int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; row < rows;
        row += (int64_t)gridDim.x * blockDim.x) {
     float* yr = y + row * V_out;
@@ -648,7 +652,8 @@ __global__ __launch_bounds__(256) void bound_output_kernel(float* __restrict__ y
       const int c = op_col[i];
       float v = yr[c];
       const float lo = op_lo[i], hi = op_hi[i];
-      v = v < lo ? lo : (v > hi ? hi : v);
+      if constexpr (LEAKY) v = bound_op(v, lo, hi, op_slope[i]);
+      else v = v < lo ? lo : (v > hi ? hi : v);
       const int m = op_mul[i];
       if (m >= 0) v *= yr[m];
       yr[c] = v;
@@ -1038,7 +1043,7 @@ int anemoi_finalize_output_rows(float* y, int V_out, const float* x, int T, int6
 static int bound_output_impl(const char* who, float* y, int V_out, int64_t rows, int n_ops, const int32_t* op_col,
                              const float* op_lo, const float* op_hi, const int32_t* op_mul, int n_fin,
                              const int32_t* fin_col, const float* fin_mul, const float* fin_add, anemoi_stream_t stream,
-                             const BoundImputeArgs* imp = nullptr) {
+                             const BoundImputeArgs* imp = nullptr, const float* op_slope = nullptr) {
   ANEMOI_REQUIRE(y && V_out > 0 && rows >= 0 && n_ops >= 0 && n_fin >= 0, ANEMOI_ERR_INVALID,
                  "anemoi_bound_output: bad argument");
   ANEMOI_REQUIRE(n_ops == 0 || (op_col && op_lo && op_hi && op_mul), ANEMOI_ERR_INVALID,
@@ -1054,12 +1059,17 @@ static int bound_output_impl(const char* who, float* y, int V_out, int64_t rows,
     if (imp->nan_map == nullptr || n_fin == 0) imp = nullptr;  // dynamic imputer / no column to restore: the plain instantiation
   }
   if (rows == 0 || (n_ops == 0 && n_fin == 0)) return ANEMOI_OK;
-  if (imp != nullptr)
-    hipLaunchKernelGGL(bound_output_kernel<true>, dim3(flat_grid(rows)), dim3(256), 0, as_stream(stream), y, V_out, rows,
-                       n_ops, op_col, op_lo, op_hi, op_mul, n_fin, fin_col, fin_mul, fin_add, *imp);
-  else
-    hipLaunchKernelGGL(bound_output_kernel<false>, dim3(flat_grid(rows)), dim3(256), 0, as_stream(stream), y, V_out, rows,
-                       n_ops, op_col, op_lo, op_hi, op_mul, n_fin, fin_col, fin_mul, fin_add, NoImpute{});
+#define ANEMOI_BOUND(IMP, LEAKY, ARG)                                                                                       \
+  hipLaunchKernelGGL((bound_output_kernel<IMP, LEAKY>), dim3(flat_grid(rows)), dim3(256), 0, as_stream(stream), y, V_out,   \
+                     rows, n_ops, op_col, op_lo, op_hi, op_mul, n_fin, fin_col, fin_mul, fin_add, ARG, op_slope)
+  if (op_slope != nullptr) {
+    if (imp != nullptr) ANEMOI_BOUND(true, true, *imp);
+    else ANEMOI_BOUND(false, true, NoImpute{});
+  } else {
+    if (imp != nullptr) ANEMOI_BOUND(true, false, *imp);
+    else ANEMOI_BOUND(false, false, NoImpute{});
+  }
+#undef ANEMOI_BOUND
   return trail::note(check_launch("anemoi_bound_output"), who, "out", ANEMOI_F32, y, V_out, rows, V_out, as_stream(stream));
 }
 
@@ -1077,6 +1087,16 @@ int anemoi_bound_output_imputed(float* y, int V_out, int64_t rows, int n_ops, co
   const BoundImputeArgs imp{G, nan_map, W, fin_nan_src};
   return bound_output_impl("anemoi_bound_output_imputed", y, V_out, rows, n_ops, op_col, op_lo, op_hi, op_mul, n_fin, fin_col,
                            fin_mul, fin_add, stream, &imp);
+}
+
+int anemoi_bound_output_leaky(float* y, int V_out, int64_t rows, int n_ops, const int32_t* op_col, const float* op_lo,
+                              const float* op_hi, const int32_t* op_mul, int n_fin, const int32_t* fin_col,
+                              const float* fin_mul, const float* fin_add, int64_t G, const uint8_t* nan_map, int W,
+                              const int32_t* fin_nan_src, const float* op_slope, anemoi_stream_t stream) {
+  ANEMOI_REQUIRE(op_slope != nullptr, ANEMOI_ERR_INVALID, "anemoi_bound_output_leaky: null slope list");
+  const BoundImputeArgs imp{G, nan_map, W, fin_nan_src};
+  return bound_output_impl("anemoi_bound_output_leaky", y, V_out, rows, n_ops, op_col, op_lo, op_hi, op_mul, n_fin, fin_col,
+                           fin_mul, fin_add, stream, &imp, op_slope);
 }
 
 int anemoi_abi_version(void) { return 55; }

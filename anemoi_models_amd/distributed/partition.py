@@ -699,7 +699,7 @@ def finish_local_rows(model, x_state: Tensor, y_local: Tensor, sp: ShardPlan) ->
             for bounding in model.boundings:
                 own = bounding(own)
         else:
-            ops.bound_output(own, *plan[0])
+            ops.bound_output(own, *plan[0], **plan[3])
     return own
 
 

@@ -11,6 +11,7 @@ import torch
 from .. import ops
 from ..models.encoder_processor_decoder import instantiate
 from ..preprocessing import Processors
+from ..utils.config import target_accepts
 
 
 class AnemoiModelInterface(torch.nn.Module):
@@ -38,6 +39,8 @@ class AnemoiModelInterface(torch.nn.Module):
         self.pre_processors = Processors(processors)
         self.post_processors = Processors(processors, inverse=True)
         extra = {} if not self.truncation_data else {"truncation_data": self.truncation_data}
+        if target_accepts(self.config.model.model, "statistics"):  # (the boundings that work in normalised space read them)
+            extra["statistics"] = self.statistics
         self.model = instantiate(self.config.model.model, model_config=self.config, data_indices=self.data_indices,
                                  graph_data=self.graph_data, _recursive_=False, **extra)
         self.forward = self.model.forward

@@ -30,6 +30,7 @@ except ImportError:  # pragma: no cover - hydra is not in the build image
 
 from ..utils.config import instantiate as _local_instantiate
 from ..utils.config import REFERENCE_PREFIX
+from ..utils.config import target_accepts
 
 LOGGER = logging.getLogger(__name__)
 
@@ -44,8 +45,10 @@ def instantiate(cfg, **kwargs):
 class AnemoiModelEncProcDec(nn.Module):
     """Encoder - processor - decoder graph network on MI355X kernels."""
 
-    def __init__(self, *, model_config, data_indices, graph_data, truncation_data=None) -> None:
-        """``truncation_data`` (keyword-only, as in current anemoi-models): ``{"down": A_down, "up": A_up}``, the sparse matrices
+    def __init__(self, *, model_config, data_indices, graph_data, truncation_data=None, statistics=None) -> None:
+        """``statistics`` (keyword-only, as in current anemoi-models): the dataset statistics, handed to the boundings that take
+        them (``layers.bounding.NormalizedReluBounding``).
+        ``truncation_data`` (keyword-only, as in current anemoi-models): ``{"down": A_down, "up": A_up}``, the sparse matrices
         of the truncated skip connection ``x_skip = A_up (A_down x[:, -1])`` in any form ``layers.truncation.canonical_csr``
         takes; ``None`` / ``{}``: the untruncated residual, exactly as without the argument."""
         super().__init__()
@@ -91,15 +94,22 @@ class AnemoiModelEncProcDec(nn.Module):
             src_grid_size=self.node_attributes.num_nodes[hidden],
             dst_grid_size=self.node_attributes.num_nodes[data],
         )
-        self.boundings = nn.ModuleList(
-            [
-                instantiate(cfg, name_to_index=self.data_indices.internal_model.output.name_to_index)
-                for cfg in getattr(model_config.model, "bounding", [])
-            ]
-        )
+        self.boundings = self._build_boundings(model_config, statistics)
         self._idx_cache: dict = {}
         self._hoisted = runtime.PackedWeights()  # call-invariant activations of the inference path (runtime.hoisted)
         self._set_truncation(truncation_data)
+
+    def _build_boundings(self, model_config, statistics) -> nn.ModuleList:
+        """``model_config.model.bounding`` instantiated.  ``statistics`` and the name map of the statistics' columns go only to a
+        target whose ``__init__`` takes them: a user's own subclass with the earlier signature keeps working."""
+        n2i = self.data_indices.internal_model.output.name_to_index
+        made = []
+        for cfg in getattr(model_config.model, "bounding", []):
+            extra = {}
+            if target_accepts(cfg, "statistics"):
+                extra = {"statistics": statistics, "name_to_index_stats": self.data_indices.data.input.name_to_index}
+            made.append(instantiate(cfg, name_to_index=n2i, **extra))
+        return nn.ModuleList(made)
 
     def _set_truncation(self, truncation_data) -> None:
         """The plan of the truncated skip connection: a plain attribute (no parameters, no buffers -- the ``state_dict`` is
@@ -229,7 +239,7 @@ class AnemoiModelEncProcDec(nn.Module):
                 plan = self._bounding_plan(y.device, None)
                 if plan is None:
                     raise NotImplementedError("a remapping needs a bounding list that layers.bounding.compile_boundings knows")
-                ops.bound_output(y, *plan[0])
+                ops.bound_output(y, *plan[0], **plan[3])
             out = ops.unmap_output(y, remap)
             return out if out.dtype == out_dtype else out.to(out_dtype)
         if truncation is not None:
@@ -261,10 +271,10 @@ class AnemoiModelEncProcDec(nn.Module):
         plan = self._bounding_plan(y.device, output_affine)
         if plan is not None and impute is not None:
             # bounded columns stay finite (and normalised) through finalize_output; bound_output restores them at its end
-            op_lists, masked_affine, fin = plan
+            op_lists, masked_affine, fin, leaky = plan
             imp_fin, imp_bound = self._imputation_split(impute, fin[0])
             ops.finalize_output(y, x, self._idx_cache[key], input_affine, masked_affine, impute=imp_fin)
-            ops.bound_output(y, *op_lists, fin=fin, impute=imp_bound)
+            ops.bound_output(y, *op_lists, fin=fin, impute=imp_bound, **leaky)
             return y if y.dtype == out_dtype else y.to(out_dtype)
         if impute is not None:
             raise NotImplementedError("an imputation needs a bounding list that layers.bounding.compile_boundings knows")
@@ -279,14 +289,17 @@ class AnemoiModelEncProcDec(nn.Module):
             return y
         # known boundings: the columns they touch stay normalised through finalize_output (mul 1 / add 0 there) and
         # are bounded, then de-normalised, by ONE kernel; every other column is finished by finalize_output
-        op_lists, masked_affine, fin = plan
+        op_lists, masked_affine, fin, leaky = plan
         ops.finalize_output(y, x, self._idx_cache[key], input_affine, masked_affine, rows=rows)
-        ops.bound_output(y, *op_lists, fin=fin)
+        ops.bound_output(y, *op_lists, fin=fin, **leaky)
         return y if y.dtype == out_dtype else y.to(out_dtype)
 
     def _bounding_plan(self, device, output_affine):
-        """Device-side op list of ``self.boundings`` (cached per device and output affine), ``None`` for unknown classes."""
+        """Device-side op list of ``self.boundings`` (cached per device and output affine), ``None`` for unknown classes:
+        ``(lists, masked affine, fin, leaky)`` -- ``leaky`` holds the further keywords of ``ops.bound_output``: ``{"slope": f32
+        tensor}`` for a list with leaky classes, nothing for the hard classes (the call is then the one it always was)."""
         from ..layers.bounding import bounded_columns
+        from ..layers.bounding import bounding_slopes
         from ..layers.bounding import compile_boundings
 
         key = ("boundings", str(device), None if output_affine is None else
@@ -310,7 +323,28 @@ class AnemoiModelEncProcDec(nn.Module):
                 m_add[cols] = 0.0
                 masked = (m_mul, m_add)
                 fin = (cols.to(torch.int32), mul[cols].contiguous(), add[cols].contiguous())
-            self._idx_cache[key] = (lists, masked, fin)
+            slopes = bounding_slopes(self.boundings)
+            leaky = {} if slopes is None else {"slope": torch.tensor(slopes, dtype=torch.float32, device=device)}
+            self._idx_cache[key] = (lists, masked, fin, leaky)
+        return self._idx_cache[key]
+
+    def _bounding_train_plan(self, device):
+        """``(lists, slope, n_tape)`` of ``autograd.bound_output`` for ``self.boundings`` (cached per device), ``None`` for
+        unknown classes: the lists of :meth:`_bounding_plan`, a slope per op (zeros for the hard classes) and the number of tape
+        entries per row."""
+        key = ("boundings_train", str(device))
+        if key not in self._idx_cache:
+            plan = self._bounding_plan(device, None)
+            if plan is None:
+                self._idx_cache[key] = None
+            else:
+                lists, slope = plan[0], plan[3].get("slope")
+                if slope is None:
+                    slope = torch.zeros(lists[0].numel(), dtype=torch.float32, device=device)
+                cols, muls = lists[0].tolist(), lists[3].tolist()
+                if any(not 0 <= c < self.num_output_channels for c in cols) or any(m >= self.num_output_channels for m in muls):
+                    raise ValueError("a bounding names a column outside the model output")
+                self._idx_cache[key] = (lists, slope, len(muls) + sum(m >= 0 for m in muls))
         return self._idx_cache[key]
 
     def _imputation_split(self, impute, fin_cols: Tensor):

@@ -23,7 +23,7 @@ class AnemoiEnsModelEncProcDec(AnemoiModelEncProcDec):
     """``forward(x)``: ``x [1, T, E, G, V_in]`` -> ``[1, E, G, V_out]``; one noise embedding ``[E * N_mesh, K]`` per call, drawn
     before the processor and handed to every block.  Transformer processor only; single device."""
 
-    def __init__(self, *, model_config, data_indices, graph_data, truncation_data=None) -> None:
+    def __init__(self, *, model_config, data_indices, graph_data, truncation_data=None, statistics=None) -> None:
         target = str(model_config.model.processor.get("_target_", ""))
         if not target.endswith(".TransformerProcessor"):
             raise NotImplementedError(
@@ -33,7 +33,7 @@ class AnemoiEnsModelEncProcDec(AnemoiModelEncProcDec):
         if cfg is None:
             raise ValueError("AnemoiEnsModelEncProcDec: the config has no model.noise_injector")
         super().__init__(model_config=model_config, data_indices=data_indices, graph_data=graph_data,
-                         truncation_data=truncation_data)  # (the members are slabs of one projection launch)
+                         truncation_data=truncation_data, statistics=statistics)  # (the members are slabs of one projection launch)
         self.noise_injector = NoiseConditioning(
             noise_std=cfg["noise_std"], noise_channels_dim=cfg["noise_channels_dim"],
             noise_mlp_hidden_dim=cfg["noise_mlp_hidden_dim"], inject_noise=cfg.get("inject_noise", True))

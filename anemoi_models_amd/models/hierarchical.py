@@ -24,7 +24,7 @@ from .encoder_processor_decoder import instantiate
 class AnemoiModelEncProcDecHierarchical(AnemoiModelEncProcDec):
     """Message passing hierarchical graph network on MI355X kernels."""
 
-    def __init__(self, *, model_config, data_indices, graph_data, truncation_data=None) -> None:
+    def __init__(self, *, model_config, data_indices, graph_data, truncation_data=None, statistics=None) -> None:
         nn.Module.__init__(self)
         self._graph_data = graph_data
         self._graph_name_data = model_config.graph.data
@@ -106,12 +106,7 @@ class AnemoiModelEncProcDecHierarchical(AnemoiModelEncProcDec):
             src_grid_size=na.num_nodes[names[0]],
             dst_grid_size=na.num_nodes[data],
         )
-        self.boundings = nn.ModuleList(
-            [
-                instantiate(cfg, name_to_index=self.data_indices.internal_model.output.name_to_index)
-                for cfg in getattr(model_config.model, "bounding", [])
-            ]
-        )
+        self.boundings = self._build_boundings(model_config, statistics)
         self._idx_cache: dict = {}
         self._set_truncation(truncation_data)  # (the truncated skip connection of the shared ``_finish``)
 

@@ -1104,19 +1104,23 @@ def finalize_output(y: Tensor, x: Tensor, src: Tensor, in_affine=None, out_affin
 
 
 def bound_output(y: Tensor, op_col: Tensor, op_lo: Tensor, op_hi: Tensor, op_mul: Tensor,
-                 fin: Optional[tuple] = None, impute=None) -> Tensor:
+                 fin: Optional[tuple] = None, impute=None, slope: Optional[Tensor] = None) -> Tensor:
     """In place on the f32 output ``y`` ``[..., V_out]``: the ordered bounding ops (see ``layers.bounding.compile_boundings``)
     and, with ``fin = (cols int32, mul f32, add f32)``, the de-normalisation of those columns afterwards.
     ``impute`` (``preprocessing.imputer.Imputation`` whose ``out_nan_src`` holds ONE ENTRY PER ``fin`` COLUMN, -1 = none; ``y``
     is ``[..., G, V_out]`` with the map's ``G``): those columns get the NaNs of the static map back after their
-    de-normalisation (``anemoi_bound_output_imputed``)."""
-    _dev(y, op_col, op_lo, op_hi, op_mul)
+    de-normalisation (``anemoi_bound_output_imputed``).
+    ``slope`` (f32, one entry per op; ``layers.bounding.bounding_slopes``): a list with leaky classes -- every variant above on
+    ``anemoi_bound_output_leaky``; ``None``: exactly the launches of the hard classes."""
+    _dev(y, op_col, op_lo, op_hi, op_mul, slope)
     if y.dtype != torch.float32 or not y.is_contiguous():
         raise ValueError("bound_output: y must be contiguous float32")
     n_ops = op_col.numel()
     if op_col.dtype != torch.int32 or op_mul.dtype != torch.int32 or op_lo.dtype != torch.float32 or \
             op_hi.dtype != torch.float32 or op_lo.numel() != n_ops or op_hi.numel() != n_ops or op_mul.numel() != n_ops:
         raise ValueError("bound_output: op lists must be int32 / float32 vectors of one length")
+    if slope is not None and (slope.dtype != torch.float32 or slope.numel() != n_ops or not slope.is_contiguous()):
+        raise ValueError("bound_output: slope must be a contiguous float32 vector with one entry per op")
     fc = fm = fa = None
     if fin is not None:
         fc, fm, fa = fin
@@ -1133,17 +1137,74 @@ def bound_output(y: Tensor, op_col: Tensor, op_lo: Tensor, op_hi: Tensor, op_mul
             raise ValueError(f"bound_output: impute.nan_map must be a contiguous bool / uint8 [G = {y.shape[-2]}, W] tensor")
         if n_fin and (ons is None or ons.dtype != torch.int32 or ons.shape != (n_fin,) or not ons.is_contiguous()):
             raise ValueError(f"bound_output: impute.out_nan_src must be int32 with one entry per fin column ({n_fin})")
+        if slope is not None:
+            st = _lib.load().anemoi_bound_output_leaky(y.data_ptr(), v_out, y.numel() // max(v_out, 1), n_ops, _ptr(op_col),
+                                                       _ptr(op_lo), _ptr(op_hi), _ptr(op_mul), n_fin, _ptr(fc), _ptr(fm),
+                                                       _ptr(fa), y.shape[-2], nm.data_ptr(), int(impute.W),
+                                                       _ptr(ons) if n_fin else None, slope.data_ptr(), _stream())
+            _lib.check(st, "anemoi_bound_output_leaky")
+            return y
         st = _lib.load().anemoi_bound_output_imputed(y.data_ptr(), v_out, y.numel() // max(v_out, 1), n_ops, _ptr(op_col),
                                                      _ptr(op_lo), _ptr(op_hi), _ptr(op_mul), n_fin, _ptr(fc), _ptr(fm),
                                                      _ptr(fa), y.shape[-2], nm.data_ptr(), int(impute.W),
                                                      _ptr(ons) if n_fin else None, _stream())
         _lib.check(st, "anemoi_bound_output_imputed")
         return y
+    if slope is not None:
+        st = _lib.load().anemoi_bound_output_leaky(y.data_ptr(), v_out, y.numel() // max(v_out, 1), n_ops, _ptr(op_col),
+                                                   _ptr(op_lo), _ptr(op_hi), _ptr(op_mul), 0 if fc is None else fc.numel(),
+                                                   _ptr(fc), _ptr(fm), _ptr(fa), 0, None, 0, None, slope.data_ptr(), _stream())
+        _lib.check(st, "anemoi_bound_output_leaky")
+        return y
     st = _lib.load().anemoi_bound_output(y.data_ptr(), v_out, y.numel() // max(v_out, 1), n_ops, _ptr(op_col),
                                          _ptr(op_lo), _ptr(op_hi), _ptr(op_mul), 0 if fc is None else fc.numel(),
                                          _ptr(fc), _ptr(fm), _ptr(fa), _stream())
     _lib.check(st, "anemoi_bound_output")
     return y
+
+
+def _bound_train_lists(who: str, t: Tensor, op_col: Tensor, op_lo: Tensor, op_hi: Tensor, op_mul: Tensor, slope: Tensor) -> int:
+    _dev(t, op_col, op_lo, op_hi, op_mul, slope)
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() < 1:
+        raise ValueError(f"{who}: the [..., V_out] tensor must be contiguous float32")
+    n_ops = op_col.numel()
+    if op_col.dtype != torch.int32 or op_mul.dtype != torch.int32 or \
+            any(v.dtype != torch.float32 or v.numel() != n_ops or not v.is_contiguous() for v in (op_lo, op_hi, slope)) or \
+            op_mul.numel() != n_ops or not op_col.is_contiguous() or not op_mul.is_contiguous():
+        raise ValueError(f"{who}: op lists must be contiguous int32 / float32 vectors of one length")
+    return n_ops
+
+
+def bound_output_train(y: Tensor, op_col: Tensor, op_lo: Tensor, op_hi: Tensor, op_mul: Tensor, slope: Tensor,
+                       n_tape: int) -> Tensor:
+    """The bounding ops in place on the f32 ``y`` ``[..., V_out]`` as ``bound_output(slope=)`` applies them, and the tape of
+    ``anemoi_bound_output_train`` (returned; f32 ``[n_tape, rows]``: what every op read) for :func:`bound_output_backward`.
+    ``n_tape``: the number of ops plus the number of ops with a multiplier."""
+    n_ops = _bound_train_lists("bound_output_train", y, op_col, op_lo, op_hi, op_mul, slope)
+    v_out = y.shape[-1]
+    rows = y.numel() // max(v_out, 1)
+    tape = torch.empty((n_tape, rows), dtype=torch.float32, device=y.device)
+    st = _lib.load().anemoi_bound_output_train(y.data_ptr(), v_out, rows, n_ops, _ptr(op_col), _ptr(op_lo), _ptr(op_hi),
+                                               _ptr(op_mul), _ptr(slope), _ptr(tape), n_tape, _stream())
+    _lib.check(st, "anemoi_bound_output_train")
+    return tape
+
+
+def bound_output_backward(g: Tensor, tape: Tensor, op_col: Tensor, op_lo: Tensor, op_hi: Tensor, op_mul: Tensor,
+                          slope: Tensor) -> Tensor:
+    """The gradient with respect to the input of :func:`bound_output_train` from the gradient ``g`` (f32 ``[..., V_out]``, left
+    as it is) of its output and its tape: a new tensor (``anemoi_bound_output_backward``)."""
+    n_ops = _bound_train_lists("bound_output_backward", g, op_col, op_lo, op_hi, op_mul, slope)
+    _dev(g, tape)
+    v_out = g.shape[-1]
+    rows = g.numel() // max(v_out, 1)
+    if tape.dtype != torch.float32 or not tape.is_contiguous() or tape.dim() != 2 or tape.shape[1] != rows:
+        raise ValueError(f"bound_output_backward: the tape must be contiguous float32 [n_tape, rows = {rows}]")
+    dx = torch.empty_like(g)
+    st = _lib.load().anemoi_bound_output_backward(g.data_ptr(), dx.data_ptr(), v_out, rows, n_ops, _ptr(op_col), _ptr(op_lo),
+                                                  _ptr(op_hi), _ptr(op_mul), _ptr(slope), _ptr(tape), tape.shape[0], _stream())
+    _lib.check(st, "anemoi_bound_output_backward")
+    return dx
 
 
 def advance_input(x: Tensor, y: Tensor, colmap: Tensor, forcing: Optional[Tensor] = None) -> Tensor:

@@ -496,6 +496,24 @@ class _PrognosticResidual(torch.autograd.Function):
         return g.reshape(ctx.out_shape).to(ctx.out_dtype), dx, None, None
 
 
+def _bound(model, y: Tensor) -> Tensor:
+    """The boundings on the fresh f32 output ``y`` of a one-pass residual: ONE launch for the whole list, and one in the backward
+    (``autograd.bound_output``: ``anemoi_bound_output_train`` / ``anemoi_bound_output_backward``), whenever the list compiles
+    (``layers.bounding.compile_boundings``); the module loop -- a gather, an activation and an index_put per module, torch's index
+    accumulation per module in the backward -- for a class this package does not know.  ``ANEMOI_AMD_TRAIN_FUSED_BOUND=0``
+    keeps the module loop for every list (A/B)."""
+    if len(model.boundings) == 0:
+        return y
+    plan = None
+    if os.environ.get("ANEMOI_AMD_TRAIN_FUSED_BOUND", "1") != "0" and y.is_cuda and y.dtype == torch.float32:
+        plan = model._bounding_train_plan(y.device)
+    if plan is None:
+        for bounding in model.boundings:
+            y = bounding(y)
+        return y
+    return autograd.bound_output(y, *plan)
+
+
 def _finish(model, out: Tensor, x: Tensor, b: int, ens: int, g: int) -> Tensor:
     truncation = getattr(model, "_truncation", None)  # (layers.truncation.TruncationPlan: x_skip = A_up (A_down x[:, -1]))
     if (out.is_cuda and _fused_io(x) and x.dtype == torch.float32 and x.dim() == 5
@@ -503,18 +521,14 @@ def _finish(model, out: Tensor, x: Tensor, b: int, ens: int, g: int) -> Tensor:
         if truncation is not None:
             o_idx, i_idx = model._prognostic_indices(x.device)
             y = autograd.truncated_residual(out, x, truncation, o_idx, i_idx, (b, ens, g, out.shape[-1]), model._idx_cache)
-            for bounding in model.boundings:
-                y = bounding(y)
-            return y
+            return _bound(model, y)
         key = ("residual_src", str(x.device))  # (the inference route's column map, models/encoder_processor_decoder.py::_finish)
         if key not in model._idx_cache:
             src = torch.full((model.num_output_channels,), -1, dtype=torch.int32)
             src[torch.as_tensor(model._internal_output_idx).long()] = torch.as_tensor(model._internal_input_idx).to(torch.int32)
             model._idx_cache[key] = src.to(x.device)
         y = _PrognosticResidual.apply(out, x, model._idx_cache[key], (b, ens, g, out.shape[-1]))
-        for bounding in model.boundings:
-            y = bounding(y)
-        return y
+        return _bound(model, y)
     y = out.float().reshape(b, ens, g, -1).to(x.dtype).clone()
     key = ("prognostic_long", str(x.device))  # index tensors resident on the device: a Python list here costs an upload
     if key not in model._idx_cache:           # and a device synchronisation per step

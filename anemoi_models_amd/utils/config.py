@@ -48,6 +48,18 @@ def resolve_target(target: str):
     return getattr(importlib.import_module(module), name)
 
 
+def target_accepts(config, argument: str) -> bool:
+    """Does the constructor of ``config["_target_"]`` take the keyword ``argument`` (by name or through ``**kwargs``)?  For
+    optional arguments newer than the reference's signatures: a user's own class that predates one is built without it."""
+    import inspect
+
+    try:
+        params = inspect.signature(resolve_target(config["_target_"]).__init__).parameters
+    except (KeyError, TypeError, ValueError, ImportError, AttributeError):
+        return False
+    return argument in params or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values())
+
+
 def instantiate(config, *args, **kwargs):
     """Create ``config["_target_"](*args, **config_without_meta_keys, **kwargs)``."""
     cfg = dict(config)

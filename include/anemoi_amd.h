@@ -412,6 +412,48 @@ int anemoi_bound_output_imputed(float* y, int V_out, int64_t rows, int n_ops, co
                                 const int32_t* fin_nan_src, anemoi_stream_t stream);
 
 /*
+ * Boundings with a slope (layers/bounding.py: NormalizedReluBounding and the Leaky* classes of current anemoi-models).
+ * Additive: no existing signature changes and the ABI version is unchanged.  One op i becomes, with s = op_slope[i],
+ *   f_i(v) = v < lo[i] ? lo[i] + s (v - lo[i]) : v > hi[i] ? hi[i] + s (v - hi[i]) : v
+ *   y[col[i]] = f_i(y[col[i]]) * (mul[i] >= 0 ? y[mul[i]] : 1)
+ * (comparisons: a NaN stays a NaN; s = 0 is the hard op of anemoi_bound_output, bit for bit).  Leaky ReLU: lo = 0, hi = +inf,
+ * s = 0.01; leaky hardtanh / fraction: lo = min_val, hi = max_val, s = 0.01; (leaky) normalised ReLU: lo = the variable's
+ * threshold in normalised space, hi = +inf, s = 0 (0.01).
+ *
+ * anemoi_bound_output_leaky: the arguments of anemoi_bound_output_imputed plus op_slope (f32 [n_ops], not NULL).  The same
+ * kernel template with a second compile-time flag; anemoi_bound_output / _imputed keep launching the instantiations without
+ * it.  nan_map == NULL: no NaN is restored (G, W and fin_nan_src are then ignored).
+ */
+int anemoi_bound_output_leaky(float* y, int V_out, int64_t rows, int n_ops, const int32_t* op_col, const float* op_lo,
+                              const float* op_hi, const int32_t* op_mul, int n_fin, const int32_t* fin_col,
+                              const float* fin_mul, const float* fin_add, int64_t G, const uint8_t* nan_map, int W,
+                              const int32_t* fin_nan_src, const float* op_slope, anemoi_stream_t stream);
+
+/*
+ * The bounding list of the TRAINING forward as a differentiable pair (csrc/bounding.hip), one launch each way.
+ *
+ * anemoi_bound_output_train: the op walk above, in place on y [rows, V_out] (f32, no de-normalisation), which also writes the
+ * TAPE the backward needs: walking i = 0..n_ops-1, the value op i read and, when mul[i] >= 0, the multiplier it read, one
+ * entry each, entry e of row r at tape[e * rows + r].  n_tape = n_ops + the number of ops with mul[i] >= 0 (the caller counts
+ * them; entries at or past n_tape are neither written nor read).  Column indices within [0, V_out) are the caller's to
+ * guarantee, as for anemoi_bound_output.
+ *
+ * anemoi_bound_output_backward: dx [rows, V_out] (a buffer of its own: g is read only, the two must not overlap) from the
+ * incoming gradient g [rows, V_out], the tape and the same op lists.  dx = g, then for i = n_ops-1..0 on every row:
+ *   go = dx[col[i]];  dx[col[i]] = go * f_i'(v) * ym;  if mul[i] >= 0: dx[mul[i]] += go * f_i(v)
+ * (v, ym: the tape's entries of op i; ym = 1 without a multiplier).  f_i'(v) = 1 strictly inside (lo[i], hi[i]) and s
+ * elsewhere, the bounds included: the convention of torch's relu / hardtanh / leaky_relu backward at the kinks.
+ *
+ * Both: no atomics, no workspace, nothing read back (capturable), the same bits on every run.
+ */
+int anemoi_bound_output_train(float* y, int V_out, int64_t rows, int n_ops, const int32_t* op_col, const float* op_lo,
+                              const float* op_hi, const int32_t* op_mul, const float* op_slope, float* tape, int n_tape,
+                              anemoi_stream_t stream);
+int anemoi_bound_output_backward(const float* g, float* dx, int V_out, int64_t rows, int n_ops, const int32_t* op_col,
+                                 const float* op_lo, const float* op_hi, const int32_t* op_mul, const float* op_slope,
+                                 const float* tape, int n_tape, anemoi_stream_t stream);
+
+/*
  * Remappers folded into predict_step's I/O kernels (csrc/remap.hip; preprocessing/monomapper.py, multimapper.py: log1p,
  * sqrt, boxcox with lambda 1/2, cos_sin).  A remapper is a per-column function of the raw state whose internal layout
  * may be wider than the raw one (V_int != V_raw).  Additive: no existing signature changes and the ABI version is unchanged.
