@@ -41,6 +41,7 @@ ENS_AFCRPS, ENS_MEAN_SE, ENS_VARIANCE = 0, 1, 2
 ENS_KINDS = {"afcrps": ENS_AFCRPS, "mean_se": ENS_MEAN_SE, "variance": ENS_VARIANCE}
 ENS_MAX_MEMBERS = 16
 
+HEAD_NORM_MAX_D = 128  # the widest head of anemoi_head_norm (HN_MAX_D of csrc/head_norm.hip)
 COND_LN_MAX_K = 32  # the fused conditional LayerNorm's widest condition (CLN_MAX_K of csrc/cond_layer_norm.hip)
 
 
@@ -387,6 +388,11 @@ SIGNATURES = {
     "anemoi_cond_layer_norm_backward": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int,
                                                 c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                                 c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "anemoi_head_norm": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int,
+                                 c_float, c_void_p]),
+    "anemoi_head_norm_backward_workspace_floats": (c_int64, [c_int64, c_int, c_int, c_int]),
+    "anemoi_head_norm_backward": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                          c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "anemoi_gaussian_noise": (c_int, [c_void_p, c_int64, c_int, c_float, c_uint32, c_void_p, c_void_p]),
     "anemoi_transpose": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "anemoi_transpose_colsum_rows": (c_int64, [c_int64, c_int64]),

@@ -475,6 +475,60 @@ def cond_layer_norm_fused(k: int) -> bool:
     return k <= _lib.COND_LN_MAX_K and os.environ.get("ANEMOI_AMD_COND_LN", "fused") != "composed"
 
 
+class _HeadNorm(torch.autograd.Function):
+    """``qk_norm`` (``anemoi_head_norm`` / ``_backward``) on the columns ``[col0, col0 + groups * H * D)`` of ``x``: out of place --
+    the pre-norm columns are what the backward reads, so ``x`` is kept and the result is a new matrix of ``x``'s width whose
+    other columns are copies (``v`` of ``q | k | v``, ``x_r`` and ``v`` of ``x_r | q | k | v``).  Per element of the normalised
+    columns the forward moves one read and one write, the backward three reads and one write (``dy`` and ``x`` once for
+    ``dx``, once more for the column sums of ``dweight``); the in-place alternative would have to save a copy of the pre-norm
+    columns first (one more read and write in the forward) to spare the copy of the other columns here."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, weight: Tensor, num_heads: int, groups: int, eps: float, col0: int, width: int):
+        rows, total = x.shape
+        y = torch.empty((rows, total), dtype=x.dtype, device=x.device)
+        _, stats = ops.head_norm(x[:, col0:col0 + width], weight, num_heads, groups, eps, out=y[:, col0:col0 + width],
+                                 with_stats=True)
+        if col0 > 0:
+            y[:, :col0].copy_(x[:, :col0])
+        if col0 + width < total:
+            y[:, col0 + width:].copy_(x[:, col0 + width:])
+        ctx.save_for_backward(x, stats, weight)
+        ctx.args = (num_heads, groups, col0, width)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        x, stats, weight = ctx.saved_tensors
+        num_heads, groups, col0, width = ctx.args
+        dy = dy if dy.stride(-1) == 1 else dy.contiguous()
+        dx = torch.empty_like(x)
+        _, dw = ops.head_norm_backward(dy[:, col0:col0 + width], x[:, col0:col0 + width], stats, weight, num_heads, groups,
+                                       out=dx[:, col0:col0 + width])
+        if col0 > 0:
+            dx[:, :col0].copy_(dy[:, :col0])
+        if col0 + width < x.shape[1]:
+            dx[:, col0 + width:].copy_(dy[:, col0 + width:])
+        return dx, dw.view(weight.shape).to(weight.dtype), None, None, None, None, None
+
+
+def head_norm(x: Tensor, weight: Tensor, num_heads: int, groups: int = 1, eps: float = 1e-5, col0: int = 0,
+              width: Optional[int] = None) -> Tensor:
+    """``qk_norm`` with gradients for ``x`` and ``weight``: the bias-free LayerNorm over every head of ``x [rows, groups * H * D]``
+    scaled by ``weight [groups, D]`` (``ops.head_norm``, bit-equal in the forward).  ``col0`` / ``width``: normalise only these
+    columns of a wider ``x`` (``q | k`` inside ``q | k | v``) and hand the others through -- the result has ``x``'s width."""
+    if x.dim() != 2:
+        raise ValueError(f"head_norm: expected [rows, columns], got shape {tuple(x.shape)}")
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    return _HeadNorm.apply(x, weight, num_heads, groups, eps, col0, x.shape[1] - col0 if width is None else width)
+
+
+def qk_weight(q_weight: Tensor, k_weight: Tensor) -> Tensor:
+    """``[2, D]``: the weights of ``q_norm`` and ``k_norm`` stacked for one ``groups = 2`` launch (differentiable)."""
+    return torch.stack([q_weight, k_weight])
+
+
 class _ScaledLinear(torch.autograd.Function):
     """``y = s[:, None] * (x @ f.T) + b``: ``x [M, Kp]`` in the compute dtype (K padded), ``f [N, Kp]`` / ``b [N]`` f32,
     ``s [M]`` f32 -- the product behind a LayerNorm whose mean has been removed algebraically (``s`` = the row's rstd).
@@ -991,6 +1045,15 @@ def _lin_edge_fold(sd: dict, prefix: str, c: int, h: int, up: int, device):
     return w_u, b_u, w_t
 
 
+QK_NORM_EPS = 1e-5  # of ``q_norm`` / ``k_norm`` (``nn.LayerNorm``'s default; the state dict carries no epsilon)
+
+
+def has_qk_norm(sd: dict, prefix: str) -> bool:
+    """Does the block ``prefix`` of ``sd`` carry ``q_norm`` / ``k_norm`` (``qk_norm=True``)?  Such a block normalises q and k between
+    the product that forms them and the edge phase, which rules out every route that folds ``lin_edge`` into that product."""
+    return prefix + ".q_norm.weight" in sd
+
+
 FOLD_MAX_UP = 16  # widest per-head edge representation of the folded edge kernels (edge_dim + 1 rounded up to 4)
 
 
@@ -1090,7 +1153,7 @@ def gt_processor_weights(sds: list, prefix: str, c: int, h: int, up: int, dtype:
     count = len(sds)
     km = ops.k_multiple(dtype)
     if (os.environ.get("ANEMOI_AMD_TRAIN_BATCHED_PARAMS", "1") == "0" or dtype != torch.bfloat16 or count < 2
-            or not folded_edge_route(dtype, c, h, up) or c % km != 0 or (h * up) % km != 0):
+            or any(has_qk_norm(sd, prefix) for sd in sds) or not folded_edge_route(dtype, c, h, up) or c % km != 0 or (h * up) % km != 0):
         return None
     names = ("lin_self", "lin_query", "lin_key", "lin_value", "lin_edge", "projection", "node_dst_mlp.1", "node_dst_mlp.3")
     key = lambda sd, n, part: sd.get(f"{prefix}.{n}.{part}")  # noqa: E731
@@ -1161,6 +1224,9 @@ def gt_processor_block(x: Tensor, sd: dict, prefix: str, edge_attr_csr: Tensor, 
     g = lambda name: sd[prefix + "." + name]  # noqa: E731
     c = x.shape[1]
     h, up = num_heads, edge_attr_csr.shape[1]
+    qk_norm = has_qk_norm(sd, prefix)
+    if prepared is not None and qk_norm:
+        raise ValueError("gt_processor_block: the prepared weights carry the lin_edge fold, which a block with qk_norm does not take")
     if prepared is not None:
         xh, x = layer_norm_skip(x, g("layer_norm1.weight"), g("layer_norm1.bias"), eps)
         sq = linear(xh, prepared.w_in, prepared.b_in, prep=prepared.p_in)  # x_r | q | k | v | u
@@ -1169,10 +1235,14 @@ def gt_processor_block(x: Tensor, sd: dict, prefix: str, edge_attr_csr: Tensor, 
         else:
             att = _GTEdgeAttentionSelf.apply(sq, edge_attr_csr, plan, h, up)
         return _gt_tail(att, x, sd, prefix, None, act, eps, prepared)
-    if not folded_edge_route(x.dtype, c, h, up):  # lin_edge as a GEMM, the conv on explicit per-edge features
+    # lin_edge as a GEMM, the conv on explicit per-edge features: shapes without a folded kernel, and qk_norm (u = q W_e comes
+    # out of the GEMM that forms q; the scores need the normalised q)
+    if qk_norm or not folded_edge_route(x.dtype, c, h, up):
         xh = layer_norm(x, g("layer_norm1.weight"), g("layer_norm1.bias"), eps)
         sq = linear(xh, torch.cat([g("lin_self.weight"), g("lin_query.weight"), g("lin_key.weight"), g("lin_value.weight")], 0),
                     torch.cat([g("lin_self.bias"), g("lin_query.bias"), g("lin_key.bias"), g("lin_value.bias")], 0))
+        if qk_norm:  # q | k are adjacent in x_r | q | k | v: one launch
+            sq = head_norm(sq, qk_weight(g("q_norm.weight"), g("k_norm.weight")), h, 2, QK_NORM_EPS, c, 2 * c)
         if plan.col.shape[0] == 0:  # an edge set without edges: the conv's sums are empty, x_r passes through
             att = sq[:, :c].contiguous()
         else:
@@ -1208,12 +1278,17 @@ def gt_mapper_block(x_src: Optional[Tensor], x_dst: Tensor, sd: dict, prefix: st
         kv = kv_fn(w_kv, b_kv, g("layer_norm1.weight"), g("layer_norm1.bias"))
     else:
         kv = linear(layer_norm(x_src, g("layer_norm1.weight"), g("layer_norm1.bias"), eps), w_kv, b_kv)
-    folded = folded_edge_route(x_dst.dtype, c, h, up)
+    qk_norm = has_qk_norm(sd, prefix)
+    if qk_norm:  # (kv_fn forms the same k | v product from the raw rows: the norm applies to its k columns all the same)
+        kv = head_norm(kv, g("k_norm.weight"), h, 1, QK_NORM_EPS, 0, c)
+    folded = not qk_norm and folded_edge_route(x_dst.dtype, c, h, up)  # qk_norm: see gt_processor_block
     if sq_fn is None or not folded:
         xd, x_dst = layer_norm_skip(x_dst, g("layer_norm2.weight"), g("layer_norm2.bias"), eps)
     if not folded:  # see gt_processor_block
         sq = linear(xd, torch.cat([g("lin_self.weight"), g("lin_query.weight")], 0),
                     torch.cat([g("lin_self.bias"), g("lin_query.bias")], 0))
+        if qk_norm:
+            sq = head_norm(sq, g("q_norm.weight"), h, 1, QK_NORM_EPS, c, c)
         if plan.col.shape[0] == 0:  # (see gt_processor_block)
             att = sq[:, :c].contiguous()
         else:

@@ -374,6 +374,19 @@ def _refuse_truncation(model) -> None:
         raise NotImplementedError(REFUSAL)
 
 
+def _refuse_qk_norm(model) -> None:
+    """GraphTransformer mappers / processors built with ``qk_norm`` are refused before any plan is built: the local-graph blocks
+    of the node-partitioned routes are written on the folded edge kernels, which have no qk_norm.  (The Transformer processor
+    keeps its routes: the norm is row- and head-local.)"""
+    from ..layers.mapper import GraphTransformerBaseMapper
+    from ..layers.processor import GraphTransformerProcessor
+
+    for part in (model.encoder, model.processor, model.decoder):
+        if isinstance(part, (GraphTransformerBaseMapper, GraphTransformerProcessor)) and part.qk_norm:
+            raise NotImplementedError("qk_norm: node-partitioned GraphTransformer blocks need the folded edge kernel, which "
+                                      "has no qk_norm")
+
+
 def sharded_forward(model, x: Tensor, group, input_affine=None, output_affine=None, local_output: bool = False):
     """Full-input / full-output forward with the mesh partitioned over ``group`` (batch size 1, as in the reference).
 
@@ -381,6 +394,7 @@ def sharded_forward(model, x: Tensor, group, input_affine=None, output_affine=No
     skipped and ``(y_local [rows, V_out] f32 WITHOUT the prognostic residual, shard plan)`` is returned; of ``x`` only
     the grid rows this rank's encoder and decoder read (``enc_src_ids``, ``dec_dst_ids``) need to be valid."""
     _refuse_truncation(model)
+    _refuse_qk_norm(model)
     if getattr(input_affine, "impute", None) is not None:
         raise NotImplementedError("the node-partitioned forward takes no imputation (predict_step takes its generic route)")
     if torch.is_grad_enabled() and any(p.requires_grad for p in model.parameters()):
@@ -542,6 +556,7 @@ def sharded_training_forward(model, x: Tensor, group) -> Tensor:
     from ..layers.processor import GraphTransformerProcessor
 
     _refuse_truncation(model)
+    _refuse_qk_norm(model)
     gt_maps = isinstance(model.encoder, GraphTransformerBaseMapper) and isinstance(model.decoder, GraphTransformerBaseMapper)
     gnn_maps = isinstance(model.encoder, GNNBaseMapper) and isinstance(model.decoder, GNNBaseMapper)
     from ..layers.processor import TransformerProcessor

@@ -1,6 +1,9 @@
 """Multi-head self attention over the mesh nodes, mirroring reference layers/attention.py:34-112.
 
-Parameters: ``lin_qkv`` (no bias by default) and ``projection`` (bias) -- identical ``state_dict`` keys.
+Parameters: ``lin_qkv`` (no bias by default) and ``projection`` (bias) -- identical ``state_dict`` keys.  ``qk_norm=True`` (the
+switch of current anemoi-models, newer than the pinned reference) adds ``q_norm`` / ``k_norm``, bias-free LayerNorms over the
+head dimension of the queries and keys (keys ``q_norm.weight``, ``k_norm.weight``): one in-place ``anemoi_head_norm`` launch on the
+``q | k`` columns of the ``lin_qkv`` product, in front of the attention kernel.
 """
 
 from __future__ import annotations
@@ -19,7 +22,7 @@ from .mlp import linear_native
 
 class MultiHeadSelfAttention(nn.Module):
     def __init__(self, num_heads: int, embed_dim: int, bias: bool = False, is_causal: bool = False,
-                 window_size: Optional[int] = None, dropout_p: float = 0.0):
+                 window_size: Optional[int] = None, dropout_p: float = 0.0, qk_norm: bool = False):
         super().__init__()
         assert (
             embed_dim % num_heads == 0
@@ -32,6 +35,10 @@ class MultiHeadSelfAttention(nn.Module):
         self.is_causal = is_causal
         self.lin_qkv = nn.Linear(embed_dim, 3 * embed_dim, bias=bias)
         self.projection = nn.Linear(embed_dim, embed_dim, bias=True)
+        self.qk_norm = qk_norm
+        if qk_norm:
+            self.q_norm = nn.LayerNorm(self.head_dim, bias=False)
+            self.k_norm = nn.LayerNorm(self.head_dim, bias=False)
 
         self._packed = runtime.PackedWeights()
 
@@ -69,8 +76,29 @@ class MultiHeadSelfAttention(nn.Module):
         self.__dict__["_layer_seed"] = seed
         return float(self.dropout_p), seed, dd.word
 
+    def qk_norm_weight(self) -> Tensor:
+        """f32 ``[2, D]``: the weights of ``q_norm`` and ``k_norm`` stacked (cached, keyed on the parameters' versions)."""
+        params = [self.q_norm.weight, self.k_norm.weight]
+        return self._packed.get(("qk_norm", "w"), params, lambda: torch.stack([p.detach().float() for p in params]).contiguous())
+
+    def norm_qk_(self, qkv: Tensor) -> Tensor:
+        """``qk_norm`` in place on the ``q | k`` columns of ``qkv [rows, 3C]`` (a no-op without the switch)."""
+        if self.qk_norm:
+            qk = qkv[:, :2 * self.embed_dim]
+            ops.head_norm(qk, self.qk_norm_weight(), self.num_heads, 2, self.q_norm.eps, out=qk)
+        return qkv
+
+    def norm_qk(self, qkv: Tensor) -> Tensor:
+        """The same with gradients (out of place: the backward reads the pre-norm columns)."""
+        if not self.qk_norm:
+            return qkv
+        from .. import autograd
+
+        return autograd.head_norm(qkv, autograd.qk_weight(self.q_norm.weight, self.k_norm.weight), self.num_heads, 2,
+                                  self.q_norm.eps, 0, 2 * self.embed_dim)
+
     def native(self, x: Tensor, batch_size: int) -> Tensor:
-        qkv = linear_native(self._packed, "lin_qkv", self.lin_qkv, x)  # [B*S, 3C] = q | k | v
+        qkv = self.norm_qk_(linear_native(self._packed, "lin_qkv", self.lin_qkv, x))  # [B*S, 3C] = q | k | v
         p, seed, seed_dev = self.dropout()
         att = ops.mhsa(qkv, batch_size, self.num_heads, self.attention_window(), dropout_p=p, dropout_seed=seed,
                        seed_dev=seed_dev)
@@ -88,10 +116,10 @@ class MultiHeadSelfAttention(nn.Module):
         grad = training.wants_grad(self, x)
         dtype = runtime.compute_dtype(x)
         xin = training._cast(x, dtype)
-        if grad:
-            qkv = autograd.linear(xin, self.lin_qkv.weight, self.lin_qkv.bias)
+        if grad:  # (qk_norm is row- and head-local: it commutes with the exchange, and runs on the own rows before it)
+            qkv = self.norm_qk(autograd.linear(xin, self.lin_qkv.weight, self.lin_qkv.bias))
         else:
-            qkv = linear_native(self._packed, "lin_qkv", self.lin_qkv, xin)
+            qkv = self.norm_qk_(linear_native(self._packed, "lin_qkv", self.lin_qkv, xin))
         n_local, h, d = qkv.shape[0], self.num_heads, self.head_dim
         # [n_local, 3, H, D] -> three (1, H, n_local, D) tensors, the layout the reference hands to shard_heads
         q, k, v = (qkv.view(n_local, 3, h, d)[:, i].permute(1, 0, 2).unsqueeze(0) for i in range(3))
@@ -126,7 +154,7 @@ class MultiHeadSelfAttention(nn.Module):
 
         if training.wants_grad(self, x):  # reference layers/attention.py:67-112 with an autograd graph
             xin = training._cast(x, runtime.compute_dtype(x))
-            qkv = autograd.linear(xin, self.lin_qkv.weight, self.lin_qkv.bias)
+            qkv = self.norm_qk(autograd.linear(xin, self.lin_qkv.weight, self.lin_qkv.bias))
             p, seed, seed_dev = self.dropout()
             att = autograd.mhsa(qkv, batch_size, self.num_heads, self.attention_window(), p, seed, seed_dev=seed_dev)
             return autograd.linear(att, self.projection.weight, self.projection.bias)

@@ -157,10 +157,12 @@ class GraphTransformerBaseBlock(BaseBlock, ABC):
         activation: str = "GELU",
         num_chunks: int = 1,
         update_src_nodes: bool = False,
+        qk_norm: bool = False,
         **kwargs,
     ) -> None:
         super().__init__(**kwargs)
         self.update_src_nodes = update_src_nodes
+        self.qk_norm = qk_norm
         self.out_channels_conv = out_channels // num_heads
         self.num_heads = num_heads
         self.num_chunks = num_chunks
@@ -175,6 +177,9 @@ class GraphTransformerBaseBlock(BaseBlock, ABC):
         self.lin_edge = nn.Linear(edge_dim, width)
         self.conv = GraphTransformerConv(out_channels=self.out_channels_conv)
         self.projection = nn.Linear(out_channels, out_channels)
+        if qk_norm:  # bias-free LayerNorms over the head dimension of the queries and keys (current anemoi-models)
+            self.q_norm = nn.LayerNorm(self.out_channels_conv, bias=False)
+            self.k_norm = nn.LayerNorm(self.out_channels_conv, bias=False)
 
         act = activation_class(activation)
         self.node_dst_mlp = nn.Sequential(
@@ -287,8 +292,10 @@ class GraphTransformerBaseBlock(BaseBlock, ABC):
     # ---- lin_edge folded into the neighbouring GEMMs (see include/anemoi_amd.h: anemoi_gt_edge_attention_folded)
     def fold_width(self, dtype) -> Optional[int]:
         """Per-head width ``up`` of the folded edge representation (``edge_dim`` attributes + the constant 1,
-        rounded up to 4), or ``None`` when this shape has to use the unfolded kernel."""
-        if not runtime.edge_fold_enabled():
+        rounded up to 4), or ``None`` when this shape has to use the unfolded kernel.  ``qk_norm`` has no fold: ``u = q W_e`` comes
+        out of the GEMM that forms ``q``, and the queries of the scores are normalised after that GEMM.  This one switch takes the
+        block off every route built on the fold (``route``: "unfolded"; no block-level entry point, decoder fold, raw source rows)."""
+        if self.qk_norm or not runtime.edge_fold_enabled():
             return None
         vec = 16 // dtype.itemsize  # (asked several times per forward, by ``route`` among others: no tensor for it)
         d, h = self.out_channels_conv, self.num_heads
@@ -431,6 +438,41 @@ class GraphTransformerBaseBlock(BaseBlock, ABC):
 
     block_abi = True  # False: op by op (tests compare the two routes)
 
+    def _norm_qk_(self, q: Optional[Tensor], k: Optional[Tensor], qk: Optional[Tensor] = None) -> None:
+        """``qk_norm`` in place on the ``q`` and ``k`` column slices of the products in front of the edge phase -- ``qk``: the
+        ``q | k`` columns where ``k`` follows ``q`` in one matrix (the processor block's ``x_r | q | k | v``), ONE ``groups = 2``
+        launch; else one launch each for ``q`` (destination rows) and ``k`` (source rows).  A no-op without the switch."""
+        if not self.qk_norm:
+            return
+        h = self.num_heads
+        params = [self.q_norm.weight, self.k_norm.weight]
+        w = self._packed.get(("qk_norm", "w"), params, lambda: torch.stack([p.detach().float() for p in params]).contiguous())
+        if qk is not None:
+            ops.head_norm(qk, w, h, 2, self.q_norm.eps, out=qk)
+            return
+        ops.head_norm(q, w[0], h, 1, self.q_norm.eps, out=q)
+        ops.head_norm(k, w[1], h, 1, self.k_norm.eps, out=k)
+
+    def _norm_qk_grad(self, q: Tensor, k: Tensor):
+        """The same with gradients, on separate ``q`` and ``k`` (the head-sharded protocol: before the rows -> heads exchange)."""
+        if not self.qk_norm:
+            return q, k
+        from .. import autograd
+
+        return (autograd.head_norm(q, self.q_norm.weight, self.num_heads, 1, self.q_norm.eps),
+                autograd.head_norm(k, self.k_norm.weight, self.num_heads, 1, self.k_norm.eps))
+
+    def _qk_norm_refuse(self, dtype, halo) -> None:
+        """The routes ``qk_norm`` does not have, refused before anything is launched."""
+        if not self.qk_norm:
+            return
+        if halo is not None:
+            raise NotImplementedError("qk_norm: node-partitioned GraphTransformer blocks need the folded edge kernel, which "
+                                      "has no qk_norm")
+        if runtime.mxfp8_enabled(dtype):
+            raise NotImplementedError("qk_norm: ANEMOI_AMD_MXFP8=1 runs the GraphTransformer blocks on the folded edge kernel, "
+                                      "which has no qk_norm")
+
     @staticmethod
     def _att_buffer(n: int, ld: int, written: int, dtype, device) -> Tensor:
         """The projection's operand ``[n, ld]``: the edge phase writes the first ``written`` columns, the K padding behind
@@ -531,6 +573,7 @@ class GraphTransformerProcessorBlock(GraphTransformerBaseBlock):
         """
         dtype = x.dtype
         self._check_channels(dtype)
+        self._qk_norm_refuse(dtype, halo)
         if runtime.mxfp8_enabled(dtype):
             return self._native_mx(x, edge_attr_csr, plan, halo)
         c = self.num_heads * self.out_channels_conv
@@ -551,6 +594,7 @@ class GraphTransformerProcessorBlock(GraphTransformerBaseBlock):
             sq = self._ln_product(xh, "sqkvu" if up is not None else "sqkv",
                                   [self.lin_self, self.lin_query, self.lin_key, self.lin_value], up)
             k, v, u = sq[:, 2 * c:3 * c], sq[:, 3 * c:4 * c], sq[:, 4 * c:]
+            self._norm_qk_(None, None, sq[:, c:3 * c])
         q, x_r, next_eps = sq[:, c:2 * c], sq[:, :c], self._next_ln_eps(dtype)
         done = None if up is None else self._block_tail(q, k, v, x_r, u, edge_attr_csr, plan, x, up, next_eps)
         if done is not None:
@@ -609,6 +653,7 @@ class GraphTransformerProcessorBlock(GraphTransformerBaseBlock):
         h = autograd.layer_norm(x, ln.weight, ln.bias, ln.eps)
         x_r, q, k, v = (autograd.linear(h, lin.weight, lin.bias) for lin in (self.lin_self, self.lin_query, self.lin_key,
                                                                               self.lin_value))
+        q, k = self._norm_qk_grad(q, k)
         e = autograd.linear(_as_compute(edge_attr, dtype), self.lin_edge.weight, self.lin_edge.bias)
         q, k, v, e = self.shard_qkve_heads(q, k, v, e, shapes, batch_size, model_comm_group)
         out = self.conv(q, k, v, e, edge_index, size=size)
@@ -715,6 +760,7 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
         tail.  Large intermediates are dropped before the next stage allocates."""
         dtype = x_dst.dtype
         self._check_channels(dtype)
+        self._qk_norm_refuse(dtype, halo)
         src, dst = Rows.of(x_src), Rows.of(x_dst)
         r = self.route(dtype, src, dst, num_chunks, halo is not None)
         # the hand-over: a mapper that asked ``route`` formed every ``h`` the route reads; other callers may not have
@@ -786,6 +832,7 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
             done = self._block_tail(q, k, v, x_r, u, edge_attr_csr, plan, res, up, out_stats_eps) if r.block_tail else None
             if done is not None:
                 return h_src, done
+            self._norm_qk_(q, k)
             att, wp, bp = self._attention(q, k, v, x_r, u, edge_attr_csr, plan, up)
             del q, k, v, x_r, u
         del sq, kv
@@ -885,6 +932,7 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
         q = autograd.linear(hd, self.lin_query.weight, self.lin_query.bias)
         k = autograd.linear(hs, self.lin_key.weight, self.lin_key.bias)
         v = autograd.linear(hs, self.lin_value.weight, self.lin_value.bias)
+        q, k = self._norm_qk_grad(q, k)
         e = autograd.linear(_as_compute(edge_attr, dtype), self.lin_edge.weight, self.lin_edge.bias)
         q, k, v, e = self.shard_qkve_heads(q, k, v, e, shapes, batch_size, model_comm_group)
         out = self.conv(q, k, v, e, edge_index, size=size)
@@ -1124,7 +1172,7 @@ class GraphConvMapperBlock(GraphConvBaseBlock):
 # =============================================================================================
 class TransformerProcessorBlock(BaseBlock):
     def __init__(self, num_channels: int, hidden_dim: int, num_heads: int, activation: str, window_size: int,
-                 dropout_p: float = 0.0, cond_dim: Optional[int] = None):
+                 dropout_p: float = 0.0, cond_dim: Optional[int] = None, qk_norm: bool = False):
         super().__init__()
         from .attention import MultiHeadSelfAttention
 
@@ -1135,7 +1183,7 @@ class TransformerProcessorBlock(BaseBlock):
             lambda: ConditionalLayerNorm(num_channels, cond_dim))
         self.layer_norm1 = norm()
         self.attention = MultiHeadSelfAttention(num_heads=num_heads, embed_dim=num_channels, window_size=window_size,
-                                                bias=False, is_causal=False, dropout_p=dropout_p)
+                                                bias=False, is_causal=False, dropout_p=dropout_p, qk_norm=qk_norm)
         self.mlp = nn.Sequential(nn.Linear(num_channels, hidden_dim), act(), nn.Linear(hidden_dim, num_channels))
         self.layer_norm2 = norm()
 
@@ -1160,7 +1208,7 @@ class TransformerProcessorBlock(BaseBlock):
         att = self.attention
         if cond is not None:  # op by op: the block-level entry point knows the plain LayerNorm only
             h = ln1.native(x, cond)
-            qkv = linear_native(att._packed, "lin_qkv", att.lin_qkv, h)
+            qkv = att.norm_qk_(linear_native(att._packed, "lin_qkv", att.lin_qkv, h))
             drop_p, drop_seed, drop_dev = att.dropout()
             a = ops.mhsa(qkv, batch_size, att.num_heads, att.attention_window(), dropout_p=drop_p, dropout_seed=drop_seed,
                          seed_dev=drop_dev)
@@ -1173,7 +1221,8 @@ class TransformerProcessorBlock(BaseBlock):
             if done is not None:
                 return done
         h = ops.layer_norm(x, runtime.f32c(ln1.weight), runtime.f32c(ln1.bias), ln1.eps)
-        qkv = linear_native(att._packed, "lin_qkv", att.lin_qkv, h)
+        # qk_norm is row- and head-local: on the own rows' q | k, in front of the rows -> heads exchange
+        qkv = att.norm_qk_(linear_native(att._packed, "lin_qkv", att.lin_qkv, h))
         # attention dropout (training mode, reference layers/attention.py:90) across a model group: ONE seed -- rank 0's draw,
         # broadcast -- and the GLOBAL head index in the mask's hash, so the ranks together drop exactly what the unsharded
         # attention drops with that seed (every rank sees the whole sequence of its heads in the unsharded row order)
@@ -1208,7 +1257,7 @@ class TransformerProcessorBlock(BaseBlock):
 
         from .. import _lib
 
-        if self.cond_dim is not None:
+        if self.cond_dim is not None or self.attention.qk_norm:  # (the C entry point knows neither: op by op)
             return None
         dtype, att = x.dtype, self.attention
         c, rows = x.shape[1], x.shape[0]

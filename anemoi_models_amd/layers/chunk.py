@@ -36,9 +36,11 @@ class BaseProcessorChunk(nn.Module, ABC):
 class TransformerProcessorChunk(BaseProcessorChunk):
     def __init__(self, num_channels: int, num_layers: int, window_size: int, num_heads: int = 16,
                  mlp_hidden_ratio: int = 4, activation: str = "GELU", dropout_p: float = 0.0,
-                 cond_dim: Optional[int] = None) -> None:
+                 cond_dim: Optional[int] = None, qk_norm: bool = False) -> None:
         super().__init__(num_channels=num_channels, num_layers=num_layers)
         kw = {} if cond_dim is None else {"cond_dim": cond_dim}
+        if qk_norm:
+            kw["qk_norm"] = True
         self.build_blocks(
             TransformerProcessorBlock, num_channels=num_channels, hidden_dim=mlp_hidden_ratio * num_channels,
             num_heads=num_heads, activation=activation, window_size=window_size, dropout_p=dropout_p, **kw,
@@ -88,11 +90,12 @@ class GNNProcessorChunk(BaseProcessorChunk):
 
 class GraphTransformerProcessorChunk(BaseProcessorChunk):
     def __init__(self, num_channels: int, num_layers: int, num_heads: int = 16, mlp_hidden_ratio: int = 4,
-                 activation: str = "GELU", edge_dim: Optional[int] = None) -> None:
+                 activation: str = "GELU", edge_dim: Optional[int] = None, qk_norm: bool = False) -> None:
         super().__init__(num_channels=num_channels, num_layers=num_layers)
         self.build_blocks(
             GraphTransformerProcessorBlock, in_channels=num_channels, hidden_dim=mlp_hidden_ratio * num_channels,
             out_channels=num_channels, num_heads=num_heads, edge_dim=edge_dim, activation=activation,
+            **({"qk_norm": True} if qk_norm else {}),
         )
 
     def native(self, x: Tensor, edge_attr_csr: Tensor, plan: EdgePlan, halo=None) -> Tensor:

@@ -143,14 +143,16 @@ class GraphTransformerBaseMapper(GraphEdgeMixin, BaseMapper):
         sub_graph_edge_attributes: Optional[list] = None,
         src_grid_size: int = 0,
         dst_grid_size: int = 0,
+        qk_norm: bool = False,
     ) -> None:
         super().__init__(in_channels_src, in_channels_dst, hidden_dim, out_channels_dst=out_channels_dst,
                          num_chunks=num_chunks, cpu_offload=cpu_offload, activation=activation)
+        self.qk_norm = qk_norm
         self._register_edges(sub_graph, sub_graph_edge_attributes, src_grid_size, dst_grid_size, trainable_size)
         self.trainable = TrainableTensor(trainable_size=trainable_size, tensor_size=self.edge_attr.shape[0])
         self.proc = GraphTransformerMapperBlock(
             hidden_dim, mlp_hidden_ratio * hidden_dim, hidden_dim, num_heads=num_heads, edge_dim=self.edge_dim,
-            activation=activation, num_chunks=num_chunks,
+            activation=activation, num_chunks=num_chunks, **({"qk_norm": True} if qk_norm else {}),
         )
         self.offload_layers(cpu_offload)
         self.emb_nodes_dst = nn.Linear(self.in_channels_dst, self.hidden_dim)
@@ -242,6 +244,9 @@ class GraphTransformerBaseMapper(GraphEdgeMixin, BaseMapper):
                      one_cols=(None, None)) -> Tensor:
         """Node-partitioned run (``distributed/partition.py``): local source / destination rows and a local CSR plan
         whose ``perm`` holds original edge ids; halo source rows (decoder) arrive by all-to-all-v inside the block."""
+        if self.qk_norm:
+            raise NotImplementedError("qk_norm: node-partitioned GraphTransformer blocks need the folded edge kernel, which "
+                                      "has no qk_norm")
         plan = local_graph.plan
         ea = runtime.edge_attr_csr_cached(self._packed, self.edge_attr, self.trainable.trainable, plan,
                                           *self.proc.edge_layout(x_dst.dtype))
@@ -301,12 +306,12 @@ class GraphTransformerForwardMapper(ForwardMapperPreProcessMixin, GraphTransform
                  trainable_size: int = 8, out_channels_dst: Optional[int] = None, num_chunks: int = 1,
                  cpu_offload: bool = False, activation: str = "GELU", num_heads: int = 16, mlp_hidden_ratio: int = 4,
                  sub_graph=None, sub_graph_edge_attributes: Optional[list] = None, src_grid_size: int = 0,
-                 dst_grid_size: int = 0) -> None:
+                 dst_grid_size: int = 0, qk_norm: bool = False) -> None:
         super().__init__(in_channels_src, in_channels_dst, hidden_dim, trainable_size,
                          out_channels_dst=out_channels_dst, num_chunks=num_chunks, cpu_offload=cpu_offload,
                          activation=activation, num_heads=num_heads, mlp_hidden_ratio=mlp_hidden_ratio,
                          sub_graph=sub_graph, sub_graph_edge_attributes=sub_graph_edge_attributes,
-                         src_grid_size=src_grid_size, dst_grid_size=dst_grid_size)
+                         src_grid_size=src_grid_size, dst_grid_size=dst_grid_size, qk_norm=qk_norm)
         self.emb_nodes_src = nn.Linear(self.in_channels_src, self.hidden_dim)
 
     def _embed(self, x_src: Tensor, x_dst: Tensor, one_cols=(None, None), num_chunks: int = 1, halo: bool = False,
@@ -333,12 +338,12 @@ class GraphTransformerBackwardMapper(BackwardMapperPostProcessMixin, GraphTransf
                  trainable_size: int = 8, out_channels_dst: Optional[int] = None, num_chunks: int = 1,
                  cpu_offload: bool = False, activation: str = "GELU", num_heads: int = 16, mlp_hidden_ratio: int = 4,
                  sub_graph=None, sub_graph_edge_attributes: Optional[list] = None, src_grid_size: int = 0,
-                 dst_grid_size: int = 0) -> None:
+                 dst_grid_size: int = 0, qk_norm: bool = False) -> None:
         super().__init__(in_channels_src, in_channels_dst, hidden_dim, trainable_size,
                          out_channels_dst=out_channels_dst, num_chunks=num_chunks, cpu_offload=cpu_offload,
                          activation=activation, num_heads=num_heads, mlp_hidden_ratio=mlp_hidden_ratio,
                          sub_graph=sub_graph, sub_graph_edge_attributes=sub_graph_edge_attributes,
-                         src_grid_size=src_grid_size, dst_grid_size=dst_grid_size)
+                         src_grid_size=src_grid_size, dst_grid_size=dst_grid_size, qk_norm=qk_norm)
         self.node_data_extractor = nn.Sequential(nn.LayerNorm(self.hidden_dim),
                                                  nn.Linear(self.hidden_dim, self.out_channels_dst))
         self.proc.mx_node_mlp = False  # MXFP8 on the grid rows' MLP costs the most accuracy (profiles/r07_mxfp8.md)

@@ -66,11 +66,15 @@ class BaseProcessor(nn.Module, ABC):
 class TransformerProcessor(BaseProcessor):
     def __init__(self, num_layers: int, *args, window_size: Optional[int] = None, num_channels: int = 128,
                  num_chunks: int = 2, activation: str = "GELU", cpu_offload: bool = False, num_heads: int = 16,
-                 mlp_hidden_ratio: int = 4, dropout_p: float = 0.1, cond_dim: Optional[int] = None, **kwargs) -> None:
+                 mlp_hidden_ratio: int = 4, dropout_p: float = 0.1, cond_dim: Optional[int] = None, qk_norm: bool = False,
+                 **kwargs) -> None:
         super().__init__(num_channels=num_channels, num_layers=num_layers, num_chunks=num_chunks,
                          activation=activation, cpu_offload=cpu_offload)
         self.cond_dim = cond_dim
+        self.qk_norm = qk_norm
         kw = {} if cond_dim is None else {"cond_dim": cond_dim}
+        if qk_norm:
+            kw["qk_norm"] = True
         self.build_layers(
             TransformerProcessorChunk, num_channels=num_channels, mlp_hidden_ratio=mlp_hidden_ratio,
             num_heads=num_heads, num_layers=self.chunk_size, window_size=window_size, activation=activation,
@@ -312,14 +316,16 @@ class GraphTransformerProcessor(GraphEdgeMixin, BaseProcessor):
     def __init__(self, num_layers: int, trainable_size: int = 8, num_channels: int = 128, num_chunks: int = 2,
                  num_heads: int = 16, mlp_hidden_ratio: int = 4, activation: str = "GELU", cpu_offload: bool = False,
                  sub_graph=None, sub_graph_edge_attributes: Optional[list] = None, src_grid_size: int = 0,
-                 dst_grid_size: int = 0, **kwargs) -> None:
+                 dst_grid_size: int = 0, qk_norm: bool = False, **kwargs) -> None:
         super().__init__(num_layers=num_layers, num_channels=num_channels, num_chunks=num_chunks,
                          activation=activation, cpu_offload=cpu_offload)
+        self.qk_norm = qk_norm
         self._register_edges(sub_graph, sub_graph_edge_attributes, src_grid_size, dst_grid_size, trainable_size)
         self.trainable = TrainableTensor(trainable_size=trainable_size, tensor_size=self.edge_attr.shape[0])
         self.build_layers(
             GraphTransformerProcessorChunk, num_channels=num_channels, num_layers=self.chunk_size,
             num_heads=num_heads, mlp_hidden_ratio=mlp_hidden_ratio, activation=activation, edge_dim=self.edge_dim,
+            **({"qk_norm": True} if qk_norm else {}),
         )
         self.offload_layers(cpu_offload)
         self._plans = runtime.PlanCache()
@@ -370,6 +376,9 @@ class GraphTransformerProcessor(GraphEdgeMixin, BaseProcessor):
 
     def native_local(self, x_own: Tensor, local_graph) -> Tensor:
         """Node-partitioned run (``distributed/partition.py``): this rank's mesh rows in, same rows out."""
+        if self.qk_norm:
+            raise NotImplementedError("qk_norm: node-partitioned GraphTransformer blocks need the folded edge kernel, which "
+                                      "has no qk_norm")
         plan = local_graph.plan
         ea = runtime.edge_attr_csr_cached(self._packed, self.edge_attr, self.trainable.trainable, plan,
                                           *self.proc[0].blocks[0].edge_layout(x_own.dtype))

@@ -1935,6 +1935,69 @@ def gaussian_noise(rows: int, k: int, std: float = 1.0, *, seed: int, seed_dev: 
     return out
 
 
+def _head_norm_args(who: str, x: Tensor, weight: Tensor, num_heads: int, groups: int):
+    """``(rows, width, head size, f32 [groups, D] weight)`` of a ``[rows, groups * H * D]`` view and its norm weights."""
+    rows, width = _rows(x).shape
+    if groups < 1 or num_heads < 1 or width % (groups * num_heads) != 0 or width == 0:
+        raise ValueError(f"{who}: {width} columns do not split into {groups} group(s) of {num_heads} heads")
+    d = width // (groups * num_heads)
+    if weight.numel() != groups * d or weight.shape[-1] != d:
+        raise ValueError(f"{who}: weight {tuple(weight.shape)} does not fit [groups = {groups}, D = {d}]")
+    if d > _lib.HEAD_NORM_MAX_D:
+        raise NotImplementedError(f"{who}: head size {d}, at most {_lib.HEAD_NORM_MAX_D}")
+    return rows, width, d, weight.detach().float().contiguous()
+
+
+def head_norm(x: Tensor, weight: Tensor, num_heads: int, groups: int = 1, eps: float = 1e-5, out: Optional[Tensor] = None,
+              with_stats: bool = False):
+    """``qk_norm``: the bias-free LayerNorm over every head of ``x [rows, groups * H * D]`` (a row-major view, e.g. the ``q | k``
+    columns of a ``q | k | v`` product: ``groups = 2``), scaled by ``weight [groups, D]`` (f32; ``[D]`` for one group).  Statistics
+    in f32, the result in ``x``'s dtype.  ``out=x`` normalises in place (no copy of the product's output); any other ``out`` is
+    a view of the same shape and dtype that does not overlap ``x``.  ``with_stats``: also the f32 ``[rows, groups * H, 2]``
+    statistics ``(rstd, -mean * rstd)`` for :func:`head_norm_backward`."""
+    _dev(x, weight, out)
+    rows, width, d, w = _head_norm_args("head_norm", x, weight, num_heads, groups)
+    if out is None:
+        out = torch.empty((rows, width), dtype=x.dtype, device=x.device)
+    elif tuple(_rows(out).shape) != (rows, width) or out.dtype != x.dtype:
+        raise ValueError("head_norm: out must have x's shape and dtype")
+    stats = torch.empty((rows, groups * num_heads, 2), dtype=torch.float32, device=x.device) if with_stats else None
+    if rows > 0:
+        with _Timed("head_norm", bytes=2 * rows * width * x.element_size()):
+            st = _lib.load().anemoi_head_norm(dtype_code(x.dtype), x.data_ptr(), _ld(x), w.data_ptr(), out.data_ptr(), _ld(out),
+                                              _ptr(stats), rows, groups, num_heads, d, eps, _stream())
+        _lib.check(st, "anemoi_head_norm")
+    return (out, stats) if with_stats else out
+
+
+def head_norm_backward(dy: Tensor, x: Tensor, stats: Tensor, weight: Tensor, num_heads: int, groups: int = 1,
+                       out: Optional[Tensor] = None):
+    """``(dx, dweight [groups, D] f32)`` of :func:`head_norm` from the pre-norm ``x`` and the forward's statistics (``dy``, ``x``
+    and the optional ``out`` for ``dx`` are ``[rows, groups * H * D]`` views).  Deterministic: fixed row chunks, partials added
+    in ascending order; a zero weight is legal (nothing divides by it)."""
+    _dev(dy, x, stats, weight, out)
+    rows, width, d, w = _head_norm_args("head_norm_backward", x, weight, num_heads, groups)
+    if (tuple(_rows(dy).shape) != (rows, width) or dy.dtype != x.dtype
+            or tuple(stats.shape) != (rows, groups * num_heads, 2) or stats.dtype != torch.float32 or not stats.is_contiguous()):
+        raise ValueError("head_norm_backward: shapes of x, dy, stats do not match")
+    if out is None:
+        out = torch.empty((rows, width), dtype=x.dtype, device=x.device)
+    elif tuple(_rows(out).shape) != (rows, width) or out.dtype != x.dtype:
+        raise ValueError("head_norm_backward: out must have x's shape and dtype")
+    dw = torch.empty((groups, d), dtype=torch.float32, device=x.device)
+    if rows == 0:
+        return out, dw.zero_()
+    lib = _lib.load()
+    n_ws = lib.anemoi_head_norm_backward_workspace_floats(rows, groups, num_heads, d)
+    ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=x.device)
+    with _Timed("head_norm_backward", bytes=5 * rows * width * x.element_size()):
+        st = lib.anemoi_head_norm_backward(dtype_code(x.dtype), dy.data_ptr(), _ld(dy), x.data_ptr(), _ld(x), stats.data_ptr(),
+                                           w.data_ptr(), out.data_ptr(), _ld(out), dw.data_ptr(), rows, groups, num_heads, d,
+                                           ws.data_ptr(), n_ws, _stream())
+    _lib.check(st, "anemoi_head_norm_backward")
+    return out, dw
+
+
 def weight_grad(dpre: Tensor, x: Tensor, k: int, want_bias: bool = False, transposed_route: bool = False,
                 out: Optional[Tensor] = None):
     """``dW [N, k] = dpre^T @ x[:, :k]`` in f32 (``dpre [M, N]``, ``x [M, >= k]`` in the compute dtype): the reduction

@@ -410,7 +410,7 @@ def transformer_block(block, x: Tensor, batch_size: int, cond: Optional[Tensor] 
     att = block.attention
     x = _cast(x, dtype)
     h = _block_norm(block.layer_norm1, x, cond)
-    qkv = autograd.linear(h, att.lin_qkv.weight, att.lin_qkv.bias)
+    qkv = att.norm_qk(autograd.linear(h, att.lin_qkv.weight, att.lin_qkv.bias))
     p, seed, seed_dev = att.dropout()  # attention dropout in training mode (reference layers/attention.py:90)
     a = autograd.mhsa(qkv, batch_size, att.num_heads, att.attention_window(), p, seed, seed_dev=seed_dev)
     x = autograd.linear(a, att.projection.weight, att.projection.bias, "Identity", x)

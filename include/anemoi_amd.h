@@ -744,6 +744,34 @@ int anemoi_cond_layer_norm_backward(int dtype, const void* dy, int64_t ldd, cons
 int anemoi_gaussian_noise(float* out, int64_t rows, int K, float std, uint32_t seed, const void* seed_dev,
                           anemoi_stream_t stream);
 
+/*
+ * qk_norm: the bias-free LayerNorm over the head dimension of queries and keys, between the q|k|v product and the attention
+ * kernel.  x, y: [rows, groups * H * D] views in `dtype` (f32 or bf16) with leading dimensions ldx, ldy; w: f32 [groups, D]
+ * (q | k adjacent in one matrix: groups = 2 and the weights of q_norm and k_norm stacked; a single q or k: groups = 1):
+ *   y[r, (g H + h) D + d] = (x - mean) * rstd * w[g, d],  mean and the biased variance over the D elements of the head, in f32,
+ *   rstd = 1 / sqrt(var + eps); the result is rounded once, to `dtype`.
+ * y == x is the in-place form (inference: no copy of the product's output); otherwise x and y must not overlap.  `stats` (may be
+ * NULL): f32 [rows, groups * H, 2] = { rstd, -mean * rstd }, the convention of anemoi_layer_norm_stats.  One read and one write
+ * of the addressed columns, no other column of a row is touched.  16-byte accesses when x, y, ldx, ldy and D * sizeof(elem) are
+ * multiples of 16 bytes, element accesses otherwise.  1 <= D <= 128 (D < 1: ANEMOI_ERR_INVALID; D > 128:
+ * ANEMOI_ERR_UNSUPPORTED).
+ */
+int anemoi_head_norm(int dtype, const void* x, int64_t ldx, const float* w, void* y, int64_t ldy, float* stats, int64_t rows,
+                     int groups, int H, int D, float eps, anemoi_stream_t stream);
+
+/*
+ * Its backward from the pre-norm x and the forward's statistics.  With g = dy * w and xhat = x * rstd + (-mean * rstd):
+ *   dx = rstd * (g - mean_d(g) - xhat * mean_d(g * xhat))       dw[g, d] = sum_{r, h} dy * xhat       (no division by w)
+ * dy, x, dx: [rows, groups * H * D] views in `dtype` (ldd, ldx, ldo); dw: f32 [groups, D] contiguous.  Deterministic, no atomics:
+ * the column sums are taken over fixed chunks of rows (a function of `rows` alone), one [groups * H * D] partial per chunk in
+ * `workspace` (anemoi_head_norm_backward_workspace_floats(rows, groups, H, D) floats), added in ascending chunk order, then
+ * the heads of a group in ascending order.
+ */
+int64_t anemoi_head_norm_backward_workspace_floats(int64_t rows, int groups, int H, int D);
+int anemoi_head_norm_backward(int dtype, const void* dy, int64_t ldd, const void* x, int64_t ldx, const float* stats,
+                              const float* w, void* dx, int64_t ldo, float* dw, int64_t rows, int groups, int H, int D,
+                              float* workspace, int64_t workspace_floats, anemoi_stream_t stream);
+
 /* dtype conversion / K-padding copy: dst[r, 0:cols] = src[r, 0:cols], dst[r, cols:ld_dst] = 0. */
 int anemoi_convert_pad(int src_dtype, const void* src, int64_t ld_src, int dst_dtype, void* dst, int64_t ld_dst,
                        int64_t rows, int cols, anemoi_stream_t stream);
