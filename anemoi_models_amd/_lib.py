@@ -108,6 +108,57 @@ def linear_route(entry: str, **fields):
     return load().anemoi_linear_route(ctypes.byref(args), ctypes.byref(route)), route
 
 
+MHSA_ENTRIES = {"forward": 0, "backward": 1}  # ANEMOI_MHSA_ENTRY_*
+MHSA_KERNEL_GENERIC, MHSA_KERNEL_W8, MHSA_KERNEL_W4, MHSA_KERNEL_BWD_MFMA = 0, 1, 2, 3
+MHSA_KERNEL_NAMES = {MHSA_KERNEL_GENERIC: "generic", MHSA_KERNEL_W8: "w8", MHSA_KERNEL_W4: "w4", MHSA_KERNEL_BWD_MFMA: "mfma"}
+
+
+class MhsaArgs(ctypes.Structure):
+    """``anemoi_mhsa_args`` of include/anemoi_amd.h (``anemoi_mhsa_route``), field for field."""
+
+    _fields_ = [
+        ("struct_bytes", c_int64),
+        ("entry", ctypes.c_int32), ("dtype", ctypes.c_int32),
+        ("qkv", c_void_p), ("out", c_void_p), ("lse", c_void_p), ("dout", c_void_p), ("delta", c_void_p),
+        ("dqkv", c_void_p), ("workspace", c_void_p), ("dropout_seed_dev", c_void_p),
+        ("ld", c_int64), ("ldo", c_int64), ("lddo", c_int64), ("lddq", c_int64),
+        ("B", ctypes.c_int32), ("S", ctypes.c_int32), ("H", ctypes.c_int32), ("D", ctypes.c_int32),
+        ("window", ctypes.c_int32), ("dropout_p", c_float), ("dropout_seed", c_uint32),
+        ("dropout_h0", ctypes.c_int32), ("dropout_h_total", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ]
+
+
+class MhsaLayout(ctypes.Structure):
+    """``anemoi_mhsa_workspace_layout``: byte offsets into the workspace, and its size."""
+
+    _fields_ = [(name, c_int64) for name in ("vt", "tail", "flag", "qt", "kt", "dot", "lse2p", "deltap", "total")]
+
+
+class MhsaRoute(ctypes.Structure):
+    """``anemoi_mhsa_route_info``: what self attention does with a call (the library's own plan)."""
+
+    _fields_ = [
+        ("struct_bytes", c_int64),
+        ("kernel", ctypes.c_int32), ("drop", ctypes.c_int32), ("win", ctypes.c_int32), ("dmax", ctypes.c_int32),
+        ("S_pad", ctypes.c_int32), ("tail_rows", ctypes.c_int32), ("tail_splits", ctypes.c_int32),
+        ("tail_chunk", ctypes.c_int32),
+        ("grid", c_uint32 * 3), ("reserved", ctypes.c_int32),
+        ("layout", MhsaLayout),
+    ]
+
+
+def mhsa_route(entry: str, **fields):
+    """``(status, MhsaRoute)`` of ``anemoi_mhsa_route`` for the arguments ``fields`` of ``anemoi_mhsa`` (``entry`` "forward") or
+    ``anemoi_mhsa_backward`` ("backward"): pointers as integers, whatever is left out is 0 / NULL.  Launches nothing and needs
+    no GPU: for tests and diagnostics."""
+    args, route = MhsaArgs(), MhsaRoute()
+    args.struct_bytes, route.struct_bytes = ctypes.sizeof(MhsaArgs), ctypes.sizeof(MhsaRoute)
+    args.entry = MHSA_ENTRIES[entry]
+    for name, value in fields.items():
+        setattr(args, name, value)
+    return load().anemoi_mhsa_route(ctypes.byref(args), ctypes.byref(route)), route
+
+
 class LinearThinArgs(ctypes.Structure):
     """``anemoi_linear_thin_args`` of include/anemoi_amd.h (``anemoi_linear_thin``), field for field."""
 
@@ -319,6 +370,7 @@ SIGNATURES = {
     "anemoi_mhsa_backward": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                      c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_uint32,
                                      c_void_p, c_int, c_int, c_void_p]),
+    "anemoi_mhsa_route": (c_int, [ctypes.POINTER(MhsaArgs), ctypes.POINTER(MhsaRoute)]),
     "anemoi_assemble_nodes": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_int,
                                       c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "anemoi_finalize_output": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p,

@@ -1738,247 +1738,367 @@ __global__ __launch_bounds__(256) void mhsa_bwd_dkv_kernel(const T* __restrict__
 
 using namespace anemoi;
 
-extern "C" {
+// ---------------------------------------------------------------------------------------------
+// Host side.  Both entry points gather their arguments in an MhsaArgs, validate them (mhsa_validate), plan the call
+// (mhsa_plan: route, template arguments, launch geometry, workspace layout) and execute the plan (mhsa_run).
+// anemoi_mhsa_route stops after the plan: what it reports is what a call does.
+// ---------------------------------------------------------------------------------------------
+using MhsaArgs = anemoi_mhsa_args;
+using MhsaPlan = anemoi_mhsa_route_info;
+using MhsaLayout = anemoi_mhsa_workspace_layout;
 
-static inline int64_t mhsa_vt_bytes(int B, int S, int H, int D) {
-  return ((int64_t)B * H * D * ((S + 63) / 64 * 64) * 2 + 255) / 256 * 256;
+static const char* const MHSA_ENTRY[2] = {"anemoi_mhsa", "anemoi_mhsa_backward"};
+
+static MhsaArgs mhsa_args(int entry, int dtype, const void* qkv, int64_t ld, void* out, int64_t ldo, float* lse,
+                          void* workspace, int B, int S, int H, int D, int window, float dropout_p, uint32_t dropout_seed,
+                          const void* dropout_seed_dev, int dropout_h0, int dropout_h_total) {
+  MhsaArgs a = {};
+  a.struct_bytes = (int64_t)sizeof(MhsaArgs);
+  a.entry = entry; a.dtype = dtype;
+  a.qkv = qkv; a.out = out; a.lse = lse; a.workspace = workspace; a.dropout_seed_dev = dropout_seed_dev;
+  a.ld = ld; a.ldo = ldo;
+  a.B = B; a.S = S; a.H = H; a.D = D; a.window = window;
+  a.dropout_p = dropout_p; a.dropout_seed = dropout_seed; a.dropout_h0 = dropout_h0; a.dropout_h_total = dropout_h_total;
+  return a;
+}
+
+static inline AttnDropout mhsa_dropout(const MhsaArgs& a) {
+  return make_dropout(a.dropout_p, a.dropout_seed, a.dropout_h0, a.dropout_h_total > 0 ? a.dropout_h_total : a.H,
+                      a.dropout_seed_dev);
+}
+
+// ---- workspace: the only place that adds up mhsa_vt_bytes / mhsa_tail_bytes
+static inline int mhsa_s_pad(int S) { return (S + 63) / 64 * 64; }
+
+static inline int64_t mhsa_vt_bytes(int B, int S, int H, int D) {  // one transposed operand [B, H, D, S_pad] bf16
+  return ((int64_t)B * H * D * mhsa_s_pad(S) * 2 + 255) / 256 * 256;
 }
 
 static inline int64_t mhsa_tail_bytes(int B, int S, int H, int D) {
   return ((int64_t)B * mhsa_tail_rows(S) * H * mhsa_tail_splits(B, S, H) * (D + 2) * 4 + 255) / 256 * 256;
 }
 
-int64_t anemoi_mhsa_workspace_bytes(int dtype, int B, int S, int H, int D) {
-  if (dtype == ANEMOI_BF16 && (D == 64 || D == 32))  // V^T, then the partial states of the left-over rows' key chunks
-    return mhsa_vt_bytes(B, S, H, D) + mhsa_tail_bytes(B, S, H, D) + 256;  // + the fallback flag of the 4-wave kernel
-  return 0;
+static inline bool mhsa_mfma_shape(int dtype, int D) { return dtype == ANEMOI_BF16 && (D == 64 || D == 32); }
+
+// forward: V^T, then the partial states of the left-over rows' key chunks, then the fallback flag of the 4-wave kernel
+static MhsaLayout mhsa_forward_layout(int B, int S, int H, int D) {
+  MhsaLayout l = {};
+  l.tail = l.vt + mhsa_vt_bytes(B, S, H, D);
+  l.flag = l.tail + mhsa_tail_bytes(B, S, H, D);
+  l.total = l.flag + 256;
+  return l;
 }
 
-int anemoi_mhsa(int dtype, const void* qkv, int64_t ld, void* out, int64_t ldo, void* workspace, float* lse, int B, int S,
-                int H, int D, int window, float dropout_p, uint32_t dropout_seed, const void* dropout_seed_dev,
-                int dropout_h0, int dropout_h_total, anemoi_stream_t stream) {
-  ANEMOI_REQUIRE(qkv && out, ANEMOI_ERR_INVALID, "anemoi_mhsa: null pointer");
-  ANEMOI_REQUIRE(B > 0 && S > 0 && H > 0 && D > 0, ANEMOI_ERR_INVALID, "anemoi_mhsa: bad shape");
-  const int C = H * D;
-  ANEMOI_REQUIRE(ld >= 3 * (int64_t)C && ldo >= C, ANEMOI_ERR_INVALID, "anemoi_mhsa: leading dimension too small");
-  hipStream_t st = as_stream(stream);
-  const float scale = 1.0f / sqrtf((float)D);
-  const int64_t units_all = (int64_t)B * S * H;  // entries of lse
-  ANEMOI_REQUIRE(dropout_p >= 0.f && dropout_p <= 1.f, ANEMOI_ERR_INVALID, "anemoi_mhsa: dropout_p %g outside [0, 1]",
-                 (double)dropout_p);
-  ANEMOI_REQUIRE(dropout_h0 >= 0 && (dropout_h_total == 0 || dropout_h0 + H <= dropout_h_total), ANEMOI_ERR_INVALID,
-                 "anemoi_mhsa: heads %d .. %d of %d", dropout_h0, dropout_h0 + H, dropout_h_total);
-  ANEMOI_REQUIRE(dropout_seed_dev == nullptr || (uintptr_t)dropout_seed_dev % 4 == 0, ANEMOI_ERR_INVALID,
-                 "anemoi_mhsa: dropout_seed_dev must be 4-byte aligned");
-  const AttnDropout dr = make_dropout(dropout_p, dropout_seed, dropout_h0, dropout_h_total > 0 ? dropout_h_total : H,
-                                      dropout_seed_dev);
-  // MFMA route, with or without dropout (the mask is applied to the packed probabilities; the kernels hash 32-bit row
-  // indices: B x heads x S < 2^32, and p = 1 -- everything dropped -- stays on the generic kernel)
-  const bool drop = dr.thr15 != 0;
-  if (!dr.drop_all && (int64_t)B * dr.h_total * S < ((int64_t)1 << 32) && dtype == ANEMOI_BF16 && (D == 64 || D == 32) &&
-      (uintptr_t)qkv % 16 == 0 && ld % 8 == 0 && (uintptr_t)out % 8 == 0 && ldo % 4 == 0) {
-    ANEMOI_REQUIRE(workspace != nullptr, ANEMOI_ERR_INVALID, "anemoi_mhsa: workspace of %lld bytes required",
-                   (long long)anemoi_mhsa_workspace_bytes(dtype, B, S, H, D));
-    const int S_pad = (S + 63) / 64 * 64;
-    hipLaunchKernelGGL(transpose_v_kernel, dim3(S_pad / 64, H, B), dim3(256), 0, st,
-                       static_cast<const bf16_t*>(qkv), ld, S, S_pad, H, D, C, static_cast<bf16_t*>(workspace));
-    // the few queries behind the last whole 512-query block: key-split kernels above (not a workgroup of their own)
-    const int rem = mhsa_tail_rows(S);
-    const int s_main = S - rem;
-    if (rem > 0) {
-      const int n_split = mhsa_tail_splits(B, S, H);
-      const int chunk = (S + n_split - 1) / n_split;
-      const int64_t n_units = (int64_t)B * rem * H, total = n_units * n_split;
-      float* part = reinterpret_cast<float*>(static_cast<char*>(workspace) + mhsa_vt_bytes(B, S, H, D));
-      const dim3 tgrid((unsigned)((total + 3) / 4)), tblock(256);
-      if (D == 64) {
-        hipLaunchKernelGGL(mhsa_tail_kernel<64>, tgrid, tblock, 0, st, static_cast<const bf16_t*>(qkv), ld, S, H, C, window,
-                           scale, s_main, rem, n_split, chunk, total, part, dr);
-        hipLaunchKernelGGL(mhsa_tail_merge_kernel<64>, dim3((unsigned)((n_units + 3) / 4)), dim3(256), 0, st, part,
-                           static_cast<bf16_t*>(out), ldo, lse, S, H, s_main, rem, n_split, n_units);
-      } else {
-        hipLaunchKernelGGL(mhsa_tail_kernel<32>, tgrid, tblock, 0, st, static_cast<const bf16_t*>(qkv), ld, S, H, C, window,
-                           scale, s_main, rem, n_split, chunk, total, part, dr);
-        hipLaunchKernelGGL(mhsa_tail_merge_kernel<32>, dim3((unsigned)((n_units + 3) / 4)), dim3(256), 0, st, part,
-                           static_cast<bf16_t*>(out), ldo, lse, S, H, s_main, rem, n_split, n_units);
-      }
-    }
-    const dim3 grid((s_main + ATT_QBLK - 1) / ATT_QBLK, H, B), block(64 * ATT_WAVES);
-#define ANEMOI_MHSA_FWD(DD, DR)                                                                                      \
-  hipLaunchKernelGGL((mhsa_bf16_kernel<DD, DR>), grid, block, 0, st, static_cast<const bf16_t*>(qkv), ld,            \
-                     static_cast<const bf16_t*>(workspace), static_cast<bf16_t*>(out), ldo, S, S_pad, H, C, window, \
-                     scale * 1.44269504088896340736f, lse, dr)
+// backward: Q^T, K^T, dO^T + the padded log-sum-exp (log2 units) and delta rows [B, H, S_pad] the dK/dV kernel's LDS-DMA reads
+static MhsaLayout mhsa_backward_layout(int B, int S, int H, int D) {
+  const int64_t vt = mhsa_vt_bytes(B, S, H, D), rows = (int64_t)B * H * mhsa_s_pad(S) * 4;
+  MhsaLayout l = {};
+  l.kt = l.qt + vt;
+  l.dot = l.kt + vt;
+  l.lse2p = l.dot + vt;
+  l.deltap = l.lse2p + rows;
+  l.total = l.deltap + rows;
+  return l;
+}
+
+extern "C" int64_t anemoi_mhsa_workspace_bytes(int dtype, int B, int S, int H, int D) {
+  return mhsa_mfma_shape(dtype, D) ? mhsa_forward_layout(B, S, H, D).total : 0;
+}
+
+extern "C" int64_t anemoi_mhsa_backward_workspace_bytes(int dtype, int B, int S, int H, int D) {
+  return mhsa_mfma_shape(dtype, D) ? mhsa_backward_layout(B, S, H, D).total : 0;
+}
+
+// ---- route
+// MFMA route, with or without dropout (the mask is applied to the packed probabilities; the kernels hash 32-bit row
+// indices: B x heads x S < 2^32, and p = 1 -- everything dropped -- stays on the generic kernel).  The alignment terms keep
+// the kernels' vector accesses to the rows of qkv, dout, out and dqkv aligned; the backward kernels index B x S, ld and lddo
+// in 32 bits.
+// Backward only: a call whose workspace is null or not 16-byte aligned is NOT refused -- it takes the VALU kernels, like
+// every other call this predicate turns down (ops.mhsa_backward(use_mfma=False) asks for them this way).  The forward
+// refuses an MFMA call without a workspace (mhsa_validate).
+static bool mhsa_takes_mfma(const MhsaArgs& a) {
+  const AttnDropout dr = mhsa_dropout(a);
+  if (dr.drop_all || (int64_t)a.B * dr.h_total * a.S >= ((int64_t)1 << 32) || !mhsa_mfma_shape(a.dtype, a.D)) return false;
+  if (a.entry == ANEMOI_MHSA_ENTRY_FORWARD)
+    return (uintptr_t)a.qkv % 16 == 0 && a.ld % 8 == 0 && (uintptr_t)a.out % 8 == 0 && a.ldo % 4 == 0;
+  const int64_t lim = (int64_t)1 << 31;
+  return a.workspace != nullptr && (int64_t)a.B * a.S < lim && a.ld < lim && a.lddo < lim &&
+         (uintptr_t)a.workspace % 16 == 0 && (uintptr_t)a.qkv % 16 == 0 && (uintptr_t)a.dout % 16 == 0 &&
+         (uintptr_t)a.out % 2 == 0 && (uintptr_t)a.dqkv % 8 == 0 && a.ld % 8 == 0 && a.lddo % 8 == 0 && a.lddq % 4 == 0;
+}
+
+// The checks of both entry points, each written once.  A call with several faults is refused for the one that comes first
+// here.  D <= 128 and the grid bound belong to the VALU kernels: the backward tests them before it chooses a route (so also
+// for calls the MFMA kernels take, which D <= 128 never stops), the forward only off the MFMA route.
+static int mhsa_validate(const MhsaArgs& a) {
+  const char* who = MHSA_ENTRY[a.entry];
+  const bool bwd = a.entry == ANEMOI_MHSA_ENTRY_BACKWARD;
+  ANEMOI_REQUIRE(a.qkv && a.out && (!bwd || (a.dout && a.lse && a.delta && a.dqkv)), ANEMOI_ERR_INVALID, "%s: null pointer", who);
+  ANEMOI_REQUIRE(a.B > 0 && a.S > 0 && a.H > 0 && a.D > 0, ANEMOI_ERR_INVALID, "%s: bad shape", who);
+  const int C = a.H * a.D;
+  ANEMOI_REQUIRE(a.ld >= 3 * (int64_t)C && a.ldo >= C && (!bwd || (a.lddq >= 3 * (int64_t)C && a.lddo >= C)), ANEMOI_ERR_INVALID,
+                 "%s: leading dimension too small", who);
+  const auto head_size = [&]() -> int {
+    ANEMOI_REQUIRE(a.D <= 128, ANEMOI_ERR_UNSUPPORTED, "%s: head size %d > 128", who, a.D);
+    return ANEMOI_OK;
+  };
+  const auto grid = [&]() -> int {
+    ANEMOI_REQUIRE(((int64_t)a.B * a.S * a.H + 3) / 4 < ((int64_t)1 << 31), ANEMOI_ERR_UNSUPPORTED, "%s: grid too large", who);
+    return ANEMOI_OK;
+  };
+  int rc = bwd ? head_size() : ANEMOI_OK;
+  if (rc != ANEMOI_OK) return rc;
+  ANEMOI_REQUIRE(a.dropout_p >= 0.f && a.dropout_p <= 1.f, ANEMOI_ERR_INVALID, "%s: dropout_p %g outside [0, 1]", who,
+                 (double)a.dropout_p);
+  ANEMOI_REQUIRE(a.dropout_h0 >= 0 && (a.dropout_h_total == 0 || a.dropout_h0 + a.H <= a.dropout_h_total), ANEMOI_ERR_INVALID,
+                 "%s: heads %d .. %d of %d", who, a.dropout_h0, a.dropout_h0 + a.H, a.dropout_h_total);
+  ANEMOI_REQUIRE(a.dropout_seed_dev == nullptr || (uintptr_t)a.dropout_seed_dev % 4 == 0, ANEMOI_ERR_INVALID,
+                 "%s: dropout_seed_dev must be 4-byte aligned", who);
+  if (bwd) return grid();
+  if (mhsa_takes_mfma(a)) {
+    ANEMOI_REQUIRE(a.workspace != nullptr, ANEMOI_ERR_INVALID, "%s: workspace of %lld bytes required", who,
+                   (long long)mhsa_forward_layout(a.B, a.S, a.H, a.D).total);
+    return ANEMOI_OK;
+  }
+  rc = head_size();
+  return rc != ANEMOI_OK ? rc : grid();
+}
+
+// What a validated call does.  The only refusal left is a dtype the VALU kernels do not have.
+static int mhsa_plan(const MhsaArgs& a, MhsaPlan& p) {
+  p = MhsaPlan{};
+  p.struct_bytes = (int64_t)sizeof(MhsaPlan);
+  const AttnDropout dr = mhsa_dropout(a);
+  p.drop = dr.thr15 != 0 && !dr.drop_all;
+  if (!mhsa_takes_mfma(a)) {
+    ANEMOI_REQUIRE(a.dtype == ANEMOI_F32 || a.dtype == ANEMOI_BF16, ANEMOI_ERR_UNSUPPORTED, "%s: dtype %d", MHSA_ENTRY[a.entry],
+                   a.dtype);
+    p.kernel = ANEMOI_MHSA_KERNEL_GENERIC;
+    p.dmax = a.D <= 32 ? 32 : a.D <= 64 ? 64 : 128;
+    p.grid[0] = (unsigned)(((int64_t)a.B * a.S * a.H + 3) / 4);  // a wave per (batch element, row, head)
+    p.grid[1] = p.grid[2] = 1;
+    return ANEMOI_OK;
+  }
+  p.S_pad = mhsa_s_pad(a.S);
+  p.grid[1] = (unsigned)a.H;
+  p.grid[2] = (unsigned)a.B;
+  if (a.entry == ANEMOI_MHSA_ENTRY_FORWARD) {
+    // the few queries behind the last whole 512-query block: key-split kernels (not a workgroup of their own)
+    p.tail_rows = mhsa_tail_rows(a.S);
+    p.tail_splits = mhsa_tail_splits(a.B, a.S, a.H);
+    p.tail_chunk = p.tail_rows > 0 ? (a.S + p.tail_splits - 1) / p.tail_splits : 0;
     // D = 64, global attention: the 4-wave software-pipelined kernel; its fallback (a probability left the f32 range under
     // the fixed reference maximum) is the 8-wave kernel behind a device-side flag -- no host round trip, graph capturable
-    if (D == 64 && window < 0 && (int64_t)S * ld * 2 < ((int64_t)1 << 31)) {
-      int* flag = reinterpret_cast<int*>(static_cast<char*>(workspace) + mhsa_vt_bytes(B, S, H, D) + mhsa_tail_bytes(B, S, H, D));
-      if (hipMemsetAsync(flag, 0, 4, st) != hipSuccess) return fail(ANEMOI_ERR_LAUNCH, "anemoi_mhsa: flag reset");
-      const dim3 block4(64 * W4_WAVES);
-      if (drop)
-        hipLaunchKernelGGL((mhsa_bf16_w4_kernel<true>), grid, block4, 0, st, static_cast<const bf16_t*>(qkv), ld,
-                           static_cast<const bf16_t*>(workspace), static_cast<bf16_t*>(out), ldo, S, S_pad, H, C,
-                           scale * 1.44269504088896340736f, lse, dr, flag);
-      else
-        hipLaunchKernelGGL((mhsa_bf16_w4_kernel<false>), grid, block4, 0, st, static_cast<const bf16_t*>(qkv), ld,
-                           static_cast<const bf16_t*>(workspace), static_cast<bf16_t*>(out), ldo, S, S_pad, H, C,
-                           scale * 1.44269504088896340736f, lse, dr, flag);
-      if (drop)
-        hipLaunchKernelGGL((mhsa_bf16_kernel<64, true>), grid, block, 0, st, static_cast<const bf16_t*>(qkv), ld,
-                           static_cast<const bf16_t*>(workspace), static_cast<bf16_t*>(out), ldo, S, S_pad, H, C, window,
-                           scale * 1.44269504088896340736f, lse, dr, flag);
-      else
-        hipLaunchKernelGGL((mhsa_bf16_kernel<64, false>), grid, block, 0, st, static_cast<const bf16_t*>(qkv), ld,
-                           static_cast<const bf16_t*>(workspace), static_cast<bf16_t*>(out), ldo, S, S_pad, H, C, window,
-                           scale * 1.44269504088896340736f, lse, dr, flag);
-    } else if (D == 64) {
-      if (drop) ANEMOI_MHSA_FWD(64, true);
-      else ANEMOI_MHSA_FWD(64, false);
-    } else {
-      if (drop) ANEMOI_MHSA_FWD(32, true);
-      else ANEMOI_MHSA_FWD(32, false);
-    }
-#undef ANEMOI_MHSA_FWD
-    {
-      int rc = trail::note(check_launch("anemoi_mhsa(bf16, MFMA)"), "anemoi_mhsa", "out", dtype, out, ldo, (int64_t)B * S, C, st);
-      if (lse != nullptr) rc = trail::note(rc, "anemoi_mhsa", "lse", ANEMOI_F32, lse, units_all, 1, units_all, st);
-      return rc;
-    }
-  }
-  ANEMOI_REQUIRE(D <= 128, ANEMOI_ERR_UNSUPPORTED, "anemoi_mhsa: head size %d > 128", D);
-  const int64_t units = (int64_t)B * S * H;
-  ANEMOI_REQUIRE((units + 3) / 4 < ((int64_t)1 << 31), ANEMOI_ERR_UNSUPPORTED, "anemoi_mhsa: grid too large");
-  dim3 grid((unsigned)((units + 3) / 4)), block(256);
-#define GEN(T, DM)                                                                                               \
-  hipLaunchKernelGGL((mhsa_generic_kernel<T, DM>), grid, block, 0, st, static_cast<const T*>(qkv), ld,           \
-                     static_cast<T*>(out), ldo, S, H, D, C, window, scale, units, lse, dr, 0, S)
-  if (dtype == ANEMOI_F32) {
-    if (D <= 32) GEN(float, 32);
-    else if (D <= 64) GEN(float, 64);
-    else GEN(float, 128);
-  } else if (dtype == ANEMOI_BF16) {
-    if (D <= 32) GEN(bf16_t, 32);
-    else if (D <= 64) GEN(bf16_t, 64);
-    else GEN(bf16_t, 128);
+    const bool w4 = a.D == 64 && a.window < 0 && (int64_t)a.S * a.ld * 2 < ((int64_t)1 << 31);
+    p.kernel = w4 ? ANEMOI_MHSA_KERNEL_W4 : ANEMOI_MHSA_KERNEL_W8;
+    p.grid[0] = (unsigned)((a.S - p.tail_rows + ATT_QBLK - 1) / ATT_QBLK);
+    p.layout = mhsa_forward_layout(a.B, a.S, a.H, a.D);
   } else {
-    return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_mhsa: dtype %d", dtype);
+    p.kernel = ANEMOI_MHSA_KERNEL_BWD_MFMA;
+    p.win = a.window >= 0;
+    p.grid[0] = (unsigned)((a.S + 32 * ATT_BWD_NW - 1) / (32 * ATT_BWD_NW));
+    p.layout = mhsa_backward_layout(a.B, a.S, a.H, a.D);
   }
-#undef GEN
-  {
-    int rc = trail::note(check_launch("anemoi_mhsa(generic)"), "anemoi_mhsa", "out", dtype, out, ldo, (int64_t)B * S, C, st);
-    if (lse != nullptr) rc = trail::note(rc, "anemoi_mhsa", "lse", ANEMOI_F32, lse, units_all, 1, units_all, st);
+  return ANEMOI_OK;
+}
+
+extern "C" int anemoi_mhsa_route(const anemoi_mhsa_args* args, anemoi_mhsa_route_info* route) {
+  ANEMOI_REQUIRE(args != nullptr && route != nullptr, ANEMOI_ERR_INVALID, "anemoi_mhsa_route: null argument");
+  ANEMOI_REQUIRE(args->struct_bytes == (int64_t)sizeof(MhsaArgs) && route->struct_bytes == (int64_t)sizeof(MhsaPlan),
+                 ANEMOI_ERR_INVALID,
+                 "anemoi_mhsa_route: argument blocks out of sync with the library (%lld / %lld bytes, expected %lld / %lld)",
+                 (long long)args->struct_bytes, (long long)route->struct_bytes, (long long)sizeof(MhsaArgs), (long long)sizeof(MhsaPlan));
+  ANEMOI_REQUIRE(args->entry == ANEMOI_MHSA_ENTRY_FORWARD || args->entry == ANEMOI_MHSA_ENTRY_BACKWARD, ANEMOI_ERR_INVALID,
+                 "anemoi_mhsa_route: entry %d", args->entry);
+  const int rc = mhsa_validate(*args);
+  return rc != ANEMOI_OK ? rc : mhsa_plan(*args, *route);
+}
+
+// ---- launch: a plan's run-time choices become template arguments here
+template <typename F>
+static void mhsa_on_bool(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}
+template <typename F>
+static void mhsa_on_head_size(int D, F&& f) {  // the MFMA kernels' ATT_D
+  if (D == 64) f(std::integral_constant<int, 64>{});
+  else f(std::integral_constant<int, 32>{});
+}
+template <typename F>
+static void mhsa_on_dmax(int dmax, F&& f) {  // the VALU kernels' DMAX
+  if (dmax == 32) f(std::integral_constant<int, 32>{});
+  else if (dmax == 64) f(std::integral_constant<int, 64>{});
+  else f(std::integral_constant<int, 128>{});
+}
+
+template <typename T>
+static T* mhsa_at(void* workspace, int64_t offset) {
+  return reinterpret_cast<T*>(static_cast<char*>(workspace) + offset);
+}
+
+static int mhsa_forward_mfma(const MhsaArgs& a, const MhsaPlan& p, const AttnDropout& dr, float scale, hipStream_t st) {
+  const int C = a.H * a.D, S = a.S, S_pad = p.S_pad, H = a.H, window = a.window;
+  const bf16_t* qkv = static_cast<const bf16_t*>(a.qkv);
+  bf16_t* out = static_cast<bf16_t*>(a.out);
+  float* lse = a.lse;
+  const int64_t ld = a.ld, ldo = a.ldo;
+  bf16_t* vt = mhsa_at<bf16_t>(a.workspace, p.layout.vt);
+  hipLaunchKernelGGL(transpose_v_kernel, dim3(S_pad / 64, H, a.B), dim3(256), 0, st, qkv, ld, S, S_pad, H, a.D, C, vt);
+  const int rem = p.tail_rows, s_main = S - rem;
+  if (rem > 0) {
+    const int n_split = p.tail_splits, chunk = p.tail_chunk;
+    const int64_t n_units = (int64_t)a.B * rem * H, total = n_units * n_split;
+    float* part = mhsa_at<float>(a.workspace, p.layout.tail);
+    mhsa_on_head_size(a.D, [&](auto d) {
+      hipLaunchKernelGGL(mhsa_tail_kernel<decltype(d)::value>, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, st, qkv, ld, S,
+                         H, C, window, scale, s_main, rem, n_split, chunk, total, part, dr);
+      hipLaunchKernelGGL(mhsa_tail_merge_kernel<decltype(d)::value>, dim3((unsigned)((n_units + 3) / 4)), dim3(256), 0, st,
+                         part, out, ldo, lse, S, H, s_main, rem, n_split, n_units);
+    });
+  }
+  const dim3 grid(p.grid[0], p.grid[1], p.grid[2]);
+  const float scale_log2e = scale * 1.44269504088896340736f;
+  int* flag = nullptr;  // w8 alone runs unconditionally
+  if (p.kernel == ANEMOI_MHSA_KERNEL_W4) {
+    flag = mhsa_at<int>(a.workspace, p.layout.flag);
+    if (hipMemsetAsync(flag, 0, 4, st) != hipSuccess) return fail(ANEMOI_ERR_LAUNCH, "anemoi_mhsa: flag reset");
+    mhsa_on_bool(p.drop != 0, [&](auto drop) {
+      hipLaunchKernelGGL(mhsa_bf16_w4_kernel<decltype(drop)::value>, grid, dim3(64 * W4_WAVES), 0, st, qkv, ld, vt, out, ldo, S,
+                         S_pad, H, C, scale_log2e, lse, dr, flag);
+    });
+  }
+  mhsa_on_head_size(a.D, [&](auto d) {
+    mhsa_on_bool(p.drop != 0, [&](auto drop) {
+      hipLaunchKernelGGL((mhsa_bf16_kernel<decltype(d)::value, decltype(drop)::value>), grid, dim3(64 * ATT_WAVES), 0, st, qkv,
+                         ld, vt, out, ldo, S, S_pad, H, C, window, scale_log2e, lse, dr, flag);
+    });
+  });
+  return ANEMOI_OK;
+}
+
+template <typename T>
+static void mhsa_forward_generic(const MhsaArgs& a, const MhsaPlan& p, const AttnDropout& dr, float scale, hipStream_t st) {
+  const int64_t units = (int64_t)a.B * a.S * a.H;
+  mhsa_on_dmax(p.dmax, [&](auto dm) {
+    hipLaunchKernelGGL((mhsa_generic_kernel<T, decltype(dm)::value>), dim3(p.grid[0]), dim3(256), 0, st,
+                       static_cast<const T*>(a.qkv), a.ld, static_cast<T*>(a.out), a.ldo, a.S, a.H, a.D, a.H * a.D, a.window,
+                       scale, units, a.lse, dr, 0, a.S);
+  });
+}
+
+// MFMA backward: delta, the three transposed operands, then the two kernels
+static void mhsa_backward_mfma(const MhsaArgs& a, const MhsaPlan& p, const AttnDropout& dr, float scale, hipStream_t st) {
+  const int C = a.H * a.D, S = a.S, S_pad = p.S_pad, H = a.H, window = a.window;
+  const int64_t units = (int64_t)a.B * S * H, ld = a.ld, lddo = a.lddo, lddq = a.lddq;
+  const bf16_t* qkvb = static_cast<const bf16_t*>(a.qkv);
+  const bf16_t* dob = static_cast<const bf16_t*>(a.dout);
+  bf16_t* dqkv = static_cast<bf16_t*>(a.dqkv);
+  bf16_t* qT = mhsa_at<bf16_t>(a.workspace, p.layout.qt);
+  bf16_t* kT = mhsa_at<bf16_t>(a.workspace, p.layout.kt);
+  bf16_t* doT = mhsa_at<bf16_t>(a.workspace, p.layout.dot);
+  float* lse2p = mhsa_at<float>(a.workspace, p.layout.lse2p);
+  float* deltap = mhsa_at<float>(a.workspace, p.layout.deltap);
+  const float* lse = a.lse;
+  float* delta = a.delta;
+  hipLaunchKernelGGL(mhsa_delta_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, st,
+                     static_cast<const bf16_t*>(a.out), a.ldo, dob, lddo, delta, lse, lse2p, deltap, S, S_pad, H, a.D, units);
+  const dim3 tgrid(S_pad / 64, H, a.B), tblock(256);
+  hipLaunchKernelGGL(transpose_v_kernel, tgrid, tblock, 0, st, qkvb, ld, S, S_pad, H, a.D, C, qT, 0);
+  hipLaunchKernelGGL(transpose_v_kernel, tgrid, tblock, 0, st, qkvb, ld, S, S_pad, H, a.D, C, kT, C);
+  hipLaunchKernelGGL(transpose_v_kernel, tgrid, tblock, 0, st, dob, lddo, S, S_pad, H, a.D, C, doT, 0);
+  const dim3 grid(p.grid[0], p.grid[1], p.grid[2]), block(64 * ATT_BWD_NW);
+  const float sl2 = scale * 1.44269504088896340736f;
+  mhsa_on_head_size(a.D, [&](auto d) {
+    mhsa_on_bool(p.drop != 0, [&](auto drop) {
+      mhsa_on_bool(p.win != 0, [&](auto win) {
+        constexpr int DD = decltype(d)::value;
+        constexpr bool DR = decltype(drop)::value, WN = decltype(win)::value;
+        hipLaunchKernelGGL((mhsa_bwd_dkv_mfma_kernel<DD, DR, WN>), grid, block, 0, st, qkvb, ld, dob, lddo, qT, doT, lse2p,
+                           deltap, dqkv, lddq, S, S_pad, H, C, window, scale, sl2, dr);
+        hipLaunchKernelGGL((mhsa_bwd_dq_mfma_kernel<DD, DR, WN>), grid, block, 0, st, qkvb, ld, dob, lddo, kT, lse, delta,
+                           dqkv, lddq, S, S_pad, H, C, window, scale, sl2, dr);
+      });
+    });
+  });
+}
+
+template <typename T>
+static void mhsa_backward_generic(const MhsaArgs& a, const MhsaPlan& p, const AttnDropout& dr, float scale, hipStream_t st) {
+  const int C = a.H * a.D;
+  const int64_t units = (int64_t)a.B * a.S * a.H;
+  const dim3 grid(p.grid[0]), block(256);
+  mhsa_on_dmax(p.dmax, [&](auto dm) {
+    constexpr int DM = decltype(dm)::value;
+    hipLaunchKernelGGL((mhsa_bwd_dq_kernel<T, DM>), grid, block, 0, st, static_cast<const T*>(a.qkv), a.ld,
+                       static_cast<const T*>(a.out), a.ldo, static_cast<const T*>(a.dout), a.lddo, a.lse, a.delta,
+                       static_cast<T*>(a.dqkv), a.lddq, a.S, a.H, a.D, C, a.window, scale, units, dr);
+    hipLaunchKernelGGL((mhsa_bwd_dkv_kernel<T, DM>), grid, block, 0, st, static_cast<const T*>(a.qkv), a.ld,
+                       static_cast<const T*>(a.dout), a.lddo, a.lse, static_cast<const float*>(a.delta),
+                       static_cast<T*>(a.dqkv), a.lddq, a.S, a.H, a.D, C, a.window, scale, units, dr);
+  });
+}
+
+// Executes a plan: the launches of its route, one launch check, the trail records of the outputs.
+static int mhsa_run(const MhsaArgs& a, const MhsaPlan& p, hipStream_t st) {
+  static const char* const LABEL[2][2] = {{"anemoi_mhsa(generic)", "anemoi_mhsa(bf16, MFMA)"},
+                                          {"anemoi_mhsa_backward", "anemoi_mhsa_backward(bf16, MFMA)"}};
+  const char* who = MHSA_ENTRY[a.entry];
+  const bool mfma = p.kernel != ANEMOI_MHSA_KERNEL_GENERIC;
+  const AttnDropout dr = mhsa_dropout(a);
+  const float scale = 1.0f / sqrtf((float)a.D);
+  const int C = a.H * a.D;
+  const int64_t rows = (int64_t)a.B * a.S, units = rows * a.H;  // units: entries of lse and delta
+  if (a.entry == ANEMOI_MHSA_ENTRY_FORWARD) {
+    if (mfma) {
+      const int rc = mhsa_forward_mfma(a, p, dr, scale, st);
+      if (rc != ANEMOI_OK) return rc;
+    } else if (a.dtype == ANEMOI_F32) {
+      mhsa_forward_generic<float>(a, p, dr, scale, st);
+    } else {
+      mhsa_forward_generic<bf16_t>(a, p, dr, scale, st);
+    }
+    int rc = trail::note(check_launch(LABEL[0][mfma]), who, "out", a.dtype, a.out, a.ldo, rows, C, st);
+    if (a.lse != nullptr) rc = trail::note(rc, who, "lse", ANEMOI_F32, a.lse, units, 1, units, st);
     return rc;
   }
+  if (mfma) mhsa_backward_mfma(a, p, dr, scale, st);
+  else if (a.dtype == ANEMOI_F32) mhsa_backward_generic<float>(a, p, dr, scale, st);
+  else mhsa_backward_generic<bf16_t>(a, p, dr, scale, st);
+  const int rc = trail::note(check_launch(LABEL[1][mfma]), who, "dqkv", a.dtype, a.dqkv, a.lddq, rows, 3 * (int64_t)C, st);
+  return trail::note(rc, who, "delta", ANEMOI_F32, a.delta, units, 1, units, st);
+}
+
+extern "C" int anemoi_mhsa(int dtype, const void* qkv, int64_t ld, void* out, int64_t ldo, void* workspace, float* lse, int B,
+                           int S, int H, int D, int window, float dropout_p, uint32_t dropout_seed,
+                           const void* dropout_seed_dev, int dropout_h0, int dropout_h_total, anemoi_stream_t stream) {
+  const MhsaArgs a = mhsa_args(ANEMOI_MHSA_ENTRY_FORWARD, dtype, qkv, ld, out, ldo, lse, workspace, B, S, H, D, window,
+                               dropout_p, dropout_seed, dropout_seed_dev, dropout_h0, dropout_h_total);
+  MhsaPlan p;
+  int rc = mhsa_validate(a);
+  if (rc == ANEMOI_OK) rc = mhsa_plan(a, p);
+  return rc != ANEMOI_OK ? rc : mhsa_run(a, p, as_stream(stream));
 }
 
 #ifdef ATT_BWD_PROF
-int anemoi_debug_att_prof(unsigned long long* out) {
+extern "C" int anemoi_debug_att_prof(unsigned long long* out) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(att_prof), sizeof(att_prof));
 }
 #endif
 
-int64_t anemoi_mhsa_backward_workspace_bytes(int dtype, int B, int S, int H, int D) {
-  // Q^T, K^T, dO^T + the padded log-sum-exp (log2 units) and delta rows [B, H, S_pad] the dK/dV kernel's LDS-DMA reads
-  if (dtype == ANEMOI_BF16 && (D == 64 || D == 32))
-    return 3 * mhsa_vt_bytes(B, S, H, D) + 2 * (int64_t)B * H * ((S + 63) / 64 * 64) * 4;
-  return 0;
+extern "C" int anemoi_mhsa_backward(int dtype, const void* qkv, int64_t ld, const void* out, int64_t ldo, const void* dout,
+                                    int64_t lddo, const float* lse, float* delta, void* dqkv, int64_t lddq, void* workspace,
+                                    int B, int S, int H, int D, int window, float dropout_p, uint32_t dropout_seed,
+                                    const void* dropout_seed_dev, int dropout_h0, int dropout_h_total,
+                                    anemoi_stream_t stream) {
+  // (out and lse are inputs here: the block's fields are the forward's, which writes them)
+  MhsaArgs a = mhsa_args(ANEMOI_MHSA_ENTRY_BACKWARD, dtype, qkv, ld, const_cast<void*>(out), ldo, const_cast<float*>(lse),
+                         workspace, B, S, H, D, window, dropout_p, dropout_seed, dropout_seed_dev, dropout_h0, dropout_h_total);
+  a.dout = dout; a.lddo = lddo; a.delta = delta; a.dqkv = dqkv; a.lddq = lddq;
+  MhsaPlan p;
+  int rc = mhsa_validate(a);
+  if (rc == ANEMOI_OK) rc = mhsa_plan(a, p);
+  return rc != ANEMOI_OK ? rc : mhsa_run(a, p, as_stream(stream));
 }
 
-int anemoi_mhsa_backward(int dtype, const void* qkv, int64_t ld, const void* out, int64_t ldo, const void* dout,
-                         int64_t lddo, const float* lse, float* delta, void* dqkv, int64_t lddq, void* workspace, int B,
-                         int S, int H, int D, int window, float dropout_p, uint32_t dropout_seed,
-                         const void* dropout_seed_dev, int dropout_h0, int dropout_h_total, anemoi_stream_t stream) {
-  ANEMOI_REQUIRE(qkv && out && dout && lse && delta && dqkv, ANEMOI_ERR_INVALID, "anemoi_mhsa_backward: null pointer");
-  ANEMOI_REQUIRE(B > 0 && S > 0 && H > 0 && D > 0, ANEMOI_ERR_INVALID, "anemoi_mhsa_backward: bad shape");
-  const int C = H * D;
-  ANEMOI_REQUIRE(ld >= 3 * (int64_t)C && lddq >= 3 * (int64_t)C && ldo >= C && lddo >= C, ANEMOI_ERR_INVALID,
-                 "anemoi_mhsa_backward: leading dimension too small");
-  ANEMOI_REQUIRE(D <= 128, ANEMOI_ERR_UNSUPPORTED, "anemoi_mhsa_backward: head size %d > 128", D);
-  ANEMOI_REQUIRE(dropout_p >= 0.f && dropout_p <= 1.f, ANEMOI_ERR_INVALID, "anemoi_mhsa_backward: dropout_p %g outside [0, 1]",
-                 (double)dropout_p);
-  ANEMOI_REQUIRE(dropout_h0 >= 0 && (dropout_h_total == 0 || dropout_h0 + H <= dropout_h_total), ANEMOI_ERR_INVALID,
-                 "anemoi_mhsa_backward: heads %d .. %d of %d", dropout_h0, dropout_h0 + H, dropout_h_total);
-  ANEMOI_REQUIRE(dropout_seed_dev == nullptr || (uintptr_t)dropout_seed_dev % 4 == 0, ANEMOI_ERR_INVALID,
-                 "anemoi_mhsa: dropout_seed_dev must be 4-byte aligned");
-  const AttnDropout dr = make_dropout(dropout_p, dropout_seed, dropout_h0, dropout_h_total > 0 ? dropout_h_total : H,
-                                      dropout_seed_dev);
-  const bool drop = dr.thr15 != 0;
-  hipStream_t st = as_stream(stream);
-  const float scale = 1.0f / sqrtf((float)D);
-  const int64_t units = (int64_t)B * S * H;
-  ANEMOI_REQUIRE((units + 3) / 4 < ((int64_t)1 << 31), ANEMOI_ERR_UNSUPPORTED, "anemoi_mhsa_backward: grid too large");
-  if (!dr.drop_all && (int64_t)B * dr.h_total * S < ((int64_t)1 << 32) && dtype == ANEMOI_BF16 && (D == 64 || D == 32) &&
-      workspace != nullptr && (int64_t)B * S < ((int64_t)1 << 31) && ld < ((int64_t)1 << 31) && lddo < ((int64_t)1 << 31) &&
-      (uintptr_t)workspace % 16 == 0 && (uintptr_t)qkv % 16 == 0 && (uintptr_t)dout % 16 == 0 && (uintptr_t)out % 2 == 0 &&
-      (uintptr_t)dqkv % 8 == 0 && ld % 8 == 0 && lddo % 8 == 0 && lddq % 4 == 0) {
-    // MFMA route: delta, the three transposed operands, then the two kernels
-    const int S_pad = (S + 63) / 64 * 64;
-    const bf16_t* qkvb = static_cast<const bf16_t*>(qkv);
-    const bf16_t* dob = static_cast<const bf16_t*>(dout);
-    bf16_t* qT = static_cast<bf16_t*>(workspace);
-    bf16_t* kT = reinterpret_cast<bf16_t*>(static_cast<char*>(workspace) + mhsa_vt_bytes(B, S, H, D));
-    bf16_t* doT = reinterpret_cast<bf16_t*>(static_cast<char*>(workspace) + 2 * mhsa_vt_bytes(B, S, H, D));
-    float* lse2p = reinterpret_cast<float*>(static_cast<char*>(workspace) + 3 * mhsa_vt_bytes(B, S, H, D));
-    float* deltap = lse2p + (int64_t)B * H * S_pad;
-    hipLaunchKernelGGL(mhsa_delta_kernel, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, st,
-                       static_cast<const bf16_t*>(out), ldo, dob, lddo, delta, lse, lse2p, deltap, S, S_pad, H, D, units);
-    const dim3 tgrid(S_pad / 64, H, B), tblock(256);
-    hipLaunchKernelGGL(transpose_v_kernel, tgrid, tblock, 0, st, qkvb, ld, S, S_pad, H, D, C, qT, 0);
-    hipLaunchKernelGGL(transpose_v_kernel, tgrid, tblock, 0, st, qkvb, ld, S, S_pad, H, D, C, kT, C);
-    hipLaunchKernelGGL(transpose_v_kernel, tgrid, tblock, 0, st, dob, lddo, S, S_pad, H, D, C, doT, 0);
-    const dim3 grid128((S + 32 * ATT_BWD_NW - 1) / (32 * ATT_BWD_NW), H, B), block256(64 * ATT_BWD_NW);
-    const float sl2 = scale * 1.44269504088896340736f;
-#define ANEMOI_MHSA_BWD_(DD, DR, WN)                                                                                     \
-  do {                                                                                                                  \
-    hipLaunchKernelGGL((mhsa_bwd_dkv_mfma_kernel<DD, DR, WN>), grid128, block256, 0, st, qkvb, ld, dob, lddo, qT, doT,  \
-                       lse2p, deltap, static_cast<bf16_t*>(dqkv), lddq, S, S_pad, H, C, window, scale, sl2, dr);       \
-    hipLaunchKernelGGL((mhsa_bwd_dq_mfma_kernel<DD, DR, WN>), grid128, block256, 0, st, qkvb, ld, dob, lddo, kT, lse,   \
-                       delta, static_cast<bf16_t*>(dqkv), lddq, S, S_pad, H, C, window, scale, sl2, dr);                \
-  } while (0)
-#define ANEMOI_MHSA_BWD(DD, DR)                       \
-  do {                                                \
-    if (window >= 0) ANEMOI_MHSA_BWD_(DD, DR, true);  \
-    else ANEMOI_MHSA_BWD_(DD, DR, false);             \
-  } while (0)
-    if (D == 64) {
-      if (drop) ANEMOI_MHSA_BWD(64, true);
-      else ANEMOI_MHSA_BWD(64, false);
-    } else {
-      if (drop) ANEMOI_MHSA_BWD(32, true);
-      else ANEMOI_MHSA_BWD(32, false);
-    }
-#undef ANEMOI_MHSA_BWD_
-#undef ANEMOI_MHSA_BWD
-    {
-      int rc = trail::note(check_launch("anemoi_mhsa_backward(bf16, MFMA)"), "anemoi_mhsa_backward", "dqkv", dtype, dqkv, lddq, (int64_t)B * S, 3 * (int64_t)C, st);
-      return trail::note(rc, "anemoi_mhsa_backward", "delta", ANEMOI_F32, delta, units, 1, units, st);
-    }
-  }
-  dim3 grid((unsigned)((units + 3) / 4)), block(256);
-#define BWD(T, DM)                                                                                                    \
-  do {                                                                                                                \
-    hipLaunchKernelGGL((mhsa_bwd_dq_kernel<T, DM>), grid, block, 0, st, static_cast<const T*>(qkv), ld,               \
-                       static_cast<const T*>(out), ldo, static_cast<const T*>(dout), lddo, lse, delta,                \
-                       static_cast<T*>(dqkv), lddq, S, H, D, C, window, scale, units, dr);                            \
-    hipLaunchKernelGGL((mhsa_bwd_dkv_kernel<T, DM>), grid, block, 0, st, static_cast<const T*>(qkv), ld,              \
-                       static_cast<const T*>(dout), lddo, lse, static_cast<const float*>(delta), static_cast<T*>(dqkv), \
-                       lddq, S, H, D, C, window, scale, units, dr);                                                   \
-  } while (0)
-  if (dtype == ANEMOI_F32) {
-    if (D <= 32) BWD(float, 32);
-    else if (D <= 64) BWD(float, 64);
-    else BWD(float, 128);
-  } else if (dtype == ANEMOI_BF16) {
-    if (D <= 32) BWD(bf16_t, 32);
-    else if (D <= 64) BWD(bf16_t, 64);
-    else BWD(bf16_t, 128);
-  } else {
-    return fail(ANEMOI_ERR_UNSUPPORTED, "anemoi_mhsa_backward: dtype %d", dtype);
-  }
-#undef BWD
-  {
-    int rc = trail::note(check_launch("anemoi_mhsa_backward"), "anemoi_mhsa_backward", "dqkv", dtype, dqkv, lddq, (int64_t)B * S, 3 * (int64_t)C, st);
-    return trail::note(rc, "anemoi_mhsa_backward", "delta", ANEMOI_F32, delta, units, 1, units, st);
-  }
-}
-
-}  // extern "C"

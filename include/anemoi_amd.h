@@ -822,6 +822,13 @@ int anemoi_segment_sum_cat(int dtype, const void* v, int64_t ldv, const int32_t*
  * `dropout_seed` when it starts -- the part of the seed a captured HIP graph can advance between replays (kernel arguments
  * are frozen at capture; anemoi_models_amd/runtime.py::DeviceDropout).  The backward must be given the same word, holding
  * the value the forward saw.
+ * Route.  The MFMA kernels take a call with dtype bf16, D = 64 or 32, dropout_p < 1, B x heads x S < 2^32 (heads =
+ * dropout_h_total, or H where that is 0), `qkv` 16-byte and `out` 8-byte aligned, ld a multiple of 8 and ldo a multiple of
+ * 4 elements; such a call without a workspace is refused (ANEMOI_ERR_INVALID).  D = 64 with window < 0 and
+ * S x ld x 2 < 2^31 bytes runs the four-wave kernel (the eight-wave one behind its device-side fallback flag), every other
+ * MFMA call the eight-wave kernel; the 1 .. 16 rows behind the last whole 512-row block of an S > 512 go to the key-split
+ * tail kernels.  Every other call takes the VALU kernel: D <= 128, B x S x H / 4 < 2^31 workgroups
+ * (ANEMOI_ERR_UNSUPPORTED beyond either).  anemoi_mhsa_route (below) answers which of these a call takes.
  */
 int64_t anemoi_mhsa_workspace_bytes(int dtype, int B, int S, int H, int D);
 int anemoi_mhsa(int dtype, const void* qkv, int64_t ld, void* out, int64_t ldo, void* workspace, float* lse, int B, int S,
@@ -837,12 +844,74 @@ int anemoi_mhsa(int dtype, const void* qkv, int64_t ld, void* out, int64_t ldo, 
  * and dropout_p < 1: MFMA kernels (one pass with the keys stationary for dK / dV, one with the queries stationary for dQ)
  * on a `workspace` of anemoi_mhsa_backward_workspace_bytes() bytes (Q^T, K^T, dO^T and the padded lse / delta rows the
  * dK / dV kernel streams); otherwise VALU kernels, O(S^2 D) on the vector pipe (workspace may be NULL).
+ * Route.  D <= 128 and B x S x H / 4 < 2^31 hold for every call (ANEMOI_ERR_UNSUPPORTED otherwise).  The MFMA kernels
+ * take a call with dtype bf16, D = 64 or 32, dropout_p < 1, B x heads x S < 2^32, B x S, ld and lddo < 2^31, a non-NULL
+ * 16-byte aligned `workspace`, `qkv` and `dout` 16-byte, `dqkv` 8-byte and `out` 2-byte aligned, ld and lddo multiples of
+ * 8 and lddq a multiple of 4 elements.  A call that misses any of these -- a NULL or misaligned workspace included --
+ * is NOT refused: it runs the VALU kernels, which compute the same gradients and are orders of magnitude slower at
+ * mesh sizes (46 s per layer at S = 40 962).  Withholding the workspace is the supported way to ask for them (the
+ * tests' yardstick); a caller that wants the MFMA kernels asks anemoi_mhsa_route what its call takes.
  */
 int64_t anemoi_mhsa_backward_workspace_bytes(int dtype, int B, int S, int H, int D);
 int anemoi_mhsa_backward(int dtype, const void* qkv, int64_t ld, const void* out, int64_t ldo, const void* dout,
                          int64_t lddo, const float* lse, float* delta, void* dqkv, int64_t lddq, void* workspace, int B,
                          int S, int H, int D, int window, float dropout_p, uint32_t dropout_seed,
                          const void* dropout_seed_dev, int dropout_h0, int dropout_h_total, anemoi_stream_t stream);
+
+/*
+ * Route query of self attention (tests and diagnostics; nothing on the hot path calls it).  anemoi_mhsa and
+ * anemoi_mhsa_backward gather their arguments in an anemoi_mhsa_args, validate them, plan an anemoi_mhsa_route_info and
+ * execute it; anemoi_mhsa_route runs the same validation and the same plan on the same two types, launches nothing,
+ * touches no memory and needs no device, and returns the status the entry point would return before its first launch.
+ * Pointers are looked at for NULL and alignment only.  Fields the forward does not have (dout, delta, dqkv, lddo, lddq)
+ * stay 0 / NULL.  `struct_bytes` of both blocks must be their sizeof (layout check across the FFI).
+ */
+enum { ANEMOI_MHSA_ENTRY_FORWARD = 0, ANEMOI_MHSA_ENTRY_BACKWARD = 1 };
+enum {
+  ANEMOI_MHSA_KERNEL_GENERIC = 0, /* the VALU kernels, forward or backward */
+  ANEMOI_MHSA_KERNEL_W8 = 1,      /* forward: the eight-wave MFMA kernel */
+  ANEMOI_MHSA_KERNEL_W4 = 2,      /* forward: the four-wave MFMA kernel, the eight-wave one behind its flag */
+  ANEMOI_MHSA_KERNEL_BWD_MFMA = 3 /* backward: the dK / dV and dQ MFMA kernels */
+};
+
+typedef struct anemoi_mhsa_args {
+  int64_t struct_bytes;
+  int32_t entry, dtype;
+  const void* qkv;
+  void* out;       /* the forward's result (the backward reads it) */
+  float* lse;      /* forward: optional output; backward: input */
+  const void* dout;
+  float* delta;
+  void* dqkv;
+  void* workspace;
+  const void* dropout_seed_dev;
+  int64_t ld, ldo, lddo, lddq;
+  int32_t B, S, H, D, window;
+  float dropout_p;
+  uint32_t dropout_seed;
+  int32_t dropout_h0, dropout_h_total, reserved;
+} anemoi_mhsa_args;
+
+typedef struct anemoi_mhsa_workspace_layout { /* byte offsets into `workspace`, and its size */
+  int64_t vt, tail, flag;                     /* forward: V^T, the tail rows' partial states, the four-wave kernel's flag */
+  int64_t qt, kt, dot, lse2p, deltap;         /* backward: Q^T, K^T, dO^T, the padded lse (log2 units) and delta rows */
+  int64_t total;                              /* = anemoi_mhsa[_backward]_workspace_bytes() */
+} anemoi_mhsa_workspace_layout;
+
+typedef struct anemoi_mhsa_route_info {
+  int64_t struct_bytes;
+  int32_t kernel;     /* ANEMOI_MHSA_KERNEL_* */
+  int32_t drop;       /* a mask is hashed (0 < dropout_p < 1 after rounding to 15 bits): the MFMA kernels' DROP argument */
+  int32_t win;        /* backward MFMA kernels' WIN argument (window >= 0); 0 elsewhere */
+  int32_t dmax;       /* the VALU kernels' DMAX (32, 64 or 128); 0 on the MFMA routes */
+  int32_t S_pad;      /* MFMA routes: S rounded up to 64, the row length of the transposed operands */
+  int32_t tail_rows, tail_splits, tail_chunk; /* forward MFMA: rows of the key-split tail pair, key chunks, keys per chunk */
+  uint32_t grid[3];   /* workgroups of the main launch (forward kernel; dK / dV and dQ kernels; VALU kernels) */
+  int32_t reserved;
+  anemoi_mhsa_workspace_layout layout; /* MFMA routes; all 0 on the VALU route, which uses no workspace */
+} anemoi_mhsa_route_info;
+
+int anemoi_mhsa_route(const anemoi_mhsa_args* args, anemoi_mhsa_route_info* route);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Backward pass, dense half (first step): the pieces the autograd of the fused Linear and of

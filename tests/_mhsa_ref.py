@@ -1,7 +1,7 @@
 """f64 references, per-element error bounds, data sets, the launcher's route and the case lists for multi-head self
 attention (csrc/attention.hip behind ``ops.mhsa`` / ``ops.mhsa_backward`` / ``autograd.mhsa``).
 
-Pure torch on the CPU; imports nothing from the GPU side.  Used by tests/test_mhsa_ref_cpu.py (validates the references
+Pure torch on the CPU; imports nothing from the GPU side (``assert_same_plan`` alone reads the library's status text).  Used by tests/test_mhsa_ref_cpu.py (validates the references
 against f64 autograd, shows that emulations of the kernels' arithmetic stay inside the bounds and that subtly wrong results do
 not) and by tests/test_gpu_mhsa.py (the kernels).
 
@@ -525,32 +525,58 @@ def _dmax(d: int) -> int:
     return 32 if d <= 32 else 64 if d <= 64 else 128
 
 
+def _generic_grid(b, s, h):
+    return (-(-b * s * h // 4), 1, 1)  # the VALU kernels: a wave per (batch element, row, head), four per workgroup
+
+
 def route(dtype, b, s, h, d, window, ld, ldo, qkv_ptr=0, out_ptr=0, p=0.0, heads_total=0):
     """The forward launcher's choices (anemoi_mhsa) restated: ``kernel`` "w4" / "w8" / "generic", tail rows and splits, DMAX of
-    the generic kernel, the DROP template argument."""
+    the generic kernel, the DROP template argument (``drop``: a mask is hashed, 0 < p < 1 after rounding), the main launch's
+    ``grid`` and the workspace the route uses (``ws_bytes``: none on the generic route)."""
     drop_all, thr = p >= 1.0, threshold15(p)
     ht = heads_total or h
     mfma = (not drop_all and b * ht * s < 2 ** 32 and dtype == BF16 and d in (32, 64) and qkv_ptr % 16 == 0 and ld % 8 == 0
             and out_ptr % 8 == 0 and ldo % 4 == 0)
     if not mfma:
-        return types.SimpleNamespace(kernel="generic", mfma=False, tail=0, n_split=0, chunk=0, dmax=_dmax(d), drop=thr != 0,
-                                     workgroups=0)
+        return types.SimpleNamespace(kernel="generic", mfma=False, tail=0, n_split=0, chunk=0, dmax=_dmax(d),
+                                     drop=thr != 0 and not drop_all, win=False, workgroups=_generic_grid(b, s, h)[0],
+                                     grid=_generic_grid(b, s, h), s_pad=0, ws_bytes=0)
     w4 = d == 64 and window < 0 and s * ld * 2 < 2 ** 31
     rem = tail_rows(s)
+    wg = -(-(s - rem) // ATT_QBLK)
     return types.SimpleNamespace(kernel="w4" if w4 else "w8", mfma=True, tail=rem, n_split=tail_splits(b, s, h),
-                                 chunk=tail_chunk(b, s, h), dmax=0, drop=thr != 0 and not drop_all,
-                                 workgroups=-(-(s - rem) // ATT_QBLK))
+                                 chunk=tail_chunk(b, s, h), dmax=0, drop=thr != 0 and not drop_all, win=False, workgroups=wg,
+                                 grid=(wg, h, b), s_pad=(s + 63) // 64 * 64, ws_bytes=workspace_bytes(dtype, b, s, h, d))
 
 
 def route_backward(dtype, b, s, h, d, window, ld, ldo, lddo, lddq, ptrs=(0, 0, 0, 0), p=0.0, heads_total=0, workspace=True):
-    """anemoi_mhsa_backward: ``kernel`` "mfma" / "generic", the WIN template argument, DMAX.  ``ptrs``: qkv, out, dout, dqkv."""
+    """anemoi_mhsa_backward: ``kernel`` "mfma" / "generic", the WIN template argument, DMAX, the grid of the two main kernels.
+    ``ptrs``: qkv, out, dout, dqkv.  ``workspace``: its address (True: some aligned one; False / 0: none) -- a call without a
+    16-byte aligned workspace takes the VALU kernels, it is not refused."""
     drop_all, thr = p >= 1.0, threshold15(p)
     ht = heads_total or h
-    mfma = (not drop_all and b * ht * s < 2 ** 32 and dtype == BF16 and d in (32, 64) and workspace and b * s < 2 ** 31
+    ws = 16 if workspace is True else int(workspace or 0)
+    mfma = (not drop_all and b * ht * s < 2 ** 32 and dtype == BF16 and d in (32, 64) and ws != 0 and ws % 16 == 0
+            and b * s < 2 ** 31 and ld < 2 ** 31 and lddo < 2 ** 31
             and ptrs[0] % 16 == 0 and ptrs[2] % 16 == 0 and ptrs[1] % 2 == 0 and ptrs[3] % 8 == 0 and ld % 8 == 0
             and lddo % 8 == 0 and lddq % 4 == 0)
     return types.SimpleNamespace(kernel="mfma" if mfma else "generic", mfma=mfma, win=mfma and window >= 0,
-                                 dmax=0 if mfma else _dmax(d), drop=thr != 0 and not drop_all)
+                                 dmax=0 if mfma else _dmax(d), drop=thr != 0 and not drop_all, tail=0, n_split=0, chunk=0,
+                                 grid=(-(-s // 128), h, b) if mfma else _generic_grid(b, s, h),
+                                 s_pad=(s + 63) // 64 * 64 if mfma else 0,
+                                 ws_bytes=backward_workspace_bytes(dtype, b, s, h, d) if mfma else 0)
+
+
+def assert_same_plan(rt, status, lib, what=""):
+    """The library's plan (``_lib.mhsa_route``: status and ``MhsaRoute``) equals the restatement ``rt`` field by field."""
+    from anemoi_models_amd import _lib
+
+    assert status == 0, f"{what}: anemoi_mhsa_route refuses the call ({status}: {_lib.load().anemoi_last_error()})"
+    got = (_lib.MHSA_KERNEL_NAMES[lib.kernel], bool(lib.drop), bool(lib.win), lib.dmax, lib.tail_rows, lib.tail_splits,
+           lib.tail_chunk, tuple(lib.grid), lib.S_pad, lib.layout.total)
+    want = (rt.kernel, bool(rt.drop), bool(rt.win), rt.dmax, rt.tail, rt.n_split, rt.chunk, tuple(rt.grid), rt.s_pad, rt.ws_bytes)
+    assert got == want, f"{what}: the library plans (kernel, drop, win, DMAX, tail rows, splits, chunk, grid, S_pad, workspace) " \
+                        f"= {got}, the restatement {want}"
 
 
 # ------------------------------------------------------------------------------------------------ cases (both test files)

@@ -9,7 +9,8 @@ Kernels: ``mhsa_bf16_w4_kernel`` (D = 64, global), ``mhsa_bf16_kernel`` <64 / 32
 fallback), ``mhsa_tail_kernel`` + ``mhsa_tail_merge_kernel`` (S = 513, 514, 528, 1026), ``mhsa_generic_kernel`` <f32 / bf16, DMAX
 32 / 64 / 128>, ``mhsa_delta_kernel``, ``mhsa_bwd_dkv_mfma_kernel`` / ``mhsa_bwd_dq_mfma_kernel`` <64 / 32, DROP, WIN>,
 ``mhsa_bwd_dq_kernel`` / ``mhsa_bwd_dkv_kernel``, ``transpose_v_kernel``.  Every case restates the launcher's dispatch on its own
-tensors (``_mhsa_ref.route``) and asserts the kernel it reaches, and cross-checks the tail geometry against the library's
+tensors (``_mhsa_ref.route``), asserts the kernel it reaches, and asserts that the library's own plan for the call's pointers
+and pitches (``anemoi_mhsa_route``) equals the restatement: kernel, DROP / WIN, DMAX, tail rows / splits / chunk, workgroups,
 workspace size.  ``qkv``, ``out`` (backward: ``out``, ``dout``) sit in buffers with guard rows before and after and guard columns
 where the pitch is wider than the data: NaN around the inputs, a bit pattern around the output that must be untouched.
 
@@ -120,8 +121,11 @@ def _forward(c, qkv, p=0.0, seed=0, expect=None):
     assert rt.kernel == (expect or c.expect), f"{R.case_id(c)}: the launcher takes {rt.kernel}"
     assert _lib.load().anemoi_mhsa_workspace_bytes(ops.dtype_code(c.dtype), c.b, c.s, c.h, c.d) == \
         R.workspace_bytes(c.dtype, c.b, c.s, c.h, c.d)
-    if rt.mfma:
-        assert (rt.tail, rt.n_split) == (R.tail_rows(c.s), R.tail_splits(c.b, c.s, c.h))
+    # the library's own plan on the pointers and pitches of this call (ops.mhsa brings a workspace wherever one is asked for)
+    st, plan = _lib.mhsa_route("forward", dtype=ops.dtype_code(c.dtype), qkv=gin.view.data_ptr(), ld=gin.ld, out=gout.view.data_ptr(),
+                               ldo=gout.ld, workspace=256, B=c.b, S=c.s, H=c.h, D=c.d, window=c.window, dropout_p=p,
+                               dropout_seed=seed)
+    R.assert_same_plan(rt, st, plan, R.case_id(c))
     out, lse = ops.mhsa(gin.view, c.b, c.h, c.window, out=gout.view, return_lse=True, dropout_p=p, dropout_seed=seed)
     assert out.data_ptr() == gout.view.data_ptr() and lse.shape == (c.b, c.h, c.s) and lse.dtype == F32
     torch.cuda.synchronize()
@@ -172,17 +176,25 @@ def test_head_size_129_is_refused():
 # ------------------------------------------------------------------------------------------------ backward
 def _backward_direct(c, qkv, out_st, dout, lse_st, p=0.0, seed=0):
     """``ops.mhsa_backward`` on guarded operands; asserts the route."""
-    from anemoi_models_amd import ops
+    from anemoi_models_amd import _lib, ops
 
     rows, cc = c.b * c.s, c.h * c.d
     gq = Guarded(rows, 3 * cc, c.dtype, data=qkv.to(DEV))
     go = Guarded(rows, cc, c.dtype, data=out_st.to(DEV))
     gd = Guarded(rows, cc, c.dtype, data=dout.to(DEV))
+    lse_dev = lse_st.to(DEV)
     use_mfma = R.backward_expect(c) == "mfma"
     rt = R.route_backward(c.dtype, c.b, c.s, c.h, c.d, c.window, gq.ld, go.ld, gd.ld, 3 * cc,
                           (gq.view.data_ptr(), go.view.data_ptr(), gd.view.data_ptr(), 0), p, workspace=use_mfma)
     assert rt.kernel == R.backward_expect(c) and rt.win == (rt.mfma and c.window >= 0)
-    dqkv = ops.mhsa_backward(gq.view, go.view, gd.view, lse_st.to(DEV), c.b, c.h, c.window, p, seed, use_mfma=use_mfma)
+    # the library's own plan on the operands of this call; dqkv, delta and the workspace are ops.mhsa_backward's own fresh
+    # allocations (256-byte aligned), the workspace withheld where the case asks for the VALU kernels
+    st, plan = _lib.mhsa_route("backward", dtype=ops.dtype_code(c.dtype), qkv=gq.view.data_ptr(), ld=gq.ld, out=go.view.data_ptr(),
+                               ldo=go.ld, dout=gd.view.data_ptr(), lddo=gd.ld, lse=lse_dev.data_ptr(), delta=256, dqkv=256,
+                               lddq=3 * cc, workspace=256 if use_mfma else 0, B=c.b, S=c.s, H=c.h, D=c.d, window=c.window,
+                               dropout_p=p, dropout_seed=seed)
+    R.assert_same_plan(rt, st, plan, R.case_id(c))
+    dqkv = ops.mhsa_backward(gq.view, go.view, gd.view, lse_dev, c.b, c.h, c.window, p, seed, use_mfma=use_mfma)
     assert dqkv.data_ptr() % 8 == 0
     return dqkv.cpu(), rt
 

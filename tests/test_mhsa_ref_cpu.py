@@ -18,6 +18,11 @@ Cannot be rejected, and said so: a backward whose delta comes from the UNROUNDED
 than the contract (delta from the stored out), so no accuracy bound tells it from a correct kernel; the test asserts that it
 passes.  (The zero-score pad key is invisible on ``pairs`` -- it weighs e^-8 next to the designated keys --, which is why
 ``cold`` exists; a window one too wide is invisible on ``pairs`` for the same reason, which is why ``intruder`` exists.)
+
+The launcher's route: ``anemoi_mhsa_route`` runs the entry points' own validation and plan without a device; its answer is
+compared field by field with the restatement (``_mhsa_ref.route`` / ``route_backward``) on every case of the case lists, on a
+forward sweep of 359 919 and a backward sweep of 399 134 argument sets (about 11 s together), and on both sides of the
+2^31 / 2^32 bounds that no allocation reaches.
 """
 
 import math
@@ -213,6 +218,166 @@ def test_route_and_workspace_against_the_library():
     assert R.route(BF16, 1, 130, 2, 64, -1, 388, 128).kernel == "generic" and R.route(BF16, 1, 130, 2, 64, 5, 392, 136).kernel == "w8"
     assert R.route(BF16, 1, 130, 2, 64, -1, 384, 128, p=1.0).kernel == "generic" and R.route(F32, 1, 9, 2, 64, -1, 384, 128).dmax == 64
     assert R.route_backward(BF16, 1, 9, 2, 32, 3, 192, 64, 64, 192).win and not R.route_backward(BF16, 1, 9, 2, 32, 3, 192, 64, 64, 192, workspace=False).mfma
+
+
+# ------------------------------------------------------------------------------------------------ the library's plan
+# anemoi_mhsa_route runs the entry points' own validation and plan and launches nothing: pointers enter as integers
+FAKE = dict(qkv=1 << 20, out=2 << 20, dout=3 << 20, lse=4 << 20, delta=5 << 20, dqkv=6 << 20, workspace=7 << 20)
+
+
+def _code(dtype):
+    from anemoi_models_amd import _lib
+
+    return _lib.F32 if dtype == F32 else _lib.BF16
+
+
+def _plan_forward(dtype, b, s, h, d, window, ld, ldo, qkv=FAKE["qkv"], out=FAKE["out"], p=0.0, ht=0, workspace=FAKE["workspace"]):
+    from anemoi_models_amd import _lib
+
+    return _lib.mhsa_route("forward", dtype=_code(dtype), qkv=qkv, ld=ld, out=out, ldo=ldo, workspace=workspace, B=b, S=s, H=h, D=d,
+                           window=window, dropout_p=p, dropout_h_total=ht)
+
+
+def _plan_backward(dtype, b, s, h, d, window, ld, ldo, lddo, lddq, ptrs=(FAKE["qkv"], FAKE["out"], FAKE["dout"], FAKE["dqkv"]),
+                   p=0.0, ht=0, workspace=FAKE["workspace"]):
+    from anemoi_models_amd import _lib
+
+    return _lib.mhsa_route("backward", dtype=_code(dtype), qkv=ptrs[0], ld=ld, out=ptrs[1], ldo=ldo, dout=ptrs[2], lddo=lddo,
+                           lse=FAKE["lse"], delta=FAKE["delta"], dqkv=ptrs[3], lddq=lddq, workspace=workspace, B=b, S=s, H=h, D=d,
+                           window=window, dropout_p=p, dropout_h_total=ht)
+
+
+def _same_forward(*args, **kw):
+    """args: dtype, b, s, h, d, window, ld, ldo; kw: qkv, out, p, ht."""
+    rt = R.route(*args, kw.get("qkv", FAKE["qkv"]), kw.get("out", FAKE["out"]), kw.get("p", 0.0), kw.get("ht", 0))
+    R.assert_same_plan(rt, *_plan_forward(*args, **kw), what=f"forward {args} {kw}")
+    return rt
+
+
+def _same_backward(*args, **kw):
+    """args: dtype, b, s, h, d, window, ld, ldo, lddo, lddq; kw: ptrs, p, ht, workspace."""
+    ptrs = kw.get("ptrs", (FAKE["qkv"], FAKE["out"], FAKE["dout"], FAKE["dqkv"]))
+    rt = R.route_backward(*args, ptrs, kw.get("p", 0.0), kw.get("ht", 0), kw.get("workspace", FAKE["workspace"]))
+    R.assert_same_plan(rt, *_plan_backward(*args, **kw), what=f"backward {args} {kw}")
+    return rt
+
+
+def test_the_library_plans_every_case_as_restated():
+    """Forward and backward plan of every case of the three case lists (and the dropout cases), the kernel the case names, the
+    two workspace functions against the plan's layout, and the layout's offsets."""
+    from anemoi_models_amd import _lib
+
+    lib = _lib.load()
+    forward = R.forward_mfma_cases() + R.forward_generic_cases() + R.dropout_cases()
+    # (the backward list names the backward's route; its bf16 "generic" cases are run without a workspace)
+    for i, c in enumerate(forward + R.backward_cases()):
+        cc = c.h * c.d
+        rt = _same_forward(c.dtype, c.b, c.s, c.h, c.d, c.window, 3 * cc + c.pad, cc + c.opad, p=c.p)
+        assert i >= len(forward) or rt.kernel == c.expect, R.case_id(c)
+        if not c.pad:
+            ws = FAKE["workspace"] if R.backward_expect(c) == "mfma" else 0
+            rb = _same_backward(c.dtype, c.b, c.s, c.h, c.d, c.window, 3 * cc, cc, cc, 3 * cc, p=c.p, workspace=ws)
+            assert rb.kernel == R.backward_expect(c), R.case_id(c)
+            assert _same_backward(c.dtype, c.b, c.s, c.h, c.d, c.window, 3 * cc, cc, cc, 3 * cc, p=c.p, workspace=0).kernel == "generic"
+        if rt.mfma:
+            _, plan = _plan_forward(c.dtype, c.b, c.s, c.h, c.d, c.window, 3 * cc + c.pad, cc + c.opad, p=c.p)
+            _, planb = _plan_backward(c.dtype, c.b, c.s, c.h, c.d, c.window, 3 * cc + c.pad, cc, cc, 3 * cc, p=c.p)
+            vt, lo, lb = R.vt_bytes(c.b, c.s, c.h, c.d), plan.layout, planb.layout
+            assert lo.total == lib.anemoi_mhsa_workspace_bytes(_lib.BF16, c.b, c.s, c.h, c.d)
+            assert (lo.vt, lo.tail, lo.flag) == (0, vt, lo.total - 256) and lo.flag - lo.tail >= c.b * rt.tail * c.h * rt.n_split * (c.d + 2) * 4
+            assert lb.total == lib.anemoi_mhsa_backward_workspace_bytes(_lib.BF16, c.b, c.s, c.h, c.d)
+            rows = c.b * c.h * planb.S_pad * 4
+            assert (lb.qt, lb.kt, lb.dot, lb.lse2p, lb.deltap, lb.total) == (0, vt, 2 * vt, 3 * vt, 3 * vt + rows, 3 * vt + 2 * rows)
+
+
+SWEEP_SHAPES = [(dtype, b, s, h, d, w) for dtype in (F32, BF16) for b in (1, 2, 3)
+                for s in (1, 9, 63, 64, 65, 130, 511, 512, 513, 528, 529, 1040) for h in (1, 2, 16) for d in (8, 32, 33, 64, 65, 128)
+                for w in (-1, 0, 5)]
+SWEEP_P = (0.0, 1e-6, 0.1, 1.0)
+FORWARD_STRIDE, BACKWARD_STRIDE = 7, 101  # coprime to the number of combinations (648, 10 368): every one meets many shapes
+
+
+def test_the_library_plans_a_forward_sweep_as_restated():
+    """3888 shapes (dtype x B {1, 2, 3} x S {1 ... 1040, the 512 / 513 / 528 / 529 tail edges} x H {1, 2, 16} x D {8 ... 128} x
+    window {-1, 0, 5}) times every 7th of the 648 combinations of qkv pitch + {0, 4, 8}, out pitch + {0, 2, 4}, qkv pointer +
+    {0, 8, 16} bytes, out pointer + {0, 4, 8}, p {0, 1e-6, 0.1, 1} and heads_total {0, 2 H}, the first combination moving with
+    the shape: 359 919 argument sets."""
+    combos = [(lp, op, qo, oo, p, t) for lp in (0, 4, 8) for op in (0, 2, 4) for qo in (0, 8, 16) for oo in (0, 4, 8)
+              for p in SWEEP_P for t in (0, 2)]
+    n, kernels = 0, set()
+    for i, (dtype, b, s, h, d, w) in enumerate(SWEEP_SHAPES):
+        cc = h * d
+        for lp, op, qo, oo, p, t in combos[i % FORWARD_STRIDE::FORWARD_STRIDE]:
+            rt = _same_forward(dtype, b, s, h, d, w, 3 * cc + lp, cc + op, qkv=FAKE["qkv"] + qo, out=FAKE["out"] + oo, p=p, ht=t * h)
+            kernels.add((rt.kernel, rt.drop, rt.tail > 0))
+            n += 1
+    assert n == 359919 and len(combos) == 648
+    assert kernels == {(k, dr, tl) for k in ("w4", "w8") for dr in (False, True) for tl in (False, True)} | {("generic", False, False), ("generic", True, False)}
+
+
+def test_the_library_plans_a_backward_sweep_as_restated():
+    """The 3888 shapes of the forward sweep times every 101st of the 10 368 combinations of qkv pitch + {0, 4, 8}, qkv pointer +
+    {0, 8, 16} bytes, out pointer + {0, 1, 4}, dout pointer + {0, 8}, dqkv pointer + {0, 4}, dout pitch + {0, 4}, dqkv pitch +
+    {0, 2}, workspace null / off by 8 bytes / aligned, p {0, 1e-6, 0.1, 1} and heads_total {0, 2 H}: 399 134 argument sets."""
+    combos = [(lp, qo, oo, do, gq, dp, gp, ws, p, t) for lp in (0, 4, 8) for qo in (0, 8, 16) for oo in (0, 1, 4) for do in (0, 8)
+              for gq in (0, 4) for dp in (0, 4) for gp in (0, 2) for ws in (0, FAKE["workspace"] + 8, FAKE["workspace"])
+              for p in SWEEP_P for t in (0, 2)]
+    n, kernels = 0, set()
+    for i, (dtype, b, s, h, d, w) in enumerate(SWEEP_SHAPES):
+        cc = h * d
+        for lp, qo, oo, do, gq, dp, gp, ws, p, t in combos[i % BACKWARD_STRIDE::BACKWARD_STRIDE]:
+            ptrs = (FAKE["qkv"] + qo, FAKE["out"] + oo, FAKE["dout"] + do, FAKE["dqkv"] + gq)
+            rt = _same_backward(dtype, b, s, h, d, w, 3 * cc + lp, cc, cc + dp, 3 * cc + gp, ptrs=ptrs, p=p, ht=t * h, workspace=ws)
+            kernels.add((rt.kernel, rt.drop, rt.win))
+            n += 1
+    assert n == 399134 and len(combos) == 10368
+    assert kernels == {("mfma", dr, wn) for dr in (False, True) for wn in (False, True)} | {("generic", False, False), ("generic", True, False)}
+
+
+def test_the_32_bit_bounds_of_the_routes():
+    """Shapes no allocation reaches: B x heads x S on either side of 2^32 (the dropout hash's row index), S x ld x 2 on either
+    side of 2^31 (four-wave -> eight-wave kernel), and the backward's B x S, ld and lddo on either side of 2^31."""
+    assert _same_forward(BF16, 65536, 4095, 1, 64, -1, 192, 64, ht=16).kernel == "w4"  # 2^32 - 2^20 rows
+    assert _same_forward(BF16, 65536, 4096, 1, 64, -1, 192, 64, ht=16).kernel == "generic"  # 2^32
+    assert _same_backward(BF16, 65536, 4095, 1, 64, -1, 192, 64, 64, 192, ht=16).kernel == "mfma"
+    assert _same_backward(BF16, 65536, 4096, 1, 64, -1, 192, 64, 64, 192, ht=16).kernel == "generic"
+    assert _same_forward(BF16, 1, (1 << 20) - 512, 1, 64, -1, 1024, 64).kernel == "w4"  # S ld 2 = 2^31 - 2^20
+    assert _same_forward(BF16, 1, 1 << 20, 1, 64, -1, 1024, 64).kernel == "w8"  # = 2^31
+    assert _same_forward(BF16, 1, 1 << 20, 1, 64, -1, 1016, 64).kernel == "w4"
+    assert _same_backward(BF16, 65536, 32767, 1, 64, -1, 192, 64, 64, 192).kernel == "mfma"  # B S = 2^31 - 2^16
+    assert _same_backward(BF16, 65536, 32768, 1, 64, -1, 192, 64, 64, 192).kernel == "generic"  # = 2^31
+    for ld, lddo, kernel in (((1 << 31) - 8, 64, "mfma"), (1 << 31, 64, "generic"), (192, (1 << 31) - 8, "mfma"), (192, 1 << 31, "generic")):
+        assert _same_backward(BF16, 1, 130, 1, 64, -1, ld, 64, lddo, 192).kernel == kernel
+
+
+def test_what_the_route_query_refuses():
+    """The query answers with the entry point's own status and text: the forward refuses an MFMA call without a workspace, the
+    backward takes the VALU kernels instead; D = 129; the backward's seed message names the backward."""
+    import ctypes
+
+    from anemoi_models_amd import _lib
+
+    err = _lib.load().anemoi_last_error
+    st, _ = _plan_forward(BF16, 1, 130, 2, 64, -1, 384, 128, workspace=0)
+    assert st == _lib.ANEMOI_ERR_INVALID and err() == b"anemoi_mhsa: workspace of %d bytes required" % R.workspace_bytes(BF16, 1, 130, 2, 64)
+    st, plan = _plan_forward(BF16, 1, 130, 2, 64, -1, 388, 128, workspace=0)  # off the MFMA route: none needed
+    assert st == 0 and plan.kernel == _lib.MHSA_KERNEL_GENERIC and plan.layout.total == 0
+    st, plan = _plan_backward(BF16, 1, 130, 2, 64, -1, 384, 128, 128, 384, workspace=0)
+    assert st == 0 and plan.kernel == _lib.MHSA_KERNEL_GENERIC
+    st, _ = _plan_forward(F32, 1, 4, 1, 129, -1, 387, 129)
+    assert st == _lib.ANEMOI_ERR_UNSUPPORTED and err() == b"anemoi_mhsa: head size 129 > 128"
+    st, _ = _plan_backward(F32, 1, 4, 1, 129, -1, 387, 129, 129, 387, p=2.0)  # the backward tests the head size first
+    assert st == _lib.ANEMOI_ERR_UNSUPPORTED and err() == b"anemoi_mhsa_backward: head size 129 > 128"
+    st, _ = _plan_forward(F32, 1, 4, 1, 129, -1, 387, 129, p=2.0)  # the forward the dropout rate
+    assert st == _lib.ANEMOI_ERR_INVALID and b"dropout_p 2 outside [0, 1]" in err()
+    st, _ = _lib.mhsa_route("backward", dtype=_lib.F32, qkv=64, out=64, dout=64, lse=64, delta=64, dqkv=64, ld=24, ldo=8, lddo=8,
+                            lddq=24, B=1, S=4, H=1, D=8, dropout_seed_dev=66)
+    assert st == _lib.ANEMOI_ERR_INVALID and err() == b"anemoi_mhsa_backward: dropout_seed_dev must be 4-byte aligned"
+    st, _ = _lib.mhsa_route("forward", dtype=2, qkv=64, out=64, ld=24, ldo=8, B=1, S=4, H=1, D=8)
+    assert st == _lib.ANEMOI_ERR_UNSUPPORTED and err() == b"anemoi_mhsa: dtype 2"
+    args, route = _lib.MhsaArgs(), _lib.MhsaRoute()
+    args.struct_bytes, route.struct_bytes = ctypes.sizeof(_lib.MhsaArgs), ctypes.sizeof(_lib.MhsaRoute) - 8
+    assert _lib.load().anemoi_mhsa_route(ctypes.byref(args), ctypes.byref(route)) == _lib.ANEMOI_ERR_INVALID and b"out of sync" in err()
 
 
 def test_wrappers_refuse_operands_that_do_not_fit_before_any_launch():
